@@ -26,6 +26,7 @@ BASELINE.json configs[2], [3] (one GPU's share), [4] (one GPU's share), each beh
 skips them).
 
 Prints ONE JSON line (rank 0).  value = scored (query,candidate) pairs per second, whole job.
+--dump-outputs DIR writes the ranked rows of the last timed step as DIR/<name>.npy (see reduce_outputs), to compare two builds.
 """
 import argparse
 import json
@@ -459,6 +460,44 @@ def _spot_check(model, om, queries, arrays, op, n, rescore=None):
         if [v for v, _d, _f in got] != [v for v, _d, _f in exp] or any(abs(a[1] - b[1]) > 1e-6 or abs(a[2] - b[2]) > 1e-6 for a, b in zip(got, exp)):
             raise RuntimeError(f"parity spot check failed on {queries[i]!r}: {got[:3]} vs {exp[:3]}")
     return f"ok ({n} queries vs the oracle)"
+
+
+DUMP_SAMPLE_QUERIES = 131072  # --dump-outputs: queries whose ranked rows are written (fixed seed; all of them for smaller batches)
+DUMP_SAMPLE_SEED = 7
+
+
+def reduce_outputs(arrays, width):
+    """The CSR rows of a finished batch (fetch_arrays) -> the float arrays --dump-outputs writes: the ranked rows of a fixed, seeded
+    sample of queries padded to `width` (vocab_id -1 and scores 0 past a query's last row) with their row counts, and totals over
+    the whole batch (rows, sums of vocab ids, dist scores and freq scores).  At most 37 MB, whatever the batch size."""
+    import numpy as np
+    off, vid, dist, freq = arrays
+    n = len(off) - 1
+    counts = np.diff(off)
+    if n > DUMP_SAMPLE_QUERIES:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_QUERIES, replace=False))
+    else:
+        idx = np.arange(n)
+    if len(idx) and int(counts[idx].max()) > width:
+        raise RuntimeError(f"--dump-outputs: a query has {int(counts[idx].max())} rows, more than max_matches + 1 = {width}")
+    out = {"totals": np.array([float(off[-1]), float(vid.sum(dtype=np.float64)), float(dist.sum(dtype=np.float64)), float(freq.sum(dtype=np.float64))]),
+           "query_index": idx.astype(np.float64), "n_matches": counts[idx].astype(np.float64),
+           "vocab_id": np.full((len(idx), width), -1.0), "dist_score": np.zeros((len(idx), width)), "freq_score": np.zeros((len(idx), width))}
+    rows = np.arange(width)
+    take = rows[None, :] < counts[idx][:, None]             # (sample, width): slot holds a row
+    src = (off[idx][:, None] + rows[None, :])[take]          # those rows' positions in the CSR arrays
+    out["vocab_id"][take] = vid[src]
+    out["dist_score"][take] = dist[src]
+    out["freq_score"][take] = freq[src]
+    return out
+
+
+def write_outputs(out_dir, outputs):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(f"{name}.npy" for name in outputs)
 
 
 def _profile_traffic(profile_key, kernel):
@@ -1018,9 +1057,15 @@ def main():
     ap.add_argument("--preroll-s", type=float, default=2.5, help="seconds of untimed steady-state steps before the timed region (lets an external "
                     "GPU-utilisation sampler see the device busy; 0 with --timed-only)")
     ap.add_argument("--spot-check", type=int, default=256, help="queries of the timed batch (and of every extra configuration) checked against the oracle after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="rank 0: write the ranked rows of the last timed step as DIR/<name>.npy "
+                    "(every query's row count; vocab ids and scores of a fixed, seeded sample of queries), to compare two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.ranks_on_one_gpu:
         args.gpus = args.ranks_on_one_gpu
+    if args.dump_outputs and args.single_process:
+        raise SystemExit("bench.py: --dump-outputs is not supported with --single-process")
     if args.single_process:
         return strong_scaling_job(args) if args.strong else single_process(args)
 
@@ -1202,6 +1247,8 @@ def main():
     barrier(True)
     elapsed = time.perf_counter() - t0
     assert finished[0] == args.steps
+    # the rows the last timed step left in its copy of the batch, before anything after the timed region runs that copy again
+    dumped = reduce_outputs(batches[(args.steps - 1) & 1].fetch_arrays(), stride) if (args.dump_outputs and rank == 0) else None
     sum_scan_kernel_ms, sum_fs_kernel_ms = kernel_ms["ms_scan_kernel"], kernel_ms["ms_filter_score_kernel"]
     # The timed steps overlap (anx_batch_run_async alternates between two streams of the library: the scan of one step runs under
     # the tail of the previous one), so the HIP-event times of their kernels include the time they share the GPU.  The roofline
@@ -1421,6 +1468,9 @@ def main():
                 out["single_process_strong"] = json.loads(r_.stdout.strip().splitlines()[-1]) if r_.returncode == 0 else {"error": (r_.stderr or r_.stdout)[-600:]}
             except Exception as e_:  # noqa: BLE001
                 out["single_process_strong"] = {"error": repr(e_)[:300]}
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": write_outputs(args.dump_outputs, dumped),
+                                   "sampled_queries": len(dumped["query_index"])}
         print(json.dumps(out))
     if use_dist:
         dist.barrier()

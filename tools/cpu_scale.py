@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from analiticcl_amd import synth
 from oracle import cwrap as O
 d = synth.materialize_golden("/tmp/anxdata")

@@ -1,8 +1,8 @@
 """Round-2 experiment (CPU, numpy): how many 64-signature blocks of a tile window pass a bounding-box test, with the signatures in
 numeric order and in a k-d order (boxes as tight as a median split makes them), for 6 / 7 / 8 signature groups.  Needs /tmp/Q.npy,
 /tmp/L.npy (count vectors and lengths of the bench queries, tools/tilesim.py).  Result: 78-87 % of the blocks pass either way."""
-import sys, collections, time
-sys.path.insert(0, "/root/repo")
+import os, sys, collections, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from analiticcl_amd import synth
 from oracle import twin as T

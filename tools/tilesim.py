@@ -1,5 +1,5 @@
-import sys, time, collections
-sys.path.insert(0, "/root/repo")
+import os, sys, time, collections
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from analiticcl_amd import synth
 from oracle import twin as T
