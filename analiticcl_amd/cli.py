@@ -1,10 +1,13 @@
-"""`python -m analiticcl_amd query|search ...` -- the `analiticcl query` / `analiticcl search` command line
+"""`python -m analiticcl_amd query|search|learn ...` -- the `analiticcl query` / `search` / `learn` command line
 (/root/reference/src/bin/analiticcl.rs) on top of the MI355X engine.
 
 Same option names and defaults (note the CLI's own weight defaults 0.5/0.125/0.125/0.125/0.125, bin:760-800, and
 k=3 d=2 n=10, bin:800-817), same TSV / JSON output (bin:21-187).  `query` reads one input per line and runs every
 `--batch-size` lines as ONE device batch (the reference: 1000-line rayon batches, bin:416-448); `search` groups lines
-into texts like bin:561-636 and decodes them with find_all_matches.  Not mirrored: learn / index modes,
+into texts like bin:561-636 and decodes them with find_all_matches.  `learn` (bin:484-553) reads the whole input, runs
+`--iterations` rounds of learn_variants over it (`--strict`: one string per line, find_variants; otherwise one text per line,
+find_all_matches) and writes the weighted variant list (bin:186-365; `-O`: one file per lexicon, with the reference's selection
+and field quirks).  Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
 (the flag is looked up under the wrong name, bin:1175), has no effect; `--allow-overlap`, `--lm-order` and `--weight-context` are
@@ -85,7 +88,7 @@ def json_item(inp: str, variants: Optional[List[dict]], seqnr: int, offset=None,
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m analiticcl_amd", description=__doc__.split("\n\n")[0])
-    p.add_argument("mode", choices=["query", "search"])
+    p.add_argument("mode", choices=["query", "search", "learn"])
     p.add_argument("files", nargs="*", help="input files (default: standard input)")
     p.add_argument("--lexicon", "-l", action="append", default=[])
     p.add_argument("--variants", "-V", action="append", default=[])
@@ -129,6 +132,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight-context", type=float, default=0.0, help="accepted for compatibility, no effect (as in the reference)")
     p.add_argument("--devices", default=None, help="comma-separated HIP device ordinals: one replica of the lexicon per device, batches are "
                                                     "sharded over them inside this process (the reference's rayon fan-out, bin:445-448)")
+    p.add_argument("--iterations", "-I", type=int, default=1,
+                   help="learn mode: the number of iterations to use for learning (more iterations cover more edit distance)")
+    p.add_argument("--multi-output", "-O", action="store_true",
+                   help="learn mode: write one weighted variant list per input lexicon (<lexicon>.variants.tsv / .json) instead of "
+                        "to standard output")
+    p.add_argument("--strict", action="store_true",
+                   help="learn mode: the input is itself a list or lexicon, one item per line (find_variants instead of search)")
     return p
 
 
@@ -304,11 +314,83 @@ def run_search(model, params, a, out) -> None:
         progress.show(seqnr, nmatches)  # bin:631-634
 
 
+def _all_lines(files) -> List[str]:
+    """BufRead::lines over the whole input: without the "\n" / "\r\n" line ends."""
+    out = []
+    for line in _lines(files):
+        out.append(line[:-1] if line.endswith("\r") else line)
+    return out
+
+
+def _variant_refs(model):
+    """(item text, [(variant text, score, freq, lexindex)]) of every item with ReferenceFor links, in vocabulary order."""
+    for vid in range(model.vocab_size()):
+        refs = [(t, sc) for kind, t, sc in model.variants(vid) if kind == "ReferenceFor"]
+        if refs:
+            yield model.vocab_text(vid), [(model.vocab_text(t), sc, model.vocab_frequency(t), model.vocab_lexindex(t)) for t, sc in refs]
+
+
+def write_multi_output(model, json: bool, out) -> None:
+    """output_weighted_variants_as_tsv / _as_json with --multi-output (bin:197-233, 271-315): standard output gets the item lines,
+    <lexicon>.variants.{tsv,json} the variants.  Kept as the reference writes them: the TSV picks lexicon i when
+    `lexindex & (1 << i) == i << i` (Rust precedence: bit 0 clear selects file 0, bit 1 set file 1, never a file >= 2), the JSON
+    puts the frequency under "score" and the score under "freq", with no line ends in the files."""
+    files = {}
+
+    def fh(i):
+        if i not in files:
+            files[i] = open(f"{model.lexicons[i]}.variants.{'json' if json else 'tsv'}", "w", encoding="utf-8", newline="")
+        return files[i]
+
+    try:
+        if json:
+            out.write("{\n")
+        for text, refs in _variant_refs(model):
+            out.write('    "%s": [ \n' % _esc(text) if json else text)
+            for vtext, score, freq, lexindex in refs:
+                for i in range(len(model.lexicons)):
+                    if json and lexindex & (1 << i) == 1 << i:
+                        fh(i).write('        { "text": "%s",  "score": %d, "freq": %s }, ' % (_esc(vtext), freq, rust_f64(score)))
+                    elif not json and (lexindex & (1 << i)) == (i << i):
+                        fh(i).write(f"\t{vtext}\t{rust_f64(score)}\t{freq}\n")
+            out.write("    ]\n" if json else "\n")
+        if json:
+            out.write("}\n")
+    finally:
+        for f in files.values():
+            f.close()
+
+
+def run_learn(model, params, a, out) -> None:
+    """process_learn (bin:484-553): all lines at once, up to --iterations rounds (each rebuilds the model), then the variant list."""
+    lines = _all_lines(a.files)
+    for i in range(a.iterations):
+        count = model.learn_variants(lines, params, strict=a.strict, auto_build=True)
+        if a.strict:
+            sys.stderr.write(f"(Iteration #{i + 1}: learned {count} variants (out of a total of {len(lines)} input strings)\n")
+        else:
+            sys.stderr.write(f"(Iteration #{i + 1}: learned {count} variants\n")
+        if count == 0 and i + 1 < a.iterations:
+            sys.stderr.write("(Halting further iterations)\n")
+            break
+    if a.multi_output:
+        write_multi_output(model, a.json, out)
+    else:
+        out.write(model.variant_list_output(a.json))
+    out.flush()
+
+
 def main(argv=None) -> int:
     a = build_parser().parse_intermixed_args(argv)
+    if a.mode == "learn" and not 0 <= a.iterations <= 255:
+        sys.stderr.write("ERROR: --iterations must be in 0..255\n")
+        return 2
     model = make_model(a)
     params = make_params(a)
     out = sys.stdout
+    if a.mode == "learn":
+        run_learn(model, params, a, out)
+        return 0
     if a.json:
         out.write("[\n")
     (run_query if a.mode == "query" else run_search)(model, params, a, out)

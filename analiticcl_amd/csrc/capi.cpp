@@ -95,6 +95,8 @@ struct anx_model {
   anx::DeviceLexicon* dev = nullptr;   // == replicas[0].dev
   std::vector<Replica> replicas;
   mutable LengthCost len_cost;
+  void* learn_vocab = nullptr;                 // learn mode's vocabulary table on replica 0's device (learn.hip via learn_capi.cpp)
+  void (*learn_vocab_release)(void*) = nullptr;
 };
 struct anx_batch {
   const anx_model* model = nullptr;
@@ -280,6 +282,8 @@ static void drop_replicas(anx_model* m) {
   }
   m->replicas.clear();
   m->dev = nullptr;
+  if (m->learn_vocab_release) m->learn_vocab_release(m->learn_vocab);
+  m->learn_vocab = nullptr;
 }
 void anx_model_free(anx_model* m) {
   if (!m) return;
@@ -1822,4 +1826,186 @@ void anx_results_free(anx_result* rows, size_t* offsets) {
   free(offsets);
 }
 
+}  // extern "C"
+
+// ---- learn mode (src/lib.rs:1029-1139) --------------------------------------------------------------------------------------------------
+// non-strict: find_all_matches' selected variants, which the search path already returns to the host, go through the host fold;
+// strict mode (the device fold) is learn_capi.cpp.  Statistics, the rebuild and the host fold live here.
+namespace {
+std::atomic<uint64_t> g_learn_stats[4];  // device folds, host folds, rows folded, ReferenceFor links added
+double g_learn_ms[6];                    // the last call: batch (encode + run + gather), device fold, host fold, host apply, build, upload
+std::mutex g_learn_mu;
+using LearnClock = std::chrono::steady_clock;
+double ms_since(LearnClock::time_point t0) { return std::chrono::duration<double, std::milli>(LearnClock::now() - t0).count(); }
+
+int check_rows(const anx_model* m, size_t n, const anx_result* rows, const size_t* off) {
+  if (off[0] != 0) return fail(ANX_EINVAL, "offsets must start at 0");
+  for (size_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return fail(ANX_EINVAL, "offsets must not decrease");
+  const size_t V = m->host.decoder.size();
+  for (size_t r = 0; r < off[n]; ++r)
+    if (rows[r].vocab_id >= V) return fail(ANX_EINVAL, "a row refers to a vocabulary id that does not exist");
+  return ANX_OK;
+}
+uint64_t host_fold(anx_model* m, const char* const* text, size_t n, const anx_result* rows, const size_t* off, double* ms) {
+  const auto t0 = LearnClock::now();
+  const uint64_t before = m->host.learn_refs_added;
+  const uint64_t c = m->host.learn_fold(text, n, rows, off);
+  g_learn_stats[1] += 1;
+  g_learn_stats[2] += off[n];
+  g_learn_stats[3] += m->host.learn_refs_added - before;
+  *ms = ms_since(t0);
+  return c;
+}
+// auto_build: build() and the upload to the devices the model was on (replicas included)
+int learn_rebuild(anx_model* m, double* ms_build, double* ms_upload) {
+  std::vector<int> devs;
+  for (const Replica& r : m->replicas) devs.push_back(r.device);
+  auto t0 = LearnClock::now();
+  std::string err;
+  const int rc = m->host.build_index(err);
+  *ms_build = ms_since(t0);
+  if (rc) return fail(rc, err);
+  t0 = LearnClock::now();
+  drop_replicas(m);
+  const int rc2 = devs.empty() ? ANX_OK : anx_model_to_devices(m, devs.data(), (int)devs.size());
+  *ms_upload = ms_since(t0);
+  return rc2;
+}
+}  // namespace
+
+// what learn_capi.cpp (strict mode: the device fold) needs of the model and of a batch
+anx::HostModel& anx_learn_host(anx_model* m) { return m->host; }
+void** anx_learn_vocab_slot(anx_model* m, void (*release)(void*)) { m->learn_vocab_release = release; return &m->learn_vocab; }
+std::mutex& anx_learn_mutex() { return g_learn_mu; }
+uint64_t anx_learn_host_fold(anx_model* m, const char* const* text, size_t n, const anx_result* rows, const size_t* off, double* ms) {
+  return host_fold(m, text, n, rows, off, ms);
+}
+void anx_learn_count_device_fold(uint64_t rows, uint64_t refs) { g_learn_stats[0] += 1; g_learn_stats[2] += rows; g_learn_stats[3] += refs; }
+int anx_learn_finish(anx_model* m, int auto_build, double* ms) {
+  const int rc = auto_build ? learn_rebuild(m, &ms[4], &ms[5]) : ANX_OK;
+  memcpy(g_learn_ms, ms, sizeof g_learn_ms);
+  return rc;
+}
+bool anx_batch_host_rescored(const anx_batch* b) { return b->rescore; }
+size_t anx_batch_rows(const anx_batch* b) {
+  size_t r = 0;
+  for (const Shard& s : b->shards) r += anx::batch_n_results(s.b);
+  return r;
+}
+int anx_learn_fail(int code, const std::string& msg) { return fail(code, msg); }
+int anx_learn_code() { return g_code; }
+
+extern "C" {
+int anx_learn_variants_search(anx_model* m, const char* const* texts, size_t n, const anx_search_params* p, int auto_build, uint64_t* count) {
+  if (!m || (!texts && n) || !p || !count) return fail(ANX_EINVAL, "NULL argument");
+  for (size_t i = 0; i < n; ++i)
+    if (!texts[i]) return fail(ANX_EINVAL, "NULL input");
+  std::lock_guard<std::mutex> lk(g_learn_mu);
+  double ms[6] = {0, 0, 0, 0, 0, 0};
+  anx_search_params sp = *p;
+  sp.unicodeoffsets = 0;  // byte offsets: the matched text is sliced out of the input below
+  anx_match* mt = nullptr;
+  size_t* mo = nullptr;
+  anx_result* rows = nullptr;
+  size_t nrows = 0;
+  const auto t0 = LearnClock::now();
+  int rc = anx_find_all_matches_batch(m, texts, n, &sp, &mt, &mo, &rows, &nrows, nullptr);
+  if (rc) return rc;
+  ms[0] = ms_since(t0);
+  // find_variants_for_learning, non-strict (src/lib.rs:1046-1062): the selected variant of every match, paired with match.text
+  std::vector<std::string> strs;
+  std::vector<anx_result> sel;
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = mo[i]; k < mo[i + 1]; ++k) {
+      const anx_match& x = mt[k];
+      if (x.selected < 0 || x.var_begin + (uint64_t)x.selected >= x.var_end) continue;
+      strs.emplace_back(texts[i] + x.begin, x.end - x.begin);
+      sel.push_back(rows[x.var_begin + (uint64_t)x.selected]);
+    }
+  anx_matches_free(mt, mo, rows, nullptr);
+  std::vector<const char*> ptrs(strs.size());
+  std::vector<size_t> off(strs.size() + 1);
+  for (size_t k = 0; k < strs.size(); ++k) { ptrs[k] = strs[k].c_str(); off[k + 1] = k + 1; }
+  *count = host_fold(m, ptrs.data(), ptrs.size(), sel.data(), off.data(), &ms[2]);
+  return anx_learn_finish(m, auto_build, ms);
+}
+
+int anx_learn_apply_rows(anx_model* m, const char* const* utf8, size_t n, const anx_result* rows, const size_t* offsets, uint64_t* count) {
+  if (!m || (!utf8 && n) || !offsets || (!rows && offsets[n]) || !count) return fail(ANX_EINVAL, "NULL argument");
+  for (size_t i = 0; i < n; ++i)
+    if (!utf8[i]) return fail(ANX_EINVAL, "NULL input");
+  if (int rc = check_rows(m, n, rows, offsets)) return rc;
+  std::lock_guard<std::mutex> lk(g_learn_mu);
+  double ms = 0;
+  *count = host_fold(m, utf8, n, rows, offsets, &ms);
+  return ANX_OK;
+}
+
+int64_t anx_model_variants(const anx_model* m, uint64_t id, uint8_t* kinds, uint64_t* ids, double* scores, size_t cap) {
+  if (!m) return fail(ANX_EINVAL, "NULL model");
+  if (id >= m->host.decoder.size()) return fail(ANX_EINVAL, "no such vocabulary id");
+  const std::vector<anx::VariantRef>& v = m->host.decoder[id].variants;
+  for (size_t k = 0; k < v.size() && k < cap; ++k) {
+    if (kinds) kinds[k] = v[k].variant_of ? 1 : 0;
+    if (ids) ids[k] = v[k].id;
+    if (scores) scores[k] = v[k].score;
+  }
+  return (int64_t)v.size();
+}
+uint32_t anx_model_vocab_type(const anx_model* m, uint64_t id) {
+  return (m && id < m->host.decoder.size()) ? m->host.decoder[id].vocabtype : 0;
+}
+
+// output_weighted_variants_as_tsv / _as_json without --multi-output (src/bin/analiticcl.rs:233-269, 317-365): decoder order, the
+// ReferenceFor entries of every item; the JSON keeps the reference's trailing commas
+int anx_format_variant_list(const anx_model* m, int json, char** out) {
+  if (!m || !out) return fail(ANX_EINVAL, "NULL argument");
+  const anx::HostModel& h = m->host;
+  std::string o;
+  if (json) o += "{\n";
+  for (const anx::VocabEntry& e : h.decoder) {
+    bool first = true;
+    for (const anx::VariantRef& r : e.variants) {
+      if (r.variant_of || r.id >= h.decoder.size()) continue;
+      const anx::VocabEntry& t = h.decoder[r.id];
+      if (json) {
+        if (first) { o += "    \""; append_json_escaped(o, e.text.c_str()); o += "\": [ \n"; }
+        o += "        { \"text\": \"";
+        append_json_escaped(o, t.text.c_str());
+        o += "\", \"score\": ";
+        append_rust_f64(o, r.score);
+        o += ", \"freq\": ";
+        o += std::to_string(t.frequency);
+        o += " }, \n";
+      } else {
+        if (first) o += e.text;
+        o += '\t';
+        o += t.text;
+        o += '\t';
+        append_rust_f64(o, r.score);
+      }
+      first = false;
+    }
+    if (!first) o += json ? "    ]\n" : "\n";
+  }
+  if (json) o += "}\n";
+  char* buf = static_cast<char*>(malloc(o.size() + 1));
+  if (!buf) return fail(ANX_EINVAL, "out of memory");
+  memcpy(buf, o.data(), o.size() + 1);
+  *out = buf;
+  return ANX_OK;
+}
+
+int anx_debug_learn_stats(uint64_t* out) {
+  if (!out) return fail(ANX_EINVAL, "NULL argument");
+  for (int i = 0; i < 4; ++i) out[i] = g_learn_stats[i].load();
+  return ANX_OK;
+}
+int anx_debug_learn_times(double* out) {
+  if (!out) return fail(ANX_EINVAL, "NULL argument");
+  std::lock_guard<std::mutex> lk(g_learn_mu);
+  memcpy(out, g_learn_ms, sizeof g_learn_ms);
+  return ANX_OK;
+}
 }  // extern "C"

@@ -127,6 +127,18 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& i
                    uint32_t* out_n, uint32_t* out_syms, std::string& err);
 void batch_free(Batch*);
 
+// ---- learn mode's fold on the device (learn.hip) ------------------------------------------------------------------------------------
+struct LearnVocab;  // vocabulary hash table of one device (text hash -> id): built on first use, rebuilt when the vocabulary size changes
+void learn_vocab_free(LearnVocab*);
+// one compact export section (anx_batch_gather_compact layout) on the fold's device: u32 offsets[n + 1] padded to 16 bytes, then the
+// records; its inputs are the call's inputs lo + j, or idx[j] (host array) when idx is set
+void* learn_device_alloc(int device, size_t bytes);  // the gather buffers of a learn call (nullptr: out of memory / HIP error)
+void learn_device_free(int device, void* p);
+struct LearnSection { const void* base; size_t n; size_t lo; const uint32_t* idx; };
+// the fold of n inputs (blob[soff[i] .. soff[i+1] - 1) + NUL, host memory) over the n_rows rows of the sections, on `device`
+int learn_fold_device(const HostModel& m, int device, LearnVocab** vocab, const char* blob, const uint32_t* soff, size_t n,
+                      const std::vector<LearnSection>& secs, size_t n_rows, LearnFold& out, std::string& err);
+
 // ---- search mode in one device pass (lattice.hip): the lattices are built on the device from the rows of the part's batches --------------
 // What the host knows without any result: the segments ("matches") of every stretch, in the order of the stretch's match list
 // (order-major), the states they connect, and the layout of the arcs ("groups", listed per destination state in (source state,

@@ -351,13 +351,18 @@ int HostModel::add_variant(uint64_t ref_id, const char* variant, double score, b
                            const anx_vocab_params& p, uint8_t lexicon_index) {
   if (ref_id >= decoder.size()) return ANX_EINVAL;
   const uint64_t variantid = add_to_vocabulary(variant, has_freq, freq, p, lexicon_index);
+  return link_by_id(ref_id, variantid, score) ? 1 : 0;
+}
+
+int HostModel::link_by_id(uint64_t ref_id, uint64_t variantid, double score, bool ref_side) {
   if (variantid == ref_id) return 0;
   built = false;
-  {  // link reference to variant: only the first mention counts
+  int rc = 1;
+  if (ref_side) {  // link reference to variant: only the first mention counts
     VocabEntry& r = decoder[ref_id];
     bool dup = false;
     for (const VariantRef& x : r.variants) dup |= !x.variant_of && x.id == variantid;
-    if (!dup) r.variants.push_back(VariantRef{false, variantid, score});
+    if (!dup) { r.variants.push_back(VariantRef{false, variantid, score}); rc = 3; }
     r.has_variants = true;
   }
   {  // link variant to reference; the reference compares the stored id with `variantid` (src/lib.rs:502-505)
@@ -367,7 +372,94 @@ int HostModel::add_variant(uint64_t ref_id, const char* variant, double score, b
     if (!dup) v.variants.push_back(VariantRef{true, ref_id, score});
     v.has_variants = true;
   }
-  return 1;
+  return rc;
+}
+
+// learn_variants (src/lib.rs:1102-1129): new strings enter as TRANSPARENT (not INDEXED: build() never hashes them), lexicon index 0,
+// frequency 1 with FrequencyHandling::Max; a known string gains 1 per run of consecutive rows (inputs without rows do not break a run)
+static anx_vocab_params learn_vocab_params() {
+  anx_vocab_params p;
+  anx_default_vocab_params(&p);
+  p.vocab_type = ANX_VOCAB_TRANSPARENT;
+  p.freq_handling = ANX_FREQ_MAX;
+  return p;
+}
+
+uint64_t HostModel::learn_fold(const char* const* text, size_t n, const anx_result* rows, const size_t* off) {
+  const anx_vocab_params vp = learn_vocab_params();
+  uint64_t count = 0;
+  const char* prev = nullptr;
+  for (size_t i = 0; i < n; ++i) {
+    const char* s = text[i] ? text[i] : "";
+    for (size_t r = off[i]; r < off[i + 1]; ++r) {
+      uint64_t id;
+      auto it = encoder.find(s);
+      if (it != encoder.end()) {
+        id = it->second;
+        if (!prev || strcmp(prev, s) != 0) decoder[id].frequency += 1;
+      } else {
+        id = add_to_vocabulary(s, true, 1, vp, 0);
+      }
+      if (rows[r].vocab_id != id) {  // (the caller has checked that every row's id exists)
+        if (link_by_id(rows[r].vocab_id, id, rows[r].dist_score) == 3) ++learn_refs_added;
+        ++count;
+      }
+      prev = s;
+    }
+  }
+  built = false;
+  return count;
+}
+
+uint64_t HostModel::learn_apply(const char* const* text, size_t n, const LearnFold& f, std::string& err) {
+  const anx_vocab_params vp = learn_vocab_params();
+  const size_t V = decoder.size();
+  for (uint32_t s : f.new_src)
+    if (s >= n) { err = "learn fold: input index out of range"; return UINT64_MAX; }
+  for (const LearnLink& l : f.var_of)
+    if (l.ref >= V + f.new_src.size() || l.var >= V + f.new_src.size()) { err = "learn fold: vocabulary id out of range"; return UINT64_MAX; }
+  for (uint32_t id : f.freq_id)
+    if (id >= V) { err = "learn fold: vocabulary id out of range"; return UINT64_MAX; }
+  // links of the entries as they were before the call: the only ones the device could not check
+  std::vector<uint32_t> before(V);
+  for (size_t k = 0; k < V; ++k) before[k] = (uint32_t)decoder[k].variants.size();
+  decoder.reserve(V + f.new_src.size());
+  encoder.reserve(encoder.size() + f.new_src.size());
+  std::vector<int16_t> codes;
+  for (size_t k = 0; k < f.new_src.size(); ++k) {  // add_to_vocabulary of a string the device found in no entry
+    VocabEntry e;
+    e.text = text[f.new_src[k]] ? text[f.new_src[k]] : "";
+    if (alphabet.scan(e.text.data(), e.text.size(), codes)) {
+      e.norm.resize(codes.size());
+      for (size_t i = 0; i < codes.size(); ++i) e.norm[i] = (uint8_t)(codes[i] >= 0 ? codes[i] : alphabet.size() + 1);
+    }
+    e.frequency = f.new_freq[k];
+    e.tokencount = (uint8_t)(std::count(e.text.begin(), e.text.end(), ' ') + 1);
+    e.lexindex = 1u;  // lexicon index 0
+    e.vocabtype = vp.vocab_type;
+    if (!encoder.emplace(e.text, decoder.size()).second) { err = "learn fold: a new string was already in the vocabulary"; return UINT64_MAX; }
+    decoder.push_back(std::move(e));
+  }
+  for (size_t k = 0; k < f.freq_id.size(); ++k) decoder[f.freq_id[k]].frequency += f.freq_delta[k];
+  // every candidate row in flat order; ref_for holds the first mention of each (ref, var) pair of the call, so the reference's
+  // duplicate test only has to look at the links that existed before it
+  size_t j = 0;
+  for (const LearnLink& l : f.var_of) {
+    const bool first = j < f.ref_for.size() && f.ref_for[j].pos == l.pos;
+    if (first) {
+      ++j;
+      VocabEntry& r = decoder[l.ref];
+      bool dup = false;
+      for (size_t k = 0; l.ref < V && k < before[l.ref]; ++k) dup |= !r.variants[k].variant_of && r.variants[k].id == l.var;
+      if (!dup) { r.variants.push_back(VariantRef{false, l.var, l.score}); ++learn_refs_added; }
+      r.has_variants = true;
+    }
+    VocabEntry& v = decoder[l.var];  // VariantOf: the reference's test compares the stored id with the variant's own (never equal)
+    v.variants.push_back(VariantRef{true, l.ref, l.score});
+    v.has_variants = true;
+  }
+  built = false;
+  return f.var_of.size();
 }
 
 int HostModel::read_variants(const char* path, const anx_vocab_params& p0, bool transparent, std::string& err) {
@@ -475,6 +567,7 @@ const SwitchDef kSwitches[] = {
     {"ANX_SEARCH_EARLY_OUTPUT", [](Switches& s, const char* v) { s.search_early_output = flag01(v, 1); }},
     {"ANX_SEARCH_FIRST_PCT", [](Switches& s, const char* v) { const int x = v ? atoi(v) : 0; s.search_first_pct = x >= 10 && x <= 100 ? x : 50; }},
     {"ANX_SEARCH_PARTS_MIN", [](Switches& s, const char* v) { const long x = v ? atol(v) : 0; s.search_parts_min = x > 0 ? x : (2l << 20); }},
+    {"ANX_LEARN_FOLD", [](Switches& s, const char* v) { s.learn_fold_host = v && strcmp(v, "host") == 0; }},
 };
 }  // namespace
 Switches& switches() {

@@ -103,6 +103,7 @@ struct Switches {
   int search_early_output = 1;       // ANX_SEARCH_EARLY_OUTPUT=0: a call's output arrays are written when its last part is done (until round 5)
   int search_first_pct = 50;         // ANX_SEARCH_FIRST_PCT: size of a call's FIRST part in percent of an even share: the device idles until the first part's host phase
                                      // is done (same-box best calls 226-247 MB/s with even parts, 246-263 / 243-273 with 40 / 60 %; medians 222 -> 226 / 232)
+  int learn_fold_host = 0;           // ANX_LEARN_FOLD=host: learn mode folds its rows with the host loop instead of learn.hip (A/B reference)
 };
 Switches& switches();
 // name = the environment variable's name, value = what the variable would hold; false: unknown name
@@ -218,6 +219,18 @@ struct PatternMatchResult {  // src/search.rs:366-371
   uint8_t seqnr;
 };
 
+// Learn mode (src/lib.rs:1029-1139).  One row of the fold: the input string (vocabulary id `var` once resolved) was matched to `ref`
+// with `score` at flat position `pos` (rows flattened in input order, rank order within an input).
+struct LearnLink { uint32_t ref, var; double score; uint32_t pos, pad; };
+// What the device fold (learn.hip) hands back for the host to apply: appends only, no string lookups.
+struct LearnFold {
+  std::vector<uint32_t> new_src;      // per new entry, in id order (ids V, V+1, ...): input index of its first mention
+  std::vector<uint32_t> new_freq;     // ... and its frequency (the runs of its string)
+  std::vector<uint32_t> freq_id, freq_delta;  // entries that existed before the call: frequency increments
+  std::vector<LearnLink> ref_for;     // ReferenceFor appends: first mention of each (ref, var) pair, flat order
+  std::vector<LearnLink> var_of;      // VariantOf appends: every row whose result is not the input itself, flat order (= the count)
+};
+
 class HostModel {
  public:
   std::vector<ContextRule> context_rules;  // src/lib.rs:82
@@ -292,6 +305,15 @@ class HostModel {
   std::string index_tag;  // stored in / read from the index image: what the caller built it from (anx_model_set_index_tag)
   int save_index(const std::string& path, std::string& err) const;  // index_cache.cpp: image of the built model
   int load_index(const std::string& path, std::string& err);        // instead of read_vocabulary + build_index
+  // learn_variants' fold (src/lib.rs:1102-1129), literally: rows[off[i] .. off[i+1]) are the ranked rows of input text[i]; returns the
+  // count (rows whose result is not the input itself).  Leaves built = false.
+  uint64_t learn_fold(const char* const* text, size_t n, const anx_result* rows, const size_t* off);
+  // the same state change from the device fold's arrays (text: the inputs the fold's input indices refer to)
+  uint64_t learn_apply(const char* const* text, size_t n, const LearnFold& f, std::string& err);
+  // add_variant_by_id (src/lib.rs:478-514) for two ids that exist; ref_side = false skips the ReferenceFor half.  0: the ids are the
+  // same (nothing linked), 1: linked, 3: linked and a ReferenceFor appended
+  int link_by_id(uint64_t ref_id, uint64_t variantid, double score, bool ref_side = true);
+  uint64_t learn_refs_added = 0;  // ReferenceFor links the learn folds appended (anx_debug_learn_stats)
   bool has(const char* text) const;   // src/lib.rs:331-338
   // encode one string: norm codes (UNK = len+1), hash-class count vector (UNK = len), symbol count
   bool encode(const char* text, std::vector<uint8_t>& norm, std::vector<uint8_t>& cv) const;

@@ -1,0 +1,139 @@
+// learn_capi.cpp -- anx_learn_variants: strict learn mode (src/lib.rs:1029-1139) with the fold on the device.
+// Every input goes through the batch pipeline (batches of at most ANX_MAX_BATCH inputs per replica); every shard's compact export is
+// gathered onto replica 0's device (anx_batch_gather_compact: the shards of other replicas are copied there), learn.hip folds all of
+// it, and HostModel::learn_apply appends the result.  The statistics, the host fold and the rebuild are capi.cpp's (shared with the
+// non-strict mode and anx_learn_apply_rows).
+#include <chrono>
+#include <cstring>
+#include <deque>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "engine.h"
+#include "host_model.h"
+
+anx::HostModel& anx_learn_host(anx_model* m);
+void** anx_learn_vocab_slot(anx_model* m, void (*release)(void*));
+std::mutex& anx_learn_mutex();
+uint64_t anx_learn_host_fold(anx_model* m, const char* const* text, size_t n, const anx_result* rows, const size_t* off, double* ms);
+void anx_learn_count_device_fold(uint64_t rows, uint64_t refs);
+int anx_learn_finish(anx_model* m, int auto_build, double* ms);
+bool anx_batch_host_rescored(const anx_batch* b);
+size_t anx_batch_rows(const anx_batch* b);
+int anx_learn_fail(int code, const std::string& msg);
+int anx_learn_code();
+
+namespace {
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+void release_vocab(void* p) { anx::learn_vocab_free(static_cast<anx::LearnVocab*>(p)); }
+
+// *host_rows: the rows exist only on the host (confusables weighted there): nothing was folded
+int strict_device(anx_model* m, const char* const* utf8, size_t n, const anx_params* p, const std::vector<char>& blob,
+                  const std::vector<uint32_t>& soff, anx::LearnFold& fold, bool* host_rows, size_t* n_rows, double* ms) {
+  *host_rows = false;
+  const int R = anx_model_num_replicas(m);
+  const int dev0 = anx_model_replica_device(m, 0);
+  const size_t per_round = (size_t)anx::switches().max_batch * (size_t)R;
+  std::vector<void*> bufs;
+  std::vector<anx::LearnSection> secs;
+  std::deque<std::vector<uint32_t>> idx_store;
+  size_t rows = 0;
+  auto release = [&]() { for (void* b : bufs) anx::learn_device_free(dev0, b); };
+  const auto t0 = Clock::now();
+  for (size_t lo = 0; lo < n; lo += per_round) {
+    const size_t cnt = std::min(per_round, n - lo);
+    anx_batch* b = anx_batch_encode(m, utf8 + lo, cnt, p);
+    if (!b) { release(); const int c = anx_learn_code(); return c ? c : ANX_EINVAL; }
+    int rc = anx_batch_run(m, b, nullptr);
+    if (rc == ANX_OK && anx_batch_host_rescored(b)) { *host_rows = true; anx_batch_free(b); release(); return ANX_OK; }
+    size_t need = 0;
+    void* buf = nullptr;
+    if (rc == ANX_OK) {
+      char probe = 0;  // capacity 0: the call only reports the bytes it needs (ANX_ELIMIT)
+      (void)anx_batch_gather_compact(b, dev0, &probe, 0, nullptr, &need);
+      if (!(buf = anx::learn_device_alloc(dev0, need))) rc = anx_learn_fail(ANX_ENODEVICE, "out of device memory for the learn gather");
+      else bufs.push_back(buf);
+    }
+    const int S = anx_batch_num_shards(b);
+    std::vector<size_t> so((size_t)S + 1, 0);
+    size_t used = 0;
+    if (rc == ANX_OK) rc = anx_batch_gather_compact(b, dev0, buf, need, so.data(), &used);
+    for (int g = 0; g < S && rc == ANX_OK; ++g) {
+      size_t first = 0, ns = 0;
+      const uint32_t* idx = nullptr;
+      rc = anx_batch_shard_info(b, g, nullptr, &first, &ns);
+      if (rc == ANX_OK) rc = anx_batch_shard_inputs(b, g, &idx);
+      if (rc) break;
+      if (idx) {  // a length-partitioned shard: its inputs by index, made call-wide
+        idx_store.emplace_back(idx, idx + ns);
+        for (uint32_t& x : idx_store.back()) x += (uint32_t)lo;
+        idx = idx_store.back().data();
+      }
+      secs.push_back(anx::LearnSection{static_cast<char*>(buf) + so[(size_t)g], ns, lo + first, idx});
+    }
+    if (rc == ANX_OK) rows += anx_batch_rows(b);
+    anx_batch_free(b);
+    if (rc) { release(); return rc; }
+  }
+  ms[0] = ms_since(t0);
+  const auto t1 = Clock::now();
+  std::string err;
+  anx::LearnVocab** vocab = reinterpret_cast<anx::LearnVocab**>(anx_learn_vocab_slot(m, release_vocab));
+  const int rc = anx::learn_fold_device(anx_learn_host(m), dev0, vocab, blob.data(), soff.data(), n, secs, rows, fold, err);
+  release();
+  ms[1] = ms_since(t1);
+  *n_rows = rows;
+  return rc ? anx_learn_fail(rc, err) : ANX_OK;
+}
+}  // namespace
+
+extern "C" {
+int anx_learn_variants(anx_model* m, const char* const* utf8, size_t n, const anx_params* p, int auto_build, uint64_t* count) {
+  if (!m || (!utf8 && n) || !p || !count) return anx_learn_fail(ANX_EINVAL, "NULL argument");
+  if (anx_model_num_replicas(m) < 1)
+    return anx_learn_fail(ANX_ENODEVICE, "model is not resident on a device (no HIP device / anx_model_to_device not called)");
+  std::lock_guard<std::mutex> lk(anx_learn_mutex());
+  anx::HostModel& host = anx_learn_host(m);
+  double ms[6] = {0, 0, 0, 0, 0, 0};
+  // the inputs packed for the device fold (each followed by a NUL byte)
+  std::vector<uint32_t> soff(n + 1, 0);
+  size_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (!utf8[i]) return anx_learn_fail(ANX_EINVAL, "NULL input");
+    total += strlen(utf8[i]) + 1;
+    if (total >= 0xFFFFFFFFull) return anx_learn_fail(ANX_ELIMIT, "learn: more than 4 GB of input text in one call");
+    soff[i + 1] = (uint32_t)total;
+  }
+  uint64_t c = 0;
+  bool host_rows = anx::switches().learn_fold_host;
+  if (!host_rows) {
+    std::vector<char> blob(total + 1, 0);
+    for (size_t i = 0; i < n; ++i) memcpy(blob.data() + soff[i], utf8[i], soff[i + 1] - soff[i]);
+    anx::LearnFold fold;
+    size_t rows = 0;
+    if (int rc = strict_device(m, utf8, n, p, blob, soff, fold, &host_rows, &rows, ms)) return rc;
+    if (!host_rows) {
+      const auto t0 = Clock::now();
+      const uint64_t before = host.learn_refs_added;
+      std::string err;
+      c = host.learn_apply(utf8, n, fold, err);
+      if (c == UINT64_MAX) return anx_learn_fail(ANX_EINVAL, err);
+      ms[3] = ms_since(t0);
+      anx_learn_count_device_fold(rows, host.learn_refs_added - before);
+    }
+  }
+  if (host_rows) {  // ANX_LEARN_FOLD=host, or confusables weighted on the host: the rows are on the host, the host fold applies them
+    const auto t0 = Clock::now();
+    anx_result* rows = nullptr;
+    size_t* offs = nullptr;
+    if (int rc = anx_find_variants_batch(m, utf8, n, p, &rows, &offs)) return rc;
+    ms[0] = ms_since(t0);
+    c = anx_learn_host_fold(m, utf8, n, rows, offs, &ms[2]);
+    anx_results_free(rows, offs);
+  }
+  *count = c;
+  return anx_learn_finish(m, auto_build, ms);
+}
+}  // extern "C"

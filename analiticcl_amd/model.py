@@ -741,6 +741,94 @@ class VariantModel:
         return out
 
     # -- context rules of search mode (src/lib.rs:570-765; bindings/python/src/lib.rs:630-700) -------------
+    # -- learn mode (src/lib.rs:1029-1139) ----------------------------------------------------------------------------------------
+    def learn_variants(self, inputs: Sequence[str], params: SearchParameters, strict: bool = True, auto_build: bool = True) -> int:
+        """learn_variants: query every input against the model as it is now, fold the ranked rows into the model (new input strings
+        become TRANSPARENT entries that build() does not index; ReferenceFor links on the results, first mention wins) and return the
+        number of rows whose result was not the input itself.  strict=False: each input is a text, its rows are the selected variants
+        of find_all_matches paired with the matched text.  auto_build: build() and the upload to the model's devices again."""
+        self.__dict__.pop("_vocab_cache", None)
+        n = len(inputs)
+        arr = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
+        count = C.c_uint64(0)
+        if strict:
+            L.check(L.lib().anx_learn_variants(self.h, arr, n, C.byref(params._c()), int(bool(auto_build)), C.byref(count)))
+        else:
+            L.check(L.lib().anx_learn_variants_search(self.h, arr, n, C.byref(params._c_search()), int(bool(auto_build)),
+                                                      C.byref(count)))
+        return count.value
+
+    def learn_apply_rows(self, inputs: Sequence[str], rows: Sequence[Sequence[tuple]]) -> int:
+        """The fold of learn_variants over caller-provided ranked rows (per input: [(vocab_id, dist_score, ...)]), on the host; no
+        build.  -> the count learn_variants would return."""
+        self.__dict__.pop("_vocab_cache", None)
+        n = len(inputs)
+        arr = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
+        off = [0]
+        for r in rows:
+            off.append(off[-1] + len(r))
+        res = (L.Result * max(off[-1], 1))()
+        k = 0
+        for r in rows:
+            for row in r:
+                res[k].vocab_id, res[k].dist_score = int(row[0]), float(row[1])
+                res[k].freq_score = float(row[2]) if len(row) > 2 else 0.0
+                res[k].via = L.ANX_NO_VIA
+                k += 1
+        offs = (C.c_size_t * (n + 1))(*off)
+        count = C.c_uint64(0)
+        L.check(L.lib().anx_learn_apply_rows(self.h, arr, n, res, offs, C.byref(count)))
+        return count.value
+
+    def variants(self, vocab_id: int) -> List[tuple]:
+        """The item's variant references in order: [("ReferenceFor" | "VariantOf", vocab_id, score)]."""
+        lib = L.lib()
+        k = lib.anx_model_variants(self.h, vocab_id, None, None, None, 0)
+        if k < 0:
+            L.check(int(k))
+        if k == 0:
+            return []
+        kinds, ids, scores = (C.c_uint8 * k)(), (C.c_uint64 * k)(), (C.c_double * k)()
+        lib.anx_model_variants(self.h, vocab_id, kinds, ids, scores, k)
+        return [("VariantOf" if kinds[i] else "ReferenceFor", ids[i], scores[i]) for i in range(k)]
+
+    def vocab_size(self) -> int:
+        return L.lib().anx_model_vocab_size(self.h)
+
+    def vocab_frequency(self, vocab_id: int) -> int:
+        return L.lib().anx_model_vocab_frequency(self.h, vocab_id)
+
+    def vocab_lexindex(self, vocab_id: int) -> int:
+        return L.lib().anx_model_vocab_lexindex(self.h, vocab_id)
+
+    def vocabtype(self, vocab_id: int) -> int:
+        """VocabType bits of the item: 1 INDEXED, 2 LM, 4 TRANSPARENT (include/anx.h ANX_VOCAB_*)."""
+        return L.lib().anx_model_vocab_type(self.h, vocab_id)
+
+    def variant_list_output(self, json: bool = False) -> str:
+        """The weighted variant list `analiticcl learn` prints (ReferenceFor links of every item in vocabulary order), as TSV or as
+        the reference's JSON (trailing commas included)."""
+        buf = C.c_void_p()
+        L.check(L.lib().anx_format_variant_list(self.h, int(bool(json)), C.byref(buf)))
+        try:
+            return C.string_at(buf).decode("utf-8")
+        finally:
+            L.lib().anx_string_free(buf)
+
+    @staticmethod
+    def learn_stats() -> dict:
+        """anx_debug_learn_stats: folds that ran on the device / on the host, rows folded, ReferenceFor links added (process totals)."""
+        out = (C.c_uint64 * 4)()
+        L.check(L.lib().anx_debug_learn_stats(out))
+        return {"device_folds": out[0], "host_folds": out[1], "rows": out[2], "links": out[3]}
+
+    @staticmethod
+    def learn_times() -> dict:
+        """The last learn call's phases in ms (anx_debug_learn_times)."""
+        out = (C.c_double * 6)()
+        L.check(L.lib().anx_debug_learn_times(out))
+        return dict(zip(("batch", "device_fold", "host_fold", "host_apply", "build", "upload"), list(out)))
+
     def add_contextrule(self, pattern: str, score: float, tag: Sequence[str] = (), tagoffset: Sequence[str] = ()):
         t = (C.c_char_p * max(1, len(tag)))(*[_b(x) for x in tag])
         o = (C.c_char_p * max(1, len(tagoffset)))(*[_b(x) for x in tagoffset])

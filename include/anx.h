@@ -28,7 +28,9 @@ extern "C" {
  * 3: anx_pipeline_submit_packed NEVER blocks: with `depth` jobs in flight it returns ANX_ELIMIT and submits nothing (until the middle
  *    of ABI 2's life it waited instead -- a binding written against the blocking contract sees failing submits, hence the new
  *    version); anx_batch_encode_packed_device_on (the caller's stream orders the encoder behind the producer of the buffer);
- *    anx_debug_search_stats, anx_debug_small_stats (anx_find_variants_batch's path for small calls); ANX_ADJ_CLOSURE is 0..2 for every builder.  Nothing was removed; every struct of version 2 is unchanged. */
+ *    anx_debug_search_stats, anx_debug_small_stats (anx_find_variants_batch's path for small calls); ANX_ADJ_CLOSURE is 0..2 for every builder.  Nothing was removed; every struct of version 2 is unchanged.
+ *    Added later within version 3 (additive, no struct changed): learn mode (anx_learn_*, anx_model_variants, anx_model_vocab_type,
+ *    anx_format_variant_list, anx_debug_learn_stats / _times). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -459,6 +461,31 @@ int anx_model_add_contextrule(anx_model *, const char *pattern, float score, con
 int anx_model_read_contextrules(anx_model *, const char *path);
 size_t anx_model_num_tags(const anx_model *);
 const char *anx_model_tag_name(const anx_model *, size_t index); /* NULL when out of range */
+
+/* ---- learn mode -------------------------------------------------------------------------------------
+ * VariantModel::learn_variants(inputs, &SearchParameters, strict, auto_build) -> usize, src/lib.rs:1065-1139: every input is queried
+ * against the model as it is at the start of the call, the ranked rows are folded into the model (new input strings become
+ * TRANSPARENT entries of lexicon index 0 -- never indexed by build() --, frequencies count runs of the same string, (result, input)
+ * links: ReferenceFor on the result, first mention wins; VariantOf on the input, appended every time).  *count = rows whose result
+ * is not the input itself.  auto_build: build() and the upload to the model's devices again (replicas included).
+ * anx_learn_variants: strict mode (find_variants per input); the fold runs on replica 0's device (ANX_LEARN_FOLD=host: on the host).
+ * anx_learn_variants_search: non-strict mode (the selected variant of every match of find_all_matches, paired with the matched text).
+ * anx_learn_apply_rows: the fold of caller-provided rows (rows[offsets[i] .. offsets[i+1]) of input i) on the host; no build. */
+int anx_learn_variants(anx_model *, const char *const *utf8, size_t n, const anx_params *, int auto_build, uint64_t *count);
+int anx_learn_variants_search(anx_model *, const char *const *utf8_texts, size_t n, const anx_search_params *, int auto_build,
+                              uint64_t *count);
+int anx_learn_apply_rows(anx_model *, const char *const *utf8, size_t n, const anx_result *rows, const size_t *offsets, uint64_t *count);
+/* an item's variant references (VocabValue::variants, src/types.rs:315-324) in order: kind 0 = ReferenceFor, 1 = VariantOf.  Writes at
+ * most cap entries (any output may be NULL); returns how many there are, negative on error. */
+int64_t anx_model_variants(const anx_model *, uint64_t vocab_id, uint8_t *kinds, uint64_t *ids, double *scores, size_t cap);
+uint32_t anx_model_vocab_type(const anx_model *, uint64_t vocab_id); /* ANX_VOCAB_* bits */
+/* the weighted variant list `analiticcl learn` writes to standard output (src/bin/analiticcl.rs:233-269 TSV, 317-365 JSON): malloc'd,
+ * release with anx_string_free */
+int anx_format_variant_list(const anx_model *, int json, char **out);
+/* out[0] device folds, out[1] host folds, out[2] rows folded, out[3] ReferenceFor links added -- since the library was loaded */
+int anx_debug_learn_stats(uint64_t out[4]);
+/* the last learn call's phases in ms: batch (encode, run, gather), device fold, host fold, host apply, build, upload */
+int anx_debug_learn_times(double out[6]);
 
 #ifdef __cplusplus
 }
