@@ -21,11 +21,15 @@ Other launch forms of the same measurement:
                             device 0, --backend gloo (records staged through pinned host memory) or nccl (if RCCL accepts
                             ranks that share a device); with --check-gather rank 0 compares every rank's gathered export with
                             that rank's own fetch().
-After the timed region (N = 1): "configs" -- the literal metric configuration (nld.aspell, ~200 k entries, len <= 16, d = 2) and
-BASELINE.json configs[2], [3] (one GPU's share), [4] (one GPU's share), each behind a spot check against the oracle (--no-extras
-skips them).
+A plain run sets up, warms up (--warmup steps, then the untimed pre-roll), times the steps, writes --dump-outputs and prints the
+line: nothing runs after the timed region.  --full adds everything else the bench measures and checks after it: the steps once more
+with every kernel alone (serial kernel times, roofline), one resident copy run synchronously, the step with the device encoder, end
+to end, spot checks against the oracle, by_batch_size, the CPU baseline, the gather check (when results are gathered; --check-gather
+asks for it alone), the strong-scaling leg (N > 1) and (N = 1) "configs" -- the literal metric configuration (nld.aspell, ~200 k
+entries, len <= 16, d = 2) and BASELINE.json configs[2], [3] (one GPU's share), [4] (one GPU's share), each behind a spot check
+against the oracle (--no-extras skips them).
 
-Prints ONE JSON line (rank 0).  value = scored (query,candidate) pairs per second, whole job.
+Prints ONE JSON line (rank 0).  value = scored (query,candidate) pairs per second, whole job; what a plain run does not measure is null.
 --dump-outputs DIR writes the ranked rows of the last timed step as DIR/<name>.npy (see reduce_outputs), to compare two builds.
 """
 import argparse
@@ -913,7 +917,7 @@ def single_process(args):
     st = batches[0].stats()
     # shard == whole: replica 0's rows equal those of the same queries run on a one-replica batch
     check = None
-    if not args.timed_only:
+    if args.full and not args.timed_only:
         off, vid, dist_, _f = batches[0].fetch_arrays()
         A.set_switch("ANX_SHARD_MIN", 1 << 30)
         b1 = model.encode_batch(per[-1], params)   # the LAST replica's inputs, on one replica
@@ -934,7 +938,7 @@ def single_process(args):
     st1["n_tests_kind"] = [x / n for x in st["n_tests_kind"]]
     roofline = roofline_of(args, model, per[0], st1, scan_ms, fs_ms, kernel_ms["ms_total"] / steps)
     ncores = usable_cores()
-    cpu = cpu_baseline_of(args, paths, per[0], ncores, 15.0 if n == 1 else 6.0) if (args.cpu_sample != 0 and not args.timed_only) else None
+    cpu = cpu_baseline_of(args, paths, per[0], ncores, 15.0 if n == 1 else 6.0) if (args.full and args.cpu_sample != 0 and not args.timed_only) else None
     out = {
         "metric": baseline_metric(), "value": st["n_pairs"] * args.steps / elapsed, "unit": "pairs/s",
         "queries_per_s": st["n_queries"] * args.steps / elapsed, "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
@@ -1035,31 +1039,36 @@ def main():
     ap.add_argument("--queries", type=int, default=1_000_000)
     ap.add_argument("--max-len", type=int, default=16)
     ap.add_argument("--lexicon", default="eng", choices=["eng", "nld"])
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="queries timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, everything else the bench measures and checks (serial kernel times "
+                    "and roofline, synchronous and with-encoder steps, end to end, oracle spot checks, by_batch_size, CPU baseline, gather check, "
+                    "strong-scaling leg, the other configurations); a plain run stops after the timed steps and --dump-outputs")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="with --full: queries timed on the CPU oracle (0 = skip)")
     ap.add_argument("--anagram-distance", type=int, default=3)
     ap.add_argument("--edit-distance", type=int, default=2)
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--force-gather", action="store_true", help="run the export + gather code at N=1 too (testing)")
-    ap.add_argument("--timed-only", action="store_true", help="skip the passes after the timed region (two-stream overlap, end to end, CPU baseline): for rocprofv3 runs")
-    ap.add_argument("--check-gather", action="store_true", default=True, help="rank 0: compare every rank's gathered export of the last step with that rank's fetch() (default whenever results are gathered)")
+    ap.add_argument("--timed-only", action="store_true", help="no pre-roll; with --full: skip the passes after the timed region (two-stream overlap, end to end, CPU baseline): for rocprofv3 runs")
+    ap.add_argument("--check-gather", action="store_true", default=None, help="rank 0: compare every rank's gathered export of the last step with that rank's fetch() (default with --full whenever results are gathered)")
     ap.add_argument("--no-check-gather", dest="check_gather", action="store_false")
     ap.add_argument("--single-process", action="store_true", help="one process, --gpus N replicas behind the C ABI (anx_model_to_devices)")
     ap.add_argument("--replicas-on-one-gpu", action="store_true", help="with --single-process: all replicas on device 0")
     ap.add_argument("--strong", action="store_true", help="with --single-process: the strong-scaling job (configs[3]'s shape on 1 and on N replicas + the gather) instead of the weak-scaling steps")
     ap.add_argument("--strong-entries", type=int, default=1_000_000)
     ap.add_argument("--strong-queries", type=int, default=4_000_000)
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the single-process strong-scaling leg rank 0 runs after the timed region")
+    ap.add_argument("--no-strong", action="store_true", help="N > 1 with --full: skip the single-process strong-scaling leg rank 0 runs after the timed region")
     ap.add_argument("--ranks-on-one-gpu", type=int, default=0, metavar="N", help="N ranks, all on device 0 (dry run of the N-rank control flow)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of the result gather")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-config numbers measured after the timed region")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the per-config numbers measured after the timed region")
     ap.add_argument("--no-overlap", action="store_true", help="ANX_RUN_OVERLAP=0 for the whole run: every kernel alone on the GPU (rocprofv3 passes: clean per-kernel durations)")
-    ap.add_argument("--extras", default="", help="comma-separated names of the extra configurations to run (default: all)")
+    ap.add_argument("--extras", default="", help="with --full: comma-separated names of the extra configurations to run (default: all)")
     ap.add_argument("--preroll-s", type=float, default=2.5, help="seconds of untimed steady-state steps before the timed region (lets an external "
                     "GPU-utilisation sampler see the device busy; 0 with --timed-only)")
-    ap.add_argument("--spot-check", type=int, default=256, help="queries of the timed batch (and of every extra configuration) checked against the oracle after the timed region")
+    ap.add_argument("--spot-check", type=int, default=256, help="with --full: queries of the timed batch (and of every extra configuration) checked against the oracle after the timed region")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="rank 0: write the ranked rows of the last timed step as DIR/<name>.npy "
                     "(every query's row count; vocab ids and scores of a fixed, seeded sample of queries), to compare two builds output for output")
     args = ap.parse_args()
+    if args.check_gather is None:
+        args.check_gather = args.full
     if args.steps < 1:
         raise SystemExit("bench.py: --steps must be at least 1")
     if args.ranks_on_one_gpu:
@@ -1253,12 +1262,14 @@ def main():
     # The timed steps overlap (anx_batch_run_async alternates between two streams of the library: the scan of one step runs under
     # the tail of the previous one), so the HIP-event times of their kernels include the time they share the GPU.  The roofline
     # uses the kernels' OWN durations: the same steps once more with ANX_RUN_OVERLAP=0 (one stream, no kernel overlaps another) --
-    # which is also how the rocprofv3 passes of profiles/ are taken.
+    # which is also how the rocprofv3 passes of profiles/ are taken.  That pass is part of --full: a plain run reports the roofline
+    # and the stage times only when the timed steps themselves ran serially (--no-overlap).
     overlapped_kernel_ms = {"k_scan_bits": sum_scan_kernel_ms / max(args.steps, 1), "k_filter_score": sum_fs_kernel_ms / max(args.steps, 1)}
     serial_ms = None
+    serial_times = args.full or args.no_overlap
     if args.no_overlap:
         serial_ms = elapsed / max(args.steps, 1) * 1e3
-    elif A.lib().anx_debug_set_switch(b"ANX_RUN_OVERLAP", b"0") == 0:
+    elif args.full and A.lib().anx_debug_set_switch(b"ANX_RUN_OVERLAP", b"0") == 0:
         for k in range(2):
             step(k, stream.cuda_stream, False)
         barrier()
@@ -1279,7 +1290,8 @@ def main():
     # one resident copy, one run at a time (anx_batch_run: launch, wait, launch ...): the like-for-like figure of round 1's records.
     # Measured here, while the GPU is still busy (after the CPU baseline its clocks have dropped).
     sync_ms = None
-    if world == 1 and not do_gather and not args.timed_only:
+    after = args.full and not args.timed_only   # the passes after the timed region
+    if world == 1 and not do_gather and after:
         batches[0].run(stream.cuda_stream)
         t1 = time.perf_counter()
         nsync = max(4, args.steps)
@@ -1292,7 +1304,7 @@ def main():
     # step i + 1 works while the GPU runs step i.  Never `value`: reported next to it.
     with_encode = None
     with_encode_rows = None
-    if world == 1 and not do_gather and not args.timed_only:
+    if world == 1 and not do_gather and after:
         packed_ = ("\0".join(queries) + "\0").encode("utf-8")
         dev_blob = torch.frombuffer(bytearray(packed_), dtype=torch.uint8).cuda()
         live = []
@@ -1381,14 +1393,14 @@ def main():
             stage_ms[k] /= max(args.steps, 1)
         scan_ms, fs_ms = sum_scan_kernel_ms / max(args.steps, 1), sum_fs_kernel_ms / max(args.steps, 1)
         n_classes = model.num_classes()
-        roofline = roofline_of(args, model, queries, st, scan_ms, fs_ms, stage_ms["ms_total"])
-        e2e = e2e_of(args, model, queries, params, stream.cuda_stream, torch) if (world == 1 and not args.timed_only) else None
+        roofline = roofline_of(args, model, queries, st, scan_ms, fs_ms, stage_ms["ms_total"]) if serial_times else None
+        e2e = e2e_of(args, model, queries, params, stream.cuda_stream, torch) if (world == 1 and after) else None
         ncores = usable_cores()
         # parity of the TIMED batch itself: sampled queries of the rows the last timed step left on the device against the oracle
         # (ranked ids, f64 scores) -- after the timed region, never inside it
         parity = None
         by_batch_size = None
-        if args.spot_check > 0 and not args.timed_only:
+        if args.spot_check > 0 and after:
             from oracle import cwrap as O
             om_ = O.OracleModel(alphabet_path=paths["alphabet"])
             om_.read_lexicon(paths[args.lexicon])
@@ -1409,10 +1421,10 @@ def main():
         if e2e is not None:
             e2e.pop("pipelined_last", None)
         # the CPU baseline is reported from rank 0; at N > 1 on a shorter sample (the other ranks wait at the final barrier)
-        cpu = cpu_baseline_of(args, paths, queries, ncores, 15.0 if world == 1 else 6.0) if (args.cpu_sample != 0 and not args.timed_only) else None
+        cpu = cpu_baseline_of(args, paths, queries, ncores, 15.0 if world == 1 else 6.0) if (args.cpu_sample != 0 and after) else None
         # one resident copy, one run at a time (anx_batch_run: launch, wait, launch ...): the like-for-like figure of round 1's records
         extras = None
-        if world == 1 and not args.timed_only:
+        if world == 1 and after:
             is_default = (args.lexicon, args.max_len, args.anagram_distance, args.edit_distance, args.queries) == ("eng", 16, 3, 2, 1_000_000)
             if is_default and not args.no_extras and not do_gather:
                 for b_ in batches:
@@ -1452,12 +1464,13 @@ def main():
                        "class_tests_per_query": tests / nq if nq else 0.0,
                        "parallelism": f"query-sharded x{world}" + (f", RCCL gather of compact top-k records ({gather_bytes[0] / 1e6:.0f} MB per rank and step)" if do_gather and gather_error[0] is None else "")
                        + (f", result gather FAILED on rank 0: {gather_error[0]}" if gather_error[0] else "")},
-            "stage_ms": {"scan": stage_ms["ms_scan"], "score": stage_ms["ms_score"], "compact": stage_ms["ms_group"], "rank": stage_ms["ms_rank"], "total": stage_ms["ms_total"]},
+            "stage_ms": ({"scan": stage_ms["ms_scan"], "score": stage_ms["ms_score"], "compact": stage_ms["ms_group"], "rank": stage_ms["ms_rank"], "total": stage_ms["ms_total"]}
+                         if serial_times else None),
             "pair_slots": st["n_pair_slots"], "dl_pairs": st["n_selected"], "survivors": st["n_survivors"], "results": st["n_results"], "encode_upload_s": t_enc,
             "gather_error": gather_error[0], "gather_check": gather_check, "process_group": (args.backend if use_dist else None), "ranks_on_one_gpu": bool(args.ranks_on_one_gpu),
             "roofline": roofline, "cpu_baseline": cpu,
         }
-        if world > 1 and not args.no_strong and not args.ranks_on_one_gpu:
+        if world > 1 and args.full and not args.no_strong and not args.ranks_on_one_gpu:
             # The other way to use the node: ONE process with N replicas behind the C ABI, the strong-scaling job of BASELINE configs[3]'s
             # shape (the ranks idle at the barrier below meanwhile; a child process: this one has initialised the GPU).  Its JSON line goes
             # into this line; a failure is reported, never fatal.

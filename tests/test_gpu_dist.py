@@ -117,7 +117,7 @@ def _bench(args, timeout=900):
 def test_bench_single_process_replicas():
     """bench.py --single-process: ONE process, the C ABI's own split over replicas (here 3 on the one GPU): same JSON contract,
     the rows of the last shard equal a one-replica run of its inputs."""
-    js = _bench(["--gpus", "3", "--single-process", "--replicas-on-one-gpu", "--queries", "150000", "--steps", "3", "--warmup", "1", "--cpu-sample", "2000"])
+    js = _bench(["--full", "--gpus", "3", "--single-process", "--replicas-on-one-gpu", "--queries", "150000", "--steps", "3", "--warmup", "1", "--cpu-sample", "2000"])
     assert js["n_gpus"] == 3 and js["shard_check"] == "ok" and js["value"] > 0 and js["scaling"] == "weak"
     # the length-partitioned split balances the replicas by COST (short queries are dearer): three shares that hold every input once
     assert [s[0] for s in js["shards"]] == [0, 0, 0] and sum(s[2] for s in js["shards"]) == 450000 and all(s[2] > 30000 for s in js["shards"])
@@ -128,7 +128,19 @@ def test_bench_n_ranks_on_one_gpu_gloo():
     """Dry run of the N-rank job on one GPU: 3 processes under torch.distributed.run, all on device 0, the index built once and
     loaded by the other ranks, compact records gathered over gloo; rank 0's view of EVERY rank's export equals that rank's fetch();
     roofline and cpu_baseline are reported at N > 1 too."""
-    js = _bench(["--ranks-on-one-gpu", "3", "--backend", "gloo", "--check-gather", "--queries", "120000", "--steps", "3", "--warmup", "1", "--cpu-sample", "2000"])
+    js = _bench(["--full", "--ranks-on-one-gpu", "3", "--backend", "gloo", "--check-gather", "--queries", "120000", "--steps", "3", "--warmup", "1", "--cpu-sample", "2000"])
     assert js["n_gpus"] == 3 and js["process_group"] == "gloo" and js["ranks_on_one_gpu"] is True
     assert js["gather_error"] is None and js["gather_check"] == "ok"
     assert js["queries_per_s"] > 0 and js["roofline"]["frac"] > 0 and js["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_stops_after_the_timed_steps(tmp_path):
+    """bench.py without --full: the headline fields and the --dump-outputs arrays; nothing is measured or checked after the timed
+    region (no serial pass, end to end, spot check, CPU baseline or extra configuration)."""
+    js = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--queries", "200000", "--dump-outputs", str(tmp_path)])
+    assert js["value"] > 0 and js["ms_per_step"] > 0 and js["unit"] == "pairs/s"
+    assert js["higher_is_better"] is True and js["dtype"] == "u8" and js["steps"] == 3 and js["warmup"] == 1
+    for k in ("serial_ms_per_step", "sync_single_copy_ms_per_step", "with_encode", "e2e", "parity", "by_batch_size", "configs",
+              "roofline", "stage_ms", "cpu_baseline"):
+        assert js[k] is None, k
+    assert js["dump_outputs"]["files"] and sorted(os.listdir(tmp_path)) == js["dump_outputs"]["files"]

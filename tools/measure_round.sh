@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/meas
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench_default.log 2>&1
+python3 $R/bench.py --full > $O/bench_default.log 2>&1
 tail -1 $O/bench_default.log > $O/bench_default.json
 rocprofv3 --kernel-trace --stats -d $O/trace -- python3 $R/bench.py --steps 5 --warmup 2 --timed-only --no-overlap > $O/trace.log 2>&1
 i=0
