@@ -172,6 +172,8 @@ def lib():
         "anx_learn_variants": (C.c_int, [vp, C.POINTER(cp), sz, C.POINTER(Params), C.c_int, C.POINTER(C.c_uint64)]),
         "anx_learn_variants_search": (C.c_int, [vp, C.POINTER(cp), sz, C.POINTER(SearchParams), C.c_int, C.POINTER(C.c_uint64)]),
         "anx_learn_apply_rows": (C.c_int, [vp, C.POINTER(cp), sz, C.POINTER(Result), C.POINTER(sz), C.POINTER(C.c_uint64)]),
+        "anx_debug_learn_fold_rows": (C.c_int, [vp, C.POINTER(cp), sz, C.POINTER(Result), C.POINTER(sz), C.c_int, C.c_int,
+                                                C.POINTER(C.c_uint64)]),
         "anx_model_variants": (C.c_int64, [vp, u64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_double), sz]),
         "anx_model_vocab_type": (C.c_uint32, [vp, u64]),
         "anx_format_variant_list": (C.c_int, [vp, C.c_int, C.POINTER(C.c_void_p)]),

@@ -1894,6 +1894,7 @@ size_t anx_batch_rows(const anx_batch* b) {
   return r;
 }
 int anx_learn_fail(int code, const std::string& msg) { return fail(code, msg); }
+int anx_learn_check_rows(const anx_model* m, size_t n, const anx_result* rows, const size_t* off) { return check_rows(m, n, rows, off); }
 int anx_learn_code() { return g_code; }
 
 extern "C" {

@@ -128,12 +128,13 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& i
 void batch_free(Batch*);
 
 // ---- learn mode's fold on the device (learn.hip) ------------------------------------------------------------------------------------
-struct LearnVocab;  // vocabulary hash table of one device (text hash -> id): built on first use, rebuilt when the vocabulary size changes
+struct LearnVocab;  // vocabulary hash table of one device (text hash -> id): built on first use, rebuilt when the vocabulary size or ANX_LEARN_HASH_BITS changes
 void learn_vocab_free(LearnVocab*);
 // one compact export section (anx_batch_gather_compact layout) on the fold's device: u32 offsets[n + 1] padded to 16 bytes, then the
 // records; its inputs are the call's inputs lo + j, or idx[j] (host array) when idx is set
 void* learn_device_alloc(int device, size_t bytes);  // the gather buffers of a learn call (nullptr: out of memory / HIP error)
 void learn_device_free(int device, void* p);
+bool learn_device_upload(int device, void* dst, const void* src, size_t bytes);  // host -> gather buffer (anx_debug_learn_fold_rows)
 struct LearnSection { const void* base; size_t n; size_t lo; const uint32_t* idx; };
 // the fold of n inputs (blob[soff[i] .. soff[i+1] - 1) + NUL, host memory) over the n_rows rows of the sections, on `device`
 int learn_fold_device(const HostModel& m, int device, LearnVocab** vocab, const char* blob, const uint32_t* soff, size_t n,

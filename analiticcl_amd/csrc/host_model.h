@@ -106,6 +106,7 @@ struct Switches {
   int surv_seg = 32;                 // ANX_SURV_SEG=C: survivors per query the scoring kernels write straight into the query's segment (0: every survivor
                                      // through the region lists and k_compact_grouped, the path until round 7; A/B)
   int learn_fold_host = 0;           // ANX_LEARN_FOLD=host: learn mode folds its rows with the host loop instead of learn.hip (A/B reference)
+  int learn_hash_bits = 63;          // ANX_LEARN_HASH_BITS=1..63 (test hook): bits of the string hash learn.hip keeps; fewer = collisions on demand, same results
 };
 Switches& switches();
 // name = the environment variable's name, value = what the variable would hold; false: unknown name

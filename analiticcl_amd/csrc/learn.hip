@@ -18,7 +18,8 @@
 //   k_lf_rows     : one lane per input: its rows -> link key (ref << 32 | var) or "no link" (the result is the input itself)
 //   stable sort of the link keys (value = flat position) -> k_lf_first marks the first mention of each (ref, var)
 //   exclusive scans + k_lf_emit / k_lf_deltas / k_lf_new : the compact arrays the host applies
-// The vocabulary table (LearnVocab) is built here from the host's texts on first use and rebuilt when the vocabulary size changes.
+// The vocabulary table (LearnVocab) is built here from the host's texts on first use and rebuilt when the vocabulary size (or the test
+// switch ANX_LEARN_HASH_BITS) changes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,10 +51,11 @@ constexpr uint32_t LF_PENDING = 0xFFFFFFFEu;  // input with rows whose string is
 constexpr unsigned long long LF_NOKEY = ~0ull;  // sorts behind every real key (hashes have the top bit clear)
 constexpr int LF_BLOCK = 256;
 
-__device__ inline unsigned long long lf_hash(const uint8_t* p, uint32_t len) {  // FNV-1a, 63 bits
+// FNV-1a under hmask: its low 63 bits, or fewer under the test switch ANX_LEARN_HASH_BITS (collisions on demand)
+__device__ inline unsigned long long lf_hash(const uint8_t* p, uint32_t len, unsigned long long hmask) {
   unsigned long long h = 1469598103934665603ull;
   for (uint32_t i = 0; i < len; ++i) { h ^= p[i]; h *= 1099511628211ull; }
-  return h & 0x7FFFFFFFFFFFFFFFull;
+  return h & hmask;
 }
 __device__ inline bool lf_eq(const uint8_t* a, uint32_t la, const uint8_t* b, uint32_t lb) {
   if (la != lb) return false;
@@ -65,10 +67,10 @@ inline unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>(1, (n + LF
 
 // vocabulary table: open addressing, linear probing, capacity a power of two >= 2 V (every probe ends at a free slot)
 __global__ void k_lv_build(uint32_t V, const uint8_t* __restrict__ pool, const uint32_t* __restrict__ voff, unsigned long long* __restrict__ vh,
-                           uint32_t* __restrict__ slots, uint32_t mask) {
+                           uint32_t* __restrict__ slots, uint32_t mask, unsigned long long hmask) {
   const uint32_t id = blockIdx.x * LF_BLOCK + threadIdx.x;
   if (id >= V) return;
-  const unsigned long long h = lf_hash(pool + voff[id], voff[id + 1] - voff[id]);
+  const unsigned long long h = lf_hash(pool + voff[id], voff[id + 1] - voff[id], hmask);
   vh[id] = h;
   uint32_t s = (uint32_t)h & mask;
   while (atomicCAS(&slots[s], LF_EMPTY, id) != LF_EMPTY) s = (s + 1) & mask;
@@ -89,15 +91,15 @@ __global__ void k_lf_sections(Section sec, uint32_t sid, uint32_t n, uint32_t* _
 
 __global__ void k_lf_lookup(uint32_t n, const uint8_t* __restrict__ blob, const uint32_t* __restrict__ soff, const uint32_t* __restrict__ cnt,
                             const uint8_t* __restrict__ pool, const uint32_t* __restrict__ voff, const unsigned long long* __restrict__ vh,
-                            const uint32_t* __restrict__ slots, uint32_t mask, uint32_t* __restrict__ id, unsigned long long* __restrict__ key,
-                            uint32_t* __restrict__ val) {
+                            const uint32_t* __restrict__ slots, uint32_t mask, unsigned long long hmask, uint32_t* __restrict__ id,
+                            unsigned long long* __restrict__ key, uint32_t* __restrict__ val) {
   const uint32_t i = blockIdx.x * LF_BLOCK + threadIdx.x;
   if (i >= n) return;
   val[i] = i;
   if (cnt[i] == 0) { id[i] = LF_NONE; key[i] = LF_NOKEY; return; }
   const uint8_t* a = blob + soff[i];
   const uint32_t la = soff[i + 1] - soff[i] - 1;  // (each input is followed by a NUL byte)
-  const unsigned long long h = lf_hash(a, la);
+  const unsigned long long h = lf_hash(a, la, hmask);
   for (uint32_t s = (uint32_t)h & mask;; s = (s + 1) & mask) {
     const uint32_t v = slots[s];
     if (v == LF_EMPTY) break;
@@ -268,6 +270,11 @@ void learn_device_free(int device, void* p) {
   (void)hipSetDevice(device);
   (void)hipFree(p);
 }
+bool learn_device_upload(int device, void* dst, const void* src, size_t bytes) {
+  if (!bytes) return true;
+  if (hipSetDevice(device) != hipSuccess || hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return true;
+}
 
 struct LearnVocab {
   int device = -1;
@@ -277,6 +284,7 @@ struct LearnVocab {
   unsigned long long* vh = nullptr;
   uint32_t* slots = nullptr;
   uint32_t mask = 0;
+  unsigned long long hmask = 0;  // what lf_hash keeps of FNV-1a (the table's hashes and the lookups' must agree)
 };
 
 void learn_vocab_free(LearnVocab* t) {
@@ -289,7 +297,9 @@ void learn_vocab_free(LearnVocab* t) {
 
 static int learn_vocab_build(const HostModel& m, int device, LearnVocab** cache, hipStream_t st, std::string& err) {
   const size_t V = m.decoder.size();
-  if (*cache && (*cache)->device == device && (*cache)->V == V) return ANX_OK;
+  const int bits = switches().learn_hash_bits;
+  const unsigned long long hmask = bits >= 63 ? 0x7FFFFFFFFFFFFFFFull : (1ull << bits) - 1;
+  if (*cache && (*cache)->device == device && (*cache)->V == V && (*cache)->hmask == hmask) return ANX_OK;
   learn_vocab_free(*cache);
   *cache = nullptr;
   if (V >= LF_PENDING) { err = "vocabulary too large for the learn fold"; return ANX_ELIMIT; }
@@ -306,6 +316,7 @@ static int learn_vocab_build(const HostModel& m, int device, LearnVocab** cache,
   t->device = device;
   t->V = V;
   t->mask = (uint32_t)(cap - 1);
+  t->hmask = hmask;
   auto body = [&]() -> int {
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->pool), pool.size()));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t->voff), (V + 1) * sizeof(uint32_t)));
@@ -314,7 +325,7 @@ static int learn_vocab_build(const HostModel& m, int device, LearnVocab** cache,
     HIP_TRY(hipMemcpyAsync(t->pool, pool.data(), pool.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(t->voff, off.data(), (V + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(t->slots, 0xFF, cap * sizeof(uint32_t), st));
-    if (V) hipLaunchKernelGGL(k_lv_build, dim3(grid_of(V)), dim3(LF_BLOCK), 0, st, (uint32_t)V, t->pool, t->voff, t->vh, t->slots, t->mask);
+    if (V) hipLaunchKernelGGL(k_lv_build, dim3(grid_of(V)), dim3(LF_BLOCK), 0, st, (uint32_t)V, t->pool, t->voff, t->vh, t->slots, t->mask, t->hmask);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));  // (the host copies above are pageable: they must outlive the copies)
     return ANX_OK;
@@ -387,7 +398,7 @@ int learn_fold_device(const HostModel& m, int device, LearnVocab** vocab, const 
     if (rows != n_rows) { err = "learn fold: the gathered sections hold " + std::to_string(rows) + " rows, the batch " + std::to_string(n_rows); return ANX_EINVAL; }
   }
   hipLaunchKernelGGL(k_lf_lookup, dim3(grid_of(n)), dim3(LF_BLOCK), 0, st, n32, d_blob, d_soff, d_cnt, t.pool, t.voff, t.vh, t.slots, t.mask,
-                     d_id, d_key, d_val);
+                     t.hmask, d_id, d_key, d_val);
   // (c) first-occurrence ids of the strings the vocabulary does not hold
   if (int rc = sort64(d_key, d_skey, d_val, d_sval, n, b, st, err)) return rc;
   hipLaunchKernelGGL(k_lf_head, dim3(grid_of(n)), dim3(LF_BLOCK), 0, st, n32, d_skey, d_head);

@@ -22,12 +22,31 @@ int anx_learn_finish(anx_model* m, int auto_build, double* ms);
 bool anx_batch_host_rescored(const anx_batch* b);
 size_t anx_batch_rows(const anx_batch* b);
 int anx_learn_fail(int code, const std::string& msg);
+int anx_learn_check_rows(const anx_model* m, size_t n, const anx_result* rows, const size_t* off);
 int anx_learn_code();
 
 namespace {
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 void release_vocab(void* p) { anx::learn_vocab_free(static_cast<anx::LearnVocab*>(p)); }
+
+// the inputs packed for the device fold (each followed by a NUL byte)
+int pack_offsets(const char* const* utf8, size_t n, std::vector<uint32_t>& soff) {
+  soff.assign(n + 1, 0);
+  size_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (!utf8[i]) return anx_learn_fail(ANX_EINVAL, "NULL input");
+    total += strlen(utf8[i]) + 1;
+    if (total >= 0xFFFFFFFFull) return anx_learn_fail(ANX_ELIMIT, "learn: more than 4 GB of input text in one call");
+    soff[i + 1] = (uint32_t)total;
+  }
+  return ANX_OK;
+}
+std::vector<char> pack_blob(const char* const* utf8, size_t n, const std::vector<uint32_t>& soff) {
+  std::vector<char> blob((size_t)soff[n] + 1, 0);
+  for (size_t i = 0; i < n; ++i) memcpy(blob.data() + soff[i], utf8[i], soff[i + 1] - soff[i]);
+  return blob;
+}
 
 // *host_rows: the rows exist only on the host (confusables weighted there): nothing was folded
 int strict_device(anx_model* m, const char* const* utf8, size_t n, const anx_params* p, const std::vector<char>& blob,
@@ -97,20 +116,12 @@ int anx_learn_variants(anx_model* m, const char* const* utf8, size_t n, const an
   std::lock_guard<std::mutex> lk(anx_learn_mutex());
   anx::HostModel& host = anx_learn_host(m);
   double ms[6] = {0, 0, 0, 0, 0, 0};
-  // the inputs packed for the device fold (each followed by a NUL byte)
-  std::vector<uint32_t> soff(n + 1, 0);
-  size_t total = 0;
-  for (size_t i = 0; i < n; ++i) {
-    if (!utf8[i]) return anx_learn_fail(ANX_EINVAL, "NULL input");
-    total += strlen(utf8[i]) + 1;
-    if (total >= 0xFFFFFFFFull) return anx_learn_fail(ANX_ELIMIT, "learn: more than 4 GB of input text in one call");
-    soff[i + 1] = (uint32_t)total;
-  }
+  std::vector<uint32_t> soff;
+  if (int rc = pack_offsets(utf8, n, soff)) return rc;
   uint64_t c = 0;
   bool host_rows = anx::switches().learn_fold_host;
   if (!host_rows) {
-    std::vector<char> blob(total + 1, 0);
-    for (size_t i = 0; i < n; ++i) memcpy(blob.data() + soff[i], utf8[i], soff[i + 1] - soff[i]);
+    const std::vector<char> blob = pack_blob(utf8, n, soff);
     anx::LearnFold fold;
     size_t rows = 0;
     if (int rc = strict_device(m, utf8, n, p, blob, soff, fold, &host_rows, &rows, ms)) return rc;
@@ -135,5 +146,82 @@ int anx_learn_variants(anx_model* m, const char* const* utf8, size_t n, const an
   }
   *count = c;
   return anx_learn_finish(m, auto_build, ms);
+}
+
+// Test hook: anx_learn_apply_rows' contract with the DEVICE fold.  The caller's rows are packed into n_sections compact export
+// sections on replica 0's device, the layout strict_device gathers a batch's shards into: contiguous input ranges (section s holds the
+// inputs [s n / S, (s + 1) n / S), empty when S > n), or with by_index index-listed sections that deal the inputs out round-robin
+// (section s holds s, s + S, ...: neighbours land in different sections).  The fold and the apply are anx_learn_variants'.
+int anx_debug_learn_fold_rows(anx_model* m, const char* const* utf8, size_t n, const anx_result* rows, const size_t* offsets, int n_sections,
+                              int by_index, uint64_t* count) {
+  if (!m || (!utf8 && n) || !offsets || (!rows && offsets[n]) || !count) return anx_learn_fail(ANX_EINVAL, "NULL argument");
+  for (size_t i = 0; i < n; ++i)
+    if (!utf8[i]) return anx_learn_fail(ANX_EINVAL, "NULL input");
+  if (n_sections < 1) return anx_learn_fail(ANX_EINVAL, "at least one section");
+  if (int rc = anx_learn_check_rows(m, n, rows, offsets)) return rc;
+  if (anx_model_num_replicas(m) < 1)
+    return anx_learn_fail(ANX_ENODEVICE, "model is not resident on a device (no HIP device / anx_model_to_device not called)");
+  if (offsets[n] >= 0x7FFFFFFFull) return anx_learn_fail(ANX_ELIMIT, "learn fold: more than 2^31 rows");
+  std::lock_guard<std::mutex> lk(anx_learn_mutex());
+  anx::HostModel& host = anx_learn_host(m);
+  std::vector<uint32_t> soff;
+  if (int rc = pack_offsets(utf8, n, soff)) return rc;
+  const std::vector<char> blob = pack_blob(utf8, n, soff);
+  const int dev0 = anx_model_replica_device(m, 0);
+  const size_t S = (size_t)n_sections;
+  std::vector<void*> bufs;
+  std::vector<anx::LearnSection> secs;
+  std::deque<std::vector<uint32_t>> idx_store;
+  auto release = [&]() { for (void* b : bufs) anx::learn_device_free(dev0, b); };
+  std::vector<char> img;
+  for (size_t s = 0; s < S; ++s) {
+    std::vector<uint32_t> members;
+    size_t lo = 0;
+    if (by_index) {
+      for (size_t i = s; i < n; i += S) members.push_back((uint32_t)i);
+    } else {
+      lo = s * n / S;
+      for (size_t i = lo; i < (s + 1) * n / S; ++i) members.push_back((uint32_t)i);
+    }
+    const size_t ns = members.size();
+    const size_t off_bytes = ((ns + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
+    size_t nr = 0;
+    for (uint32_t i : members) nr += offsets[i + 1] - offsets[i];
+    img.assign(off_bytes + nr * sizeof(anx_topk_record), 0);
+    uint32_t* so = reinterpret_cast<uint32_t*>(img.data());
+    anx_topk_record* rec = reinterpret_cast<anx_topk_record*>(img.data() + off_bytes);
+    size_t k = 0;
+    for (size_t j = 0; j < ns; ++j) {
+      so[j] = (uint32_t)k;
+      for (size_t r = offsets[members[j]]; r < offsets[members[j] + 1]; ++r, ++k) {
+        rec[k].vocab_id = (uint32_t)rows[r].vocab_id;
+        rec[k].freq_score = (float)rows[r].freq_score;
+        rec[k].dist_score = rows[r].dist_score;
+      }
+    }
+    so[ns] = (uint32_t)k;
+    void* buf = anx::learn_device_alloc(dev0, img.size());
+    if (!buf) { release(); return anx_learn_fail(ANX_ENODEVICE, "out of device memory for the learn sections"); }
+    bufs.push_back(buf);
+    if (!anx::learn_device_upload(dev0, buf, img.data(), img.size())) { release(); return anx_learn_fail(ANX_ENODEVICE, "upload of a learn section failed"); }
+    const uint32_t* idx = nullptr;
+    if (by_index) {
+      idx_store.push_back(std::move(members));
+      idx = idx_store.back().data();
+    }
+    secs.push_back(anx::LearnSection{buf, ns, lo, idx});
+  }
+  std::string err;
+  anx::LearnFold fold;
+  anx::LearnVocab** vocab = reinterpret_cast<anx::LearnVocab**>(anx_learn_vocab_slot(m, release_vocab));
+  const int rc = anx::learn_fold_device(host, dev0, vocab, blob.data(), soff.data(), n, secs, offsets[n], fold, err);
+  release();
+  if (rc) return anx_learn_fail(rc, err);
+  const uint64_t before = host.learn_refs_added;
+  const uint64_t c = host.learn_apply(utf8, n, fold, err);
+  if (c == UINT64_MAX) return anx_learn_fail(ANX_EINVAL, err);
+  anx_learn_count_device_fold(offsets[n], host.learn_refs_added - before);
+  *count = c;
+  return ANX_OK;
 }
 }  // extern "C"

@@ -761,8 +761,19 @@ class VariantModel:
     def learn_apply_rows(self, inputs: Sequence[str], rows: Sequence[Sequence[tuple]]) -> int:
         """The fold of learn_variants over caller-provided ranked rows (per input: [(vocab_id, dist_score, ...)]), on the host; no
         build.  -> the count learn_variants would return."""
+        return self._learn_rows(inputs, rows, None)
+
+    def learn_fold_rows_device(self, inputs: Sequence[str], rows: Sequence[Sequence[tuple]], n_sections: int = 1,
+                               by_index: bool = False) -> int:
+        """The same fold through learn.hip on replica 0's device (anx_debug_learn_fold_rows, a test hook): the rows are packed into
+        n_sections compact export sections, contiguous input ranges or (by_index) index-listed round-robin ones; no build."""
+        return self._learn_rows(inputs, rows, (int(n_sections), int(bool(by_index))))
+
+    def _learn_rows(self, inputs, rows, device_sections) -> int:
         self.__dict__.pop("_vocab_cache", None)
         n = len(inputs)
+        if len(rows) != n:
+            raise ValueError("one list of rows per input")
         arr = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
         off = [0]
         for r in rows:
@@ -777,7 +788,10 @@ class VariantModel:
                 k += 1
         offs = (C.c_size_t * (n + 1))(*off)
         count = C.c_uint64(0)
-        L.check(L.lib().anx_learn_apply_rows(self.h, arr, n, res, offs, C.byref(count)))
+        if device_sections is None:
+            L.check(L.lib().anx_learn_apply_rows(self.h, arr, n, res, offs, C.byref(count)))
+        else:
+            L.check(L.lib().anx_debug_learn_fold_rows(self.h, arr, n, res, offs, device_sections[0], device_sections[1], C.byref(count)))
         return count.value
 
     def variants(self, vocab_id: int) -> List[tuple]:

@@ -30,7 +30,8 @@ extern "C" {
  *    version); anx_batch_encode_packed_device_on (the caller's stream orders the encoder behind the producer of the buffer);
  *    anx_debug_search_stats, anx_debug_small_stats (anx_find_variants_batch's path for small calls); ANX_ADJ_CLOSURE is 0..2 for every builder.  Nothing was removed; every struct of version 2 is unchanged.
  *    Added later within version 3 (additive, no struct changed): learn mode (anx_learn_*, anx_model_variants, anx_model_vocab_type,
- *    anx_format_variant_list, anx_debug_learn_stats / _times). */
+ *    anx_format_variant_list, anx_debug_learn_stats / _times); the test hook anx_debug_learn_fold_rows and the test switch
+ *    ANX_LEARN_HASH_BITS. */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -486,6 +487,15 @@ int anx_format_variant_list(const anx_model *, int json, char **out);
 int anx_debug_learn_stats(uint64_t out[4]);
 /* the last learn call's phases in ms: batch (encode, run, gather), device fold, host fold, host apply, build, upload */
 int anx_debug_learn_times(double out[6]);
+/* Test hook of the device fold (learn.hip): anx_learn_apply_rows' contract and validation, but the rows are folded ON replica 0's
+ * DEVICE, as anx_learn_variants folds a batch's rows: packed into n_sections (>= 1) compact export sections (u32 offsets padded to 16
+ * bytes, then 16-byte anx_topk_record rows) -- contiguous input ranges, some empty when n_sections > n, or with by_index index-listed
+ * sections that deal the inputs out round-robin --, folded by learn.hip and applied by the host; no build.  Counts as a device fold in
+ * anx_debug_learn_stats.  ANX_ENODEVICE without a resident model.
+ * The test switch ANX_LEARN_HASH_BITS = 1..63 (anx_debug_set_switch; default 63) narrows the string hash of the fold, so that the
+ * collision branches run; results do not depend on it. */
+int anx_debug_learn_fold_rows(anx_model *, const char *const *utf8, size_t n, const anx_result *rows, const size_t *offsets, int n_sections,
+                              int by_index, uint64_t *count);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 """Learn mode without a device: the fold of learn_variants over C-oracle rows (anx_learn_apply_rows, the host fold) and the weighted
-variant list writers, against the restatement in tests/learn_twin.py; the `learn` subcommand's options."""
+variant list writers, against the restatement in tests/learn_twin.py; the generated edge cases of tests/learn_cases.py through the host
+fold; the `learn` subcommand's options."""
 import io
 import os
 import subprocess
@@ -13,6 +14,7 @@ from analiticcl_amd import cli, synth
 from oracle import cwrap as O
 from oracle import twin as T
 
+import learn_cases as LC
 import learn_twin as LT
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -126,3 +128,81 @@ def test_learn_help_lists_options():
     assert r.returncode == 0, r.stderr
     for opt in ("--iterations", "-I", "--strict", "--multi-output", "-O", "--lexicon", "--max-anagram-distance", "--json"):
         assert opt in r.stdout, opt
+
+
+# ---- the generated cases of tests/learn_cases.py through the host fold ---------------------------------------------------------------
+@pytest.mark.parametrize("kind", LC.KINDS)
+@pytest.mark.parametrize("case", LC.all_cases(seeds=(1, 2)), ids=repr)
+def test_generated_cases_host_fold(data_dir, tmp_path, case, kind):
+    """Every hand-made and random case, call after call: count and the whole state (text, frequency, type, lexicon index, links in
+    order with their scores) of the host fold equal the restatement of the reference's loop.  What the device fold is compared with
+    (tests/test_gpu_learn_fold.py) is thereby itself pinned."""
+    g, m = LC.build_models(os.path.join(data_dir, "simple.alphabet.tsv"), tmp_path, kind)
+    LT.assert_same_state(g, m)
+    ncalls = 0
+    for inputs, rows in case.calls(m):
+        assert all(vid < len(m.decoder) for rs in rows for vid, _ in rs)
+        assert g.learn_apply_rows(inputs, rows) == LT.learn_fold(m, inputs, rows)
+        LT.assert_same_state(g, m)
+        ncalls += 1
+    assert ncalls >= 2
+
+
+def test_hand_cases_say_what_they_claim(data_dir, tmp_path):
+    """The outcomes the comments of the hand-made cases promise, read off the restatement (which the test above ties to the product)."""
+    alpha = os.path.join(data_dir, "simple.alphabet.tsv")
+    cases = {c.name: c for c in LC.HAND_CASES}
+
+    def run(name, kind="plain", ncalls=1):
+        _g, m = LC.build_models(alpha, tmp_path, kind)
+        it = cases[name].calls(m)
+        counts = [LT.learn_fold(m, *next(it)) for _ in range(ncalls)]
+        return m, counts
+
+    lex = dict(LC.LEXICON)
+    m, c = run("duplicate_pairs")
+    hauze, house = m.encoder["hauze"], m.encoder["house"]
+    assert c == [7] and m.decoder[hauze].frequency == 2
+    assert [v for v in m.decoder[house].variants if v[0] == "ref_for"] == [("ref_for", hauze, 0.9), ("ref_for", m.encoder["xx"], 0.7)]
+    assert [s for k, y, s in m.decoder[hauze].variants if y == house] == [0.9, 0.5, 0.1, 0.2]
+    m, c = run("own_id_between_links")
+    assert c == [4] and m.decoder[m.encoder["house"]].variants == [("variant_of", m.encoder["mouse"], 0.5), ("variant_of", m.encoder["horse"], 0.4),
+                                                                 ("variant_of", m.encoder["mouse"], 0.3)]
+    m, _ = run("rowless_between_mentions")
+    f = lambda t: m.decoder[m.encoder[t]].frequency
+    assert (f("house"), f("recieve"), f("mouse"), f("teh")) == (lex["house"] + 1, 1, lex["mouse"] + 2, 2)
+    assert "zzzz" not in m.encoder and "" not in m.encoder
+    m, _ = run("runs_across_block_borders")
+    f = lambda t: m.decoder[m.encoder[t]].frequency
+    assert (f("house"), f("mouse"), f("qqq")) == (lex["house"] + 1, lex["mouse"] + 2, 2)
+    m, _ = run("prefix_family")
+    V = 3 + len(LC.LEXICON)
+    assert [v.text for v in m.decoder[V:]] == ["abcde", "abcdef", "b", "ééé", LC.LONG[:66], LC.LONG]
+    m, c = run("no_rows")
+    assert c == [0] and len(m.decoder) == V
+    m, c = run("second_call", ncalls=2)
+    hauze, house = m.encoder["hauze"], m.encoder["house"]
+    assert c == [3, 7] and m.decoder[hauze].frequency == 2 and m.decoder[m.encoder["mauze"]].frequency == 2
+    assert [v for v in m.decoder[house].variants if v[1] == hauze] == [("ref_for", hauze, 0.9)]
+    assert ("ref_for", m.encoder["hauzen"], 0.6) in m.decoder[hauze].variants
+    m, _ = run("links_before_the_call", kind="variants")
+    hous, house = m.encoder["hous"], m.encoder["house"]
+    assert hous < len(m.decoder) - 1 and [v for v in m.decoder[house].variants if v[1] == hous] == [("ref_for", hous, 0.75)]
+    assert [s for k, y, s in m.decoder[hous].variants if k == "variant_of" and y == house] == [0.75, 0.2, 0.3]
+
+
+def test_learn_fold_rows_device_validates_like_apply_rows(data_dir, tmp_path):
+    """The device fold's test hook checks its rows as anx_learn_apply_rows does, and there is no host fall-back behind it."""
+    g, m = LC.build_models(os.path.join(data_dir, "simple.alphabet.tsv"), tmp_path, "plain")
+    for bad in ([[(g.vocab_size(), 0.5)]], [[(0, 0.5), (g.vocab_size() + 5, 0.5)]]):
+        for call in (g.learn_apply_rows, g.learn_fold_rows_device):
+            with pytest.raises(A.AnxError) as e:
+                call(["huis"], bad)
+            assert e.value.code == L.ANX_EINVAL
+    with pytest.raises(A.AnxError) as e:
+        g.learn_fold_rows_device(["huis"], [[(3, 0.5)]], n_sections=0)
+    assert e.value.code == L.ANX_EINVAL
+    with pytest.raises(A.AnxError) as e:   # (the model is not resident on a device: it was never built for one)
+        g.learn_fold_rows_device(["huis"], [[(3, 0.5)]])
+    assert e.value.code == L.ANX_ENODEVICE
+    LT.assert_same_state(g, m)
