@@ -187,6 +187,8 @@ def lib():
         "anx_batch_fetch_compact": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint32))]),
         "anx_compact_free": (None, [C.c_void_p, C.POINTER(C.c_uint32)]),
         "anx_compact_to_results": (None, [C.c_void_p, sz, C.POINTER(Result)]),
+        "anx_batch_fetch_compact_via": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32))]),
+        "anx_compact_to_results_via": (None, [C.c_void_p, C.POINTER(C.c_uint32), sz, C.POINTER(Result)]),
         "anx_batch_fetch_pairs": (C.c_int, [vp, C.POINTER(C.POINTER(Pair)), C.POINTER(sz)]),
         "anx_pairs_free": (None, [C.POINTER(Pair)]),
         "anx_batch_pair_counts": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_uint32))]),
@@ -199,6 +201,7 @@ def lib():
         "anx_pipeline_submit_packed": (C.c_int, [vp, cp, C.c_size_t, C.c_size_t, C.POINTER(Params)]),
         "anx_pipeline_pending": (C.c_int, [vp]),
         "anx_pipeline_next": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]),
+        "anx_pipeline_next_via": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]),
         "anx_pipeline_free": (None, [vp]),
         "anx_debug_kernel_timer": (None, [C.c_int]),
         "anx_debug_kernel_time": (C.c_int, [cp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

@@ -115,6 +115,12 @@ struct anx_batch {
   std::vector<uint32_t> in_off;   // n + 1 offsets into in_text
 };
 
+// anx::batch_fetch_compact_via_into as compact_via_capi.cpp hands it over (see anx_compact_fetch)
+using anx_compact_via_into = int (*)(const anx::Batch*, anx_topk_record*, uint32_t*, uint32_t*, uint32_t, bool, std::string&);
+struct anx_pipeline;
+int anx_compact_fetch(const anx_batch* b, anx_topk_record** rows, uint32_t** offs, uint32_t** via, anx_compact_via_into via_into);
+int anx_pipeline_take(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, uint32_t** via, size_t* n);
+
 static thread_local std::string g_err;
 static thread_local int g_code = 0;
 static int fail(int code, const std::string& msg) {
@@ -1330,19 +1336,22 @@ int anx_batch_run(const anx_model* m, anx_batch* b, void* stream) {
 }  // extern "C"
 // Rows of a batch whose shards hold scattered inputs (length-partitioned split), back in the call's input order: every shard
 // downloads into a buffer of its own (pinned cache), the per-input counts give the global offsets, and the shards' threads copy
-// their rows to where they belong.  Row = anx_result / anx_topk_record, Off = size_t / uint32_t.
+// their rows to where they belong.  Row = anx_result / anx_topk_record, Off = size_t / uint32_t.  via_out (compact records of a
+// model with variant lists): one more word per row, which takes the same way; fetch_into gets nullptr for it otherwise.
 template <typename Row, typename Off, typename FetchFn>
-static int scatter_fetch(const anx_batch* b, Row* out, Off* off, const FetchFn& fetch_into) {
+static int scatter_fetch(const anx_batch* b, Row* out, Off* off, const FetchFn& fetch_into, uint32_t* via_out = nullptr) {
   const size_t n = b->n_input, S = b->shards.size();
   std::vector<Row*> rows(S, nullptr);
+  std::vector<uint32_t*> vias(S, nullptr);
   std::vector<std::vector<Off>> loff(S);
-  auto release = [&]() { for (Row* r : rows) anx::host_result_free(r); };
+  auto release = [&]() { for (Row* r : rows) anx::host_result_free(r); for (uint32_t* v : vias) anx::host_result_free(v); };
   int rc = on_shards(b, [&](size_t g, std::string& err) {
     const Shard& s = b->shards[g];
     rows[g] = static_cast<Row*>(anx::host_result_alloc(std::max<size_t>(1, anx::batch_n_results(s.b)) * sizeof(Row)));
-    if (!rows[g]) { err = "out of memory"; return (int)ANX_EINVAL; }
+    if (via_out) vias[g] = static_cast<uint32_t*>(anx::host_result_alloc(std::max<size_t>(1, anx::batch_n_results(s.b)) * sizeof(uint32_t)));
+    if (!rows[g] || (via_out && !vias[g])) { err = "out of memory"; return (int)ANX_EINVAL; }
     loff[g].assign(s.n + 1, 0);
-    return fetch_into(s.b, rows[g], loff[g].data(), err);
+    return fetch_into(s.b, rows[g], loff[g].data(), vias[g], err);
   });
   if (rc) { release(); return rc; }
   for (size_t i = 0; i <= n; ++i) off[i] = 0;
@@ -1357,6 +1366,7 @@ static int scatter_fetch(const anx_batch* b, Row* out, Off* off, const FetchFn& 
     for (size_t i = 0; i < s.n; ++i) {
       const size_t c = (size_t)(loff[g][i + 1] - loff[g][i]);
       if (c) memcpy(out + off[s.input(i)], rows[g] + loff[g][i], c * sizeof(Row));
+      if (c && via_out) memcpy(via_out + off[s.input(i)], vias[g] + loff[g][i], c * sizeof(uint32_t));
     }
     return (int)ANX_OK;
   });
@@ -1378,7 +1388,7 @@ int anx_batch_fetch(const anx_batch* b, anx_result** rows, size_t** offs) {
   anx_result* out = static_cast<anx_result*>(anx::host_result_alloc(std::max<size_t>(1, base[S]) * sizeof(anx_result)));
   if (!off || !out) { free(off); anx::host_result_free(out); return fail(ANX_EINVAL, "out of memory"); }
   if (scattered(b)) {
-    const int rcs = scatter_fetch<anx_result, size_t>(b, out, off, [](const anx::Batch* sb, anx_result* r, size_t* o, std::string& err) {
+    const int rcs = scatter_fetch<anx_result, size_t>(b, out, off, [](const anx::Batch* sb, anx_result* r, size_t* o, uint32_t*, std::string& err) {
       return anx::batch_fetch_into(sb, r, o, 0, err);
     });
     if (rcs) { free(off); anx::host_result_free(out); return rcs; }
@@ -1403,27 +1413,39 @@ int anx_batch_fetch(const anx_batch* b, anx_result** rows, size_t** offs) {
   *offs = off;
   return ANX_OK;
 }
-int anx_batch_fetch_compact(const anx_batch* b, anx_topk_record** rows, uint32_t** offs) {
-  if (!b || !rows || !offs) return fail(ANX_EINVAL, "NULL argument");
+}  // extern "C"
+static const char kCompactNoVia[] = "variant lists are loaded: compact records carry no `via`, use anx_batch_fetch";
+// Compact records of every shard layout (one shard, contiguous shards, scattered shards) in ONE pinned block of the result cache.
+// via == nullptr: [rows | offsets], filled by anx::batch_fetch_compact_into.  Else [rows | via | offsets], filled by via_into, the
+// engine's fetch that also writes the `via` words: compact_via_capi.cpp hands it in (anx_batch_fetch_compact_via) or installs it
+// for the pipeline's fetch stage, so that this file refers to no engine symbol the CPU harness' stub engine lacks.
+int anx_compact_fetch(const anx_batch* b, anx_topk_record** rows, uint32_t** offs, uint32_t** via, anx_compact_via_into via_into) {
   if (b->rescore) return fail(ANX_EINVAL, "confusables are loaded: results are rescored on the host, use anx_batch_fetch");
-  if (b->model->host.lex.any_variants) return fail(ANX_EINVAL, "variant lists are loaded: compact records carry no `via`, use anx_batch_fetch");
+  if (via && !via_into) return fail(ANX_EINVAL, kCompactNoVia);
+  const bool plain = !b->model->host.lex.any_variants;
   const size_t n = b->n_input, S = b->shards.size();
   std::vector<size_t> base(S + 1, 0);
   for (size_t g = 0; g < S; ++g) base[g + 1] = base[g] + anx::batch_n_results(b->shards[g].b);
   if (base[S] >= ((size_t)1 << 32)) return fail(ANX_ELIMIT, "more than 2^32 result rows: use anx_batch_fetch");
-  // offsets (pinned as well: they are a D2H target) and rows in ONE pinned block of the result cache: [rows | offsets]
+  // (the offsets are pinned as well: they are a D2H target)
   const size_t row_bytes = (std::max<size_t>(1, base[S]) * sizeof(anx_topk_record) + 63) & ~(size_t)63;
-  char* blk = static_cast<char*>(anx::host_result_alloc(row_bytes + (n + 2) * sizeof(uint32_t)));
+  const size_t via_bytes = via ? (std::max<size_t>(1, base[S]) * sizeof(uint32_t) + 63) & ~(size_t)63 : 0;
+  char* blk = static_cast<char*>(anx::host_result_alloc(row_bytes + via_bytes + (n + 2) * sizeof(uint32_t)));
   if (!blk) return fail(ANX_EINVAL, "out of memory");
   anx_topk_record* out = reinterpret_cast<anx_topk_record*>(blk);
-  uint32_t* off = reinterpret_cast<uint32_t*>(blk + row_bytes);
+  uint32_t* vout = via ? reinterpret_cast<uint32_t*>(blk + row_bytes) : nullptr;
+  uint32_t* off = reinterpret_cast<uint32_t*>(blk + row_bytes + via_bytes);
+  auto fetch_into = [&](const anx::Batch* sb, anx_topk_record* r, uint32_t* o, uint32_t* v, uint32_t at, std::string& err) {
+    return v ? via_into(sb, r, o, v, at, plain, err) : anx::batch_fetch_compact_into(sb, r, o, at, err);
+  };
   if (scattered(b)) {
-    const int rcs = scatter_fetch<anx_topk_record, uint32_t>(b, out, off, [](const anx::Batch* sb, anx_topk_record* r, uint32_t* o, std::string& err) {
-      return anx::batch_fetch_compact_into(sb, r, o, 0u, err);
-    });
+    const int rcs = scatter_fetch<anx_topk_record, uint32_t>(b, out, off, [&](const anx::Batch* sb, anx_topk_record* r, uint32_t* o, uint32_t* v, std::string& err) {
+      return fetch_into(sb, r, o, v, 0u, err);
+    }, vout);
     if (rcs) { anx::host_result_free(blk); return rcs; }
     *rows = out;
     *offs = off;
+    if (via) *via = vout;
     return ANX_OK;
   }
   const int rc = on_shards(b, [&](size_t g, std::string& err) {
@@ -1431,7 +1453,7 @@ int anx_batch_fetch_compact(const anx_batch* b, anx_topk_record** rows, uint32_t
     std::vector<uint32_t> tmp;  // the last offset of a shard is the first of the next: keep the slices disjoint
     uint32_t* dst = off + s.lo;
     if (g + 1 < S) { tmp.resize(s.n + 1); dst = tmp.data(); }
-    const int r = anx::batch_fetch_compact_into(s.b, out + base[g], dst, (uint32_t)base[g], err);
+    const int r = fetch_into(s.b, out + base[g], dst, vout ? vout + base[g] : nullptr, (uint32_t)base[g], err);
     if (r == ANX_OK && g + 1 < S && s.n) memcpy(off + s.lo, tmp.data(), s.n * sizeof(uint32_t));
     return r;
   });
@@ -1439,7 +1461,18 @@ int anx_batch_fetch_compact(const anx_batch* b, anx_topk_record** rows, uint32_t
   off[n] = (uint32_t)base[S];
   *rows = out;
   *offs = off;
+  if (via) *via = vout;
   return ANX_OK;
+}
+// what compact_via_capi.cpp installs when it is part of the library: the pipeline's fetch stage serves variant-list models with it
+static anx_compact_via_into g_via_into = nullptr;
+void anx_compact_via_install(anx_compact_via_into f) { g_via_into = f; }
+extern "C" {
+int anx_batch_fetch_compact(const anx_batch* b, anx_topk_record** rows, uint32_t** offs) {
+  if (!b || !rows || !offs) return fail(ANX_EINVAL, "NULL argument");
+  if (b->rescore) return fail(ANX_EINVAL, "confusables are loaded: results are rescored on the host, use anx_batch_fetch");
+  if (b->model->host.lex.any_variants) return fail(ANX_EINVAL, kCompactNoVia);
+  return anx_compact_fetch(b, rows, offs, nullptr, nullptr);
 }
 void anx_compact_free(anx_topk_record* rows, uint32_t* offsets) {
   (void)offsets;  // one block: the offsets live behind the rows
@@ -1652,6 +1685,7 @@ struct PipeJob {
   std::string err;
   anx_topk_record* rows = nullptr;
   uint32_t* offs = nullptr;
+  uint32_t* via = nullptr;  // fetched with `via` (a model with variant lists, or the caller has asked for it): inside the rows' block
   int stage = 0;  // 0 submitted, 1 encoded, 2 run, 3 fetched (done)
   uint64_t seq = 0;
 };
@@ -1667,6 +1701,7 @@ struct anx_pipeline {
   void* enc_stream = nullptr;  // the encode thread's own stream (single-replica models; highest stream priority)
   void* fetch_stream = nullptr;  // the downloads' stream (highest stream priority as well)
   int running = 0;             // runs launched and not yet waited for (at most 2: the scan of one under the tail of the other)
+  std::atomic<bool> want_via{false};  // anx_pipeline_next_via was called: the fetch stage of a plain model leaves room for `via` from now on
   std::thread th[3];
 };
 static void pipeline_stage(anx_pipeline* pl, int stage) {
@@ -1711,7 +1746,11 @@ static void pipeline_stage(anx_pipeline* pl, int stage) {
       } else {
         if (pl->fetch_stream)  // the run has been waited for: its rows are downloaded on the pipeline's download stream
           for (Shard& s_ : job->b->shards) anx::batch_set_last_stream(s_.b, pl->fetch_stream);
-        job->rc = anx_batch_fetch_compact(job->b, &job->rows, &job->offs);
+        // a model with variant lists needs the fetch that carries `via` (compact_via_capi.cpp installs it); without it
+        // anx_batch_fetch_compact refuses such a model
+        if (g_via_into && (pl->m->host.lex.any_variants || pl->want_via.load()))
+          job->rc = anx_compact_fetch(job->b, &job->rows, &job->offs, &job->via, g_via_into);
+        else job->rc = anx_batch_fetch_compact(job->b, &job->rows, &job->offs);
         if (job->rc) job->err = g_err;
       }
     }
@@ -1781,6 +1820,15 @@ int anx_pipeline_pending(const anx_pipeline* pl) {
 }
 int anx_pipeline_next(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, size_t* n) {
   if (!pl || !rows || !offs) return fail(ANX_EINVAL, "NULL argument");
+  return anx_pipeline_take(pl, rows, offs, nullptr, n);
+}
+}  // extern "C"
+// The oldest job's results, or its error.  via == nullptr (anx_pipeline_next): a job of a model with variant lists is refused as the
+// fetch stage refused it before it could carry `via` (the records alone would drop it silently).  via != nullptr
+// (anx_pipeline_next_via, compact_via_capi.cpp): a job fetched without `via` -- a plain model, before the caller first asked --
+// moves into a block with room for it, every word 0xFFFFFFFF.
+int anx_pipeline_take(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, uint32_t** via, size_t* n) {
+  if (via) pl->want_via.store(true);
   std::shared_ptr<PipeJob> job;
   {
     std::unique_lock<std::mutex> lk(pl->mu);
@@ -1791,11 +1839,31 @@ int anx_pipeline_next(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs,
   }
   pl->cv.notify_all();
   if (job->rc != ANX_OK) return fail(job->rc, job->err);
+  if (!via && job->via && pl->m->host.lex.any_variants) {
+    anx_compact_free(job->rows, job->offs);
+    return fail(ANX_EINVAL, kCompactNoVia);
+  }
+  if (via && !job->via) {
+    const size_t total = job->offs[job->n];
+    const size_t row_bytes = (std::max<size_t>(1, total) * sizeof(anx_topk_record) + 63) & ~(size_t)63;
+    const size_t via_bytes = (std::max<size_t>(1, total) * sizeof(uint32_t) + 63) & ~(size_t)63;
+    char* blk = static_cast<char*>(anx::host_result_alloc(row_bytes + via_bytes + (job->n + 2) * sizeof(uint32_t)));
+    if (!blk) { anx_compact_free(job->rows, job->offs); return fail(ANX_EINVAL, "out of memory"); }
+    memcpy(blk, job->rows, total * sizeof(anx_topk_record));
+    memset(blk + row_bytes, 0xFF, total * sizeof(uint32_t));
+    memcpy(blk + row_bytes + via_bytes, job->offs, (job->n + 1) * sizeof(uint32_t));
+    anx_compact_free(job->rows, job->offs);
+    job->rows = reinterpret_cast<anx_topk_record*>(blk);
+    job->via = reinterpret_cast<uint32_t*>(blk + row_bytes);
+    job->offs = reinterpret_cast<uint32_t*>(blk + row_bytes + via_bytes);
+  }
   *rows = job->rows;
   *offs = job->offs;
+  if (via) *via = job->via;
   if (n) *n = job->n;
   return ANX_OK;
 }
+extern "C" {
 void anx_pipeline_free(anx_pipeline* pl) {
   if (!pl) return;
   for (;;) {  // the jobs in flight finish; their results are dropped

@@ -114,6 +114,51 @@ __global__ __launch_bounds__(COMPACT_B) void k_compact_grouped(const SurvRec* __
   }
 }
 
+// k_compact's rows (variant lists: references first, then the entry itself unless TRANSPARENT) with k_compact_grouped's contract,
+// for the small call, which has fixed capacities and no host round trip to size a grid or a row buffer with: the grid does not
+// depend on the number of survivors (gridDim.x / SCAN_REGIONS blocks per region walk its survivors in strides), nothing is written
+// when the batch has more rows than c_rows holds (soff[nq] > row_cap) or when a region dropped survivor records (its fill exceeds
+// region_cap: the per-query counts no longer match the records; *overflow is raised and the host discards the run).
+// A survivor's rows are contiguous from ONE returning atomic on its query's cursor; the scoring kernels counted the same rows into
+// qsurv (score_finish), so cursor + rows <= soff[q + 1] <= soff[nq] <= row_cap -- and a survivor whose rows would still end
+// beyond row_cap (counts and records out of step) writes nothing and raises *overflow instead.
+// No grouping by query in LDS here: a few rows per survivor already share one atomic, and an expanding entry's loop dominates.
+constexpr uint32_t EXPAND_B = 256, EXPAND_P = 4;  // threads per block, blocks per region the small call launches
+__global__ __launch_bounds__(EXPAND_B) void k_compact_expand(const SurvRec* __restrict__ surv, const uint32_t* __restrict__ sctr,
+                                                             uint32_t region_cap, int have_freq, uint32_t* __restrict__ qcur,
+                                                             const EntRec* __restrict__ ent_rec, const uint32_t* __restrict__ ent_var_off,
+                                                             const uint32_t* __restrict__ var_target,
+                                                             const uint32_t* __restrict__ var_target_freq,
+                                                             const double* __restrict__ var_score, SurvRow* __restrict__ c_rows,
+                                                             const uint32_t* __restrict__ total_rows, uint32_t row_cap,
+                                                             uint32_t* __restrict__ overflow) {
+  if (*total_rows > row_cap) return;
+  const uint32_t region = blockIdx.x % SCAN_REGIONS;
+  const uint32_t fill = sctr[region * RC_STRIDE];
+  if (fill > region_cap) {  // block-uniform
+    if (threadIdx.x == 0) *overflow = 1u;
+    return;
+  }
+  for (uint32_t i = (blockIdx.x / SCAN_REGIONS) * EXPAND_B + threadIdx.x; i < fill; i += (gridDim.x / SCAN_REGIONS) * EXPAND_B) {
+    const SurvRec sr = surv[(size_t)region * region_cap + i];
+    const uint32_t e = sr.e;
+    const EntRec er = ent_rec[e];
+    const uint32_t v0 = ent_var_off[e], v1 = ent_var_off[e + 1];
+    const uint32_t self = (er.meta & 0x400u) ? 0u : 1u;
+    const uint32_t nrows = (v1 - v0) + self;
+    const uint32_t f = have_freq ? er.freq : 1u;
+    const unsigned long long ord = (unsigned long long)er.order << 20;
+    uint32_t pos = atomicAdd(&qcur[sr.q], nrows);  // qcur starts as a copy of soff
+    if (pos > row_cap || nrows > row_cap - pos) { *overflow = 1u; continue; }
+    for (uint32_t j = v0; j < v1; ++j, ++pos) {  // references first, then the item itself (src/lib.rs:1689-1717)
+      const uint32_t tf = var_target_freq[j];
+      c_rows[pos] = SurvRow{sr.score * var_score[j], ord | (unsigned long long)(j - v0), var_target[j],
+                            have_freq ? (tf < f ? tf : f) : (tf < 1u ? tf : 1u), er.vocab, 0u};
+    }
+    if (self) c_rows[pos] = SurvRow{sr.score, ord | (unsigned long long)(v1 - v0), er.vocab, f, 0xFFFFFFFFu, 0u};
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K4: rank.  One wave per query over its survivors.  freq normalisation (src/lib.rs:1521-1525),
 // stable sort by rank_cmp (src/types.rs:344-365) realised as a total order with ent_order as last key,
@@ -704,6 +749,25 @@ __global__ __launch_bounds__(256) void k_export_rows(uint32_t nq, const uint32_t
     r.freq_score = (float)d.freq_score;
     r.dist_score = d.dist_score;
     out[dst + i] = r;
+  }
+}
+// the same for models with variant lists: the 16-byte record keeps its layout, `via` (the vocabulary id of the variant a row was
+// reached through, 0xFFFFFFFF = none) travels as a parallel array, one word per row
+__global__ __launch_bounds__(256) void k_export_rows_via(uint32_t nq, const uint32_t* __restrict__ soff, const uint32_t* __restrict__ r_count,
+                                                         const DevRow* __restrict__ r_rows, const uint32_t* __restrict__ q_orig,
+                                                         const uint32_t* __restrict__ off_orig, anx_topk_record* __restrict__ out,
+                                                         uint32_t* __restrict__ via) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= nq) return;
+  const uint32_t n = r_count[s], src = soff[s], dst = off_orig[q_orig[s]];
+  for (uint32_t i = 0; i < n; ++i) {
+    const DevRow d = r_rows[src + i];
+    anx_topk_record r;
+    r.vocab_id = d.vocab_id;
+    r.freq_score = (float)d.freq_score;
+    r.dist_score = d.dist_score;
+    out[dst + i] = r;
+    via[dst + i] = d.via;
   }
 }
 

@@ -14,6 +14,10 @@
 //     k_filter_score, k_small_lists (k_filter_wide + k_score_fast8 + k_score_pairs, a block per region) | k_small_offsets,
 //     k_compact_grouped, k_rank | k_small_fetch (rows and offsets straight into pinned host memory, with the run's fills) -- and ONE host wait
 //     (eleven in the first version: 66 us for one input);
+//   * a model with variant lists launches k_compact_expand in k_compact_grouped's place (a survivor's rows: its VariantOf references, then
+//     itself unless TRANSPARENT) and k_rank<false>; the launch count and the one host wait stay.  The expanded rows meet the same fixed
+//     capacities: an entry with many references first fills the caller's block of ranked rows (16 n + 64 rows: what survives dedup and crop
+//     of a call of n inputs), and only for the largest calls the context's candidate rows (16 * 4096 + 1024 for the call, before the crop);
 //   * a run whose fills exceeded a fixed capacity (a handful of very short queries can) is discarded and the call takes the batch path.
 // Same kernels, same arithmetic as the batch path: the results are identical (tests/test_gpu_small.py: against the batch path and the oracle).
 #pragma once
@@ -123,7 +127,7 @@ void small_stats(uint64_t* out) { out[0] = g_small_taken.load(); out[1] = g_smal
 // negative: an error of the device
 int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* utf8, size_t n, const anx_params& p, anx_result** out_rows, size_t** out_offs,
                std::string& err) {
-  if (!dl || n == 0 || n > SMALL_MAX || !switches().small_path || dl->any_variants || p.stop_at_exact_match || dl->nplanes > 42) return 1;
+  if (!dl || n == 0 || n > SMALL_MAX || !switches().small_path || p.stop_at_exact_match || dl->nplanes > 42) return 1;
   uint32_t lens[SMALL_MAX];
   uint32_t maxbytes = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -210,7 +214,7 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   sa.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;
   sa.score_threshold = p.score_threshold;
   sa.have_freq = m.have_freq ? 1 : 0;
-  sa.any_variants = 0;
+  sa.any_variants = dl->any_variants;  // the scoring kernels count a survivor's EXPANDED rows into qsurv and set qexpand
   sa.lqp = qw * 16;
   sa.lcp = (dl->max_len + 15) / 16 * 16;
   uint32_t stride = sa.lqp + sa.lcp + (d + 2) * (2 * d + 3);
@@ -241,8 +245,9 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   fa.use_nw8 = (have_long_q || use8) ? 1 : 0; fa.counters = c->counters; fa.stat_ctr = c->sctr; fa.fill_cap = fs_cap; fa.blk = SMALL_FS_BLK;
   {
     // k_filter_score's rarely used arguments live in device memory (FsCold): uploaded again only when they change (another model,
-    // other weights / thresholds / row width) -- compared field by field (struct padding is not)
-    const double key[12] = {sa.w_ld, sa.w_lcs, sa.w_prefix, sa.w_suffix, sa.w_case, sa.w_sum, sa.score_threshold, (double)sa.have_freq, (double)sa.lqp, (double)sa.lcp, (double)sa.stride,
+    // other weights / thresholds / row width) -- compared field by field (struct padding is not).  any_variants is part of the key: a
+    // model with variant lists and one without share the context pool of a device
+    const double key[12] = {sa.w_ld, sa.w_lcs, sa.w_prefix, sa.w_suffix, sa.w_case, sa.w_sum, sa.score_threshold, (double)sa.have_freq + 2.0 * (double)sa.any_variants, (double)sa.lqp, (double)sa.lcp, (double)sa.stride,
                             (double)sa.qw + 1e3 * (double)(reinterpret_cast<uintptr_t>(sa.quot) & 0xFFFFFFFFu)};
     if (!c->cold_valid || memcmp(key, c->cold_key, sizeof key) != 0) {
       memcpy(c->cold_key, key, sizeof key);
@@ -295,11 +300,15 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   ra.max_matches = p.max_matches;
   ra.freq_weight = p.freq_weight;
   ra.have_freq = m.have_freq ? 1 : 0;
-  ra.any_variants = 0;
+  ra.any_variants = dl->any_variants;
   const uint32_t crow_cap = (uint32_t)c->row_cap;
   hipLaunchKernelGGL(k_small_offsets, dim3(1), dim3(SMALL_T), 0, st, c->qsurv, n32, c->soff, c->qcur);
-  hipLaunchKernelGGL(k_compact_grouped, dim3(SCAN_REGIONS), dim3(COMPACT_B), 0, st, c->surv, c->sctr, SMALL_SURV_CAP, m.have_freq ? 1 : 0, c->qcur, dl->ent_rec, c->c_rows,
-                     c->soff + n32, crow_cap, c->counters + CTR_OVERFLOW);
+  if (dl->any_variants)  // variant lists: a survivor expands to a row per VariantOf reference (+ itself), within the same fixed capacity
+    hipLaunchKernelGGL(k_compact_expand, dim3(EXPAND_P * SCAN_REGIONS), dim3(EXPAND_B), 0, st, c->surv, c->sctr, SMALL_SURV_CAP, m.have_freq ? 1 : 0, c->qcur, dl->ent_rec,
+                       dl->ent_var_off, dl->var_target, dl->var_target_freq, dl->var_score, c->c_rows, c->soff + n32, crow_cap, c->counters + CTR_OVERFLOW);
+  else
+    hipLaunchKernelGGL(k_compact_grouped, dim3(SCAN_REGIONS), dim3(COMPACT_B), 0, st, c->surv, c->sctr, SMALL_SURV_CAP, m.have_freq ? 1 : 0, c->qcur, dl->ent_rec, c->c_rows,
+                       c->soff + n32, crow_cap, c->counters + CTR_OVERFLOW);
   ANX_RANK_LAUNCH(dim3((n32 + 4 * RANK_QPW - 1) / (4 * RANK_QPW)), dim3(256), 0, st, n32, c->soff, c->c_rows, c->qmaxfreq, c->qexpand, ra, c->t_key, c->r_rows, c->r_count, crow_cap,
                   c->counters + CTR_OVERFLOW, SegRows{nullptr, 0u, nullptr});
   hipLaunchKernelGGL(k_small_fetch, dim3(n32 > 256u ? SMALL_FETCH_BLOCKS : 1u), dim3(SMALL_T), 0, st, n32, c->soff, c->r_count, c->r_rows, c->rctr, c->sctr, c->lctr, c->counters, h_off64, rows, (uint32_t)row_cap, crow_cap, h_ctl);

@@ -179,6 +179,24 @@ def _offsets(offs, n: int) -> List[int]:
     return np.ctypeslib.as_array(offs, shape=(n + 1,)).tolist()
 
 
+def _compact_views(rows, offs, via, n: int):
+    """numpy views of one block of compact records ([rows | offsets] or [rows | via | offsets]): ONE owner for the whole block, which
+    every view keeps alive through .base and whose collection releases the block (anx_compact_free)."""
+    import weakref
+
+    import numpy as np
+    dt = np.dtype([("vocab_id", "<u4"), ("freq_score", "<f4"), ("dist_score", "<f8")])
+    off_addr = C.addressof(offs.contents)
+    owner = (C.c_char * (off_addr - rows.value + (n + 1) * 4)).from_address(rows.value)
+    weakref.finalize(owner, L.lib().anx_compact_free, rows, offs)
+    off = np.frombuffer(owner, dtype="<u4", count=n + 1, offset=off_addr - rows.value)
+    total = int(off[-1])
+    rec = np.frombuffer(owner, dtype=dt, count=total)
+    if via is None:
+        return off, rec
+    return off, rec, np.frombuffer(owner, dtype="<u4", count=total, offset=C.addressof(via.contents) - rows.value)
+
+
 class Batch:
     """A batch of queries encoded and resident in HBM (anx_batch_*): encode once, run many times."""
 
@@ -275,23 +293,20 @@ class Batch:
             if release:
                 L.lib().anx_results_free(rows, offs)
 
-    def fetch_compact(self):
+    def fetch_compact(self, with_via: bool = False):
         """-> (offsets[n+1] uint32, rows) with rows a structured array of 16-byte records (vocab_id u32, freq_score f32, dist_score
         f64): anx_batch_fetch_compact, half the bytes of fetch_arrays over PCIe.  Views of the library's pinned block, which is
-        released when the last of them is garbage collected.  Not for models with variant lists or confusables."""
-        import weakref
-
-        import numpy as np
+        released when the last of them is garbage collected.  Not for models with variant lists or confusables.
+        with_via: -> (offsets, rows, via) through anx_batch_fetch_compact_via, for every model, variant lists included: via[r] is
+        the vocabulary id of the variant row r was reached through, 0xFFFFFFFF = none (uint32, one word per row)."""
         rows = C.c_void_p()
         offs = C.POINTER(C.c_uint32)()
-        L.check(L.lib().anx_batch_fetch_compact(self.h, C.byref(rows), C.byref(offs)))
-        dt = np.dtype([("vocab_id", "<u4"), ("freq_score", "<f4"), ("dist_score", "<f8")])
-        off_addr = C.addressof(offs.contents)
-        # ONE owner for the whole block [rows | offsets]: both views keep it alive through .base
-        owner = (C.c_char * (off_addr - rows.value + (self.n + 1) * 4)).from_address(rows.value)
-        weakref.finalize(owner, L.lib().anx_compact_free, rows, offs)
-        off = np.frombuffer(owner, dtype="<u4", count=self.n + 1, offset=off_addr - rows.value)
-        return off, np.frombuffer(owner, dtype=dt, count=int(off[-1]))
+        via = C.POINTER(C.c_uint32)()
+        if with_via:
+            L.check(L.lib().anx_batch_fetch_compact_via(self.h, C.byref(rows), C.byref(offs), C.byref(via)))
+        else:
+            L.check(L.lib().anx_batch_fetch_compact(self.h, C.byref(rows), C.byref(offs)))
+        return _compact_views(rows, offs, via if with_via else None, self.n)
 
     def fetch_pairs(self) -> List[tuple]:
         """-> every scored pair (query, vocab_id, ld|-1, lcs, prefixlen, suffixlen, samecase, score)"""
@@ -362,21 +377,19 @@ class Pipeline:
     def pending(self) -> int:
         return L.lib().anx_pipeline_pending(self.h)
 
-    def next(self):
-        import weakref
-
-        import numpy as np
+    def next(self, with_via: bool = False):
+        """with_via: -> (offsets, rows, via) through anx_pipeline_next_via, as Batch.fetch_compact(with_via=True): what a model with
+        variant lists needs (next() without it raises ANX_EINVAL for such a model's jobs)."""
         rows = C.c_void_p()
         offs = C.POINTER(C.c_uint32)()
+        via = C.POINTER(C.c_uint32)()
         n = C.c_size_t()
-        L.check(L.lib().anx_pipeline_next(self.h, C.byref(rows), C.byref(offs), C.byref(n)))
+        if with_via:
+            L.check(L.lib().anx_pipeline_next_via(self.h, C.byref(rows), C.byref(offs), C.byref(via), C.byref(n)))
+        else:
+            L.check(L.lib().anx_pipeline_next(self.h, C.byref(rows), C.byref(offs), C.byref(n)))
         self._keep.pop(0)
-        dt = np.dtype([("vocab_id", "<u4"), ("freq_score", "<f4"), ("dist_score", "<f8")])
-        off_addr = C.addressof(offs.contents)
-        owner = (C.c_char * (off_addr - rows.value + (n.value + 1) * 4)).from_address(rows.value)
-        weakref.finalize(owner, L.lib().anx_compact_free, rows, offs)
-        off = np.frombuffer(owner, dtype="<u4", count=n.value + 1, offset=off_addr - rows.value)
-        return off, np.frombuffer(owner, dtype=dt, count=int(off[-1]))
+        return _compact_views(rows, offs, via if with_via else None, n.value)
 
     def close(self):
         if self.h:

@@ -31,7 +31,8 @@ extern "C" {
  *    anx_debug_search_stats, anx_debug_small_stats (anx_find_variants_batch's path for small calls); ANX_ADJ_CLOSURE is 0..2 for every builder.  Nothing was removed; every struct of version 2 is unchanged.
  *    Added later within version 3 (additive, no struct changed): learn mode (anx_learn_*, anx_model_variants, anx_model_vocab_type,
  *    anx_format_variant_list, anx_debug_learn_stats / _times); the test hook anx_debug_learn_fold_rows and the test switch
- *    ANX_LEARN_HASH_BITS. */
+ *    ANX_LEARN_HASH_BITS; compact records with `via` for models with variant lists (anx_batch_fetch_compact_via,
+ *    anx_compact_to_results_via, anx_pipeline_next_via: additive, anx_topk_record and every existing call unchanged). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -236,20 +237,31 @@ int anx_batch_fetch(const anx_batch *, anx_result **out_rows, size_t **out_offse
 int anx_batch_fetch_compact(const anx_batch *, anx_topk_record **out_rows, uint32_t **out_offsets);
 void anx_compact_free(anx_topk_record *rows, uint32_t *offsets);
 void anx_compact_to_results(const anx_topk_record *rows, size_t n_rows, anx_result *out);
+/* Compact records for EVERY model: the records of anx_batch_fetch_compact plus a parallel array out_via[n_rows], one word per row:
+ * the vocabulary id of the variant the row was reached through (anx_result::via), UINT32_MAX = none.  The 16-byte record keeps its
+ * layout.  A model without variant lists gets rows and offsets byte-equal to anx_batch_fetch_compact's and every word UINT32_MAX
+ * (written on the host: nothing more crosses PCIe).  Rows, `via` and offsets live in one cached pinned block: release it with
+ * anx_compact_free(rows, offsets).  Host-rescored confusable batches are refused as by anx_batch_fetch_compact.
+ * anx_compact_to_results_via writes the anx_result view (via = ANX_NO_VIA for UINT32_MAX) of n_rows records into caller storage. */
+int anx_batch_fetch_compact_via(const anx_batch *, anx_topk_record **out_rows, uint32_t **out_offsets, uint32_t **out_via);
+void anx_compact_to_results_via(const anx_topk_record *rows, const uint32_t *via, size_t n_rows, anx_result *out);
 /* The staged calls as an asynchronous pipeline for ONE caller thread (the reference's counterpart: independent find_variants calls in
  * flight on rayon's pool, src/bin/analiticcl.rs:445-448): submit hands over a packed buffer (as anx_batch_encode_packed; it must stay
  * valid until that job's results were returned) and returns at once -- ANX_ELIMIT, nothing submitted, when `depth` jobs are in flight
  * already: a job counts until anx_pipeline_next has returned its results, so the caller takes a result first; three library
  * threads encode, run and download the jobs on separate HIP streams, so the upload + encoding of batch i + 2, the device pipeline of
  * batch i + 1 and the download of batch i overlap; anx_pipeline_next returns the oldest job's ranked rows (compact records, as
- * anx_batch_fetch_compact; release with anx_compact_free) in submission order, or that job's error.  Models with variant lists or
- * host-side confusable rescoring are refused by the fetch stage (use the staged calls).  anx_pipeline_free waits for the jobs in
- * flight and drops their results. */
+ * anx_batch_fetch_compact; release with anx_compact_free) in submission order, or that job's error.  Host-side confusable rescoring
+ * is refused by the fetch stage (use the staged calls).  A model with variant lists is served by anx_pipeline_next_via, which also
+ * returns the job's `via` array (as anx_batch_fetch_compact_via; it works for every model); anx_pipeline_next has nowhere to put
+ * `via` and answers ANX_EINVAL for every job of such a model (the job is taken off the queue).  anx_pipeline_free waits for the jobs
+ * in flight and drops their results. */
 typedef struct anx_pipeline anx_pipeline;
 anx_pipeline *anx_pipeline_new(const anx_model *, int depth /* jobs in flight; <= 0: 6 (three stages, each working on one job with one queued) */);
 int anx_pipeline_submit_packed(anx_pipeline *, const char *blob, size_t blob_len, size_t n, const anx_params *);
 int anx_pipeline_pending(const anx_pipeline *); /* jobs submitted and not yet returned */
 int anx_pipeline_next(anx_pipeline *, anx_topk_record **out_rows, uint32_t **out_offsets, size_t *out_n);
+int anx_pipeline_next_via(anx_pipeline *, anx_topk_record **out_rows, uint32_t **out_offsets, uint32_t **out_via, size_t *out_n);
 void anx_pipeline_free(anx_pipeline *);
 /* every scored pair of the batch (order unspecified within a query) */
 int anx_batch_fetch_pairs(const anx_batch *, anx_pair **out_pairs, size_t *out_n);
