@@ -169,6 +169,8 @@ def lib():
         "anx_batch_encode_packed_device": (vp, [vp, vp, sz, sz, C.POINTER(Params)]),
         "anx_batch_encode_packed_device_on": (vp, [vp, vp, sz, sz, C.POINTER(Params), vp]),
         "anx_debug_search_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+        "anx_debug_search_lattice_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+        "anx_debug_contextrule_match": (C.c_int, [vp, sz, sz, u64, C.c_uint32, C.c_int, C.POINTER(C.c_int)]),
         "anx_learn_variants": (C.c_int, [vp, C.POINTER(cp), sz, C.POINTER(Params), C.c_int, C.POINTER(C.c_uint64)]),
         "anx_learn_variants_search": (C.c_int, [vp, C.POINTER(cp), sz, C.POINTER(SearchParams), C.c_int, C.POINTER(C.c_uint64)]),
         "anx_learn_apply_rows": (C.c_int, [vp, C.POINTER(cp), sz, C.POINTER(Result), C.POINTER(sz), C.POINTER(C.c_uint64)]),

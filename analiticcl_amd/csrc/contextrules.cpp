@@ -104,6 +104,44 @@ bool parse_pattern(const std::string& raw, const HostModel& m, PatternMatch& out
   return false;
 }
 
+// One pattern element in the flat form of contextrules_flat.hpp; false when it does not fit (nothing parse_pattern produces).
+bool flatten_element(const PatternMatch& pm, std::vector<FlatAtom>& atoms, FlatElem& e) {
+  auto strip = [](const PatternMatch* p, bool* neg) {
+    *neg = false;
+    while (p->kind == PatternMatch::Not && p->sub.size() == 1) { *neg = !*neg; p = &p->sub[0]; }
+    return p;
+  };
+  auto atom = [&](const PatternMatch& a, bool neg) {
+    FlatAtom f{0u, 0u};
+    switch (a.kind) {
+      case PatternMatch::Any: f.kind = CF_ANY; break;
+      case PatternMatch::NoLexicon: f.kind = CF_NOLEXICON; break;
+      case PatternMatch::Vocab:
+        if (a.vocab_id >= CF_COVERED) return false;
+        f.kind = CF_VOCAB; f.value = (uint32_t)a.vocab_id; break;
+      case PatternMatch::FromLexicon: f.kind = CF_FROMLEXICON; f.value = a.lexicon; break;
+      default: return false;
+    }
+    if (neg) f.kind |= CF_NEG;
+    atoms.push_back(f);
+    return true;
+  };
+  bool neg;
+  const PatternMatch* core = strip(&pm, &neg);
+  e.atom0 = (uint32_t)atoms.size();
+  e.neg = neg ? 1 : 0;
+  if (core->kind == PatternMatch::Disjunction) {
+    if (core->sub.size() > 0xFFFFu) return false;
+    for (const PatternMatch& item : core->sub) {
+      bool ineg;
+      const PatternMatch* a = strip(&item, &ineg);
+      if (!atom(*a, ineg)) return false;
+    }
+  } else if (!atom(*core, false)) return false;
+  e.natoms = (uint16_t)(atoms.size() - e.atom0);
+  return true;
+}
+
 }  // namespace
 
 bool PatternMatch::matches(uint64_t id, uint32_t lexindex) const {
@@ -163,6 +201,19 @@ int HostModel::add_contextrule(const std::string& pattern_s, float score, const 
     r.score = score;
     r.tag = std::move(tag);
     r.tagoffset = std::move(tagoffset);
+    // the same rule for the device decoder
+    FlatRule fr{(uint32_t)flat_rules.elems.size(), (uint32_t)r.pattern.size(), score};
+    bool fits = context_rules.size() < CF_MAX_RULES && r.pattern.size() <= CF_MAX_LEN;
+    for (size_t c = 0; c < r.pattern.size() && fits; ++c) {
+      FlatElem e{0u, 0, 0, 0};
+      fits = flatten_element(r.pattern[c], flat_rules.atoms, e);
+      e.covers = r.tag.empty() ? 1 : 0;  // (test_context_rules: a rule with tags leaves a result only inside a tag offset)
+      for (size_t t = 0; t < r.tag.size() && t < r.tagoffset.size(); ++t)
+        if (c >= r.tagoffset[t].first && c < (size_t)r.tagoffset[t].first + r.tagoffset[t].second) e.covers = 1;
+      flat_rules.elems.push_back(e);
+    }
+    if (fits) flat_rules.rules.push_back(fr);
+    else flat_rules.ok = false;
     context_rules.push_back(std::move(r));
   }
   return ANX_OK;

@@ -124,6 +124,9 @@ struct LatView {
   const uint32_t* btok_off; size_t nboff;
   const int32_t* btok; size_t nbtok;
   size_t out_total;
+  // models with context rules: beside out_syms, what covers each chosen symbol (rule << 8 | position in the rule, 0xFFFFFFFF =
+  // uncovered), [out_total], written by lattice_decode; nullptr: such a model's lattices are handed back
+  uint32_t* out_cover = nullptr;
 };
 // out_n[i] = symbols on the chosen path of stretch i (0xFFFFFFFF: not decoded here -> the host decoder), out_syms[st[i].out0 ..]
 // decodes the lattices [first, first + count) of the view on the replica `dl` (a multi-device model gives every replica a share)
@@ -172,6 +175,7 @@ struct OnePassOut {   // host_result_alloc'd (block, rows): release with host_re
   uint32_t* e_match = nullptr;  // [out_total] per out slot: match index within its stretch
   uint32_t* e_sel = nullptr;    // ... chosen variant, 0xFFFFFFFF = none (out of vocabulary)
   uint32_t* e_row0 = nullptr;   // [out_total + 1] ... first of the match's rows in `rows`
+  uint32_t* cover = nullptr;    // [out_total] models with context rules (else nullptr): rule << 8 | position in the rule that covers the symbol, 0xFFFFFFFF = uncovered
   anx_result* rows = nullptr;
   size_t n_rows = 0;
   bool handed_back = false;     // some lattice is beyond the device decoder's limits: nothing above is valid, take the classic path

@@ -12,6 +12,7 @@
 
 #include "../../include/anx.h"
 #include "confusables_core.hpp"
+#include "contextrules_flat.hpp"
 
 namespace anx {
 
@@ -238,6 +239,7 @@ class HostModel {
  public:
   std::vector<ContextRule> context_rules;  // src/lib.rs:82
   std::vector<std::string> tags;           // src/lib.rs:84
+  FlatRules flat_rules;                    // context_rules as the device decoder reads them (contextrules_flat.hpp): add_contextrule appends
   int add_contextrule(const std::string& pattern, float score, const std::vector<std::string>& tag,
                       const std::vector<std::string>& tagoffset, std::string& err);  // src/lib.rs:658-765
   int read_contextrules(const std::string& path, std::string& err);                  // src/lib.rs:570-656

@@ -3,7 +3,7 @@
 // Replaces, for all stretches of a find_all_matches batch at once, most_likely_sequence
 // (/root/reference/src/lib.rs:2088-2495: lattice with one state per boundary, rustfst shortest_path(nshortest = max_seq), rerank
 // :2318-2425) and lm_score_tokens (:2580-2674) -- the host decoder in search.cpp is the same algorithm and stays as the A/B
-// reference (ANX_LATTICE=host) and for what the device leaves to it (context rules; lattices beyond the limits below).
+// reference (ANX_LATTICE=host) and for what the device leaves to it (lattices beyond the limits below; rule sets outside the flat form).
 // One WAVE decodes one stretch:
 //   k-best  : states in topological order; the K best paths into a state are the K smallest of {best[src][r] + arc} under
 //             (cost, arc, r): every lane holds the head of one incoming arc's (sorted) candidate list, a wave-wide minimum over
@@ -13,7 +13,10 @@
 //             a node's (f32 log-probability sum, token count, last token) = its parent's, extended by the tokens of its symbol --
 //             the same additions in the same order as the host's per-path sum.  Bigram terms come from a device hash table whose
 //             VALUES are the host's logf results (no device logf: bit-identical terms).
-//   select  : perplexity / cost normalisation with portable_log (same bits as the host), weighted mean, first maximum wins;
+//   rules   : models with context rules (k_ctx_rules, between the two kernels): a lane per final path walks its symbols into
+//             scratch rows and runs HostModel::test_context_rules over them on the flat rule table (contextrules_flat.hpp); the f32
+//             sum and its order are the host's.  The chosen path's cover words go out beside its symbols (the host expands the tags).
+//   select  : perplexity / cost / context normalisation with portable_log (same bits as the host), weighted mean, first maximum wins;
 //             the winner's symbols are walked back and written out.
 #include <hip/hip_runtime.h>
 
@@ -53,7 +56,13 @@ struct DeviceLm {  // per replica: the bigram terms and the token lists of the v
   uint32_t* ngram_off = nullptr;         // [V + 1]
   uint32_t* ngram_ids = nullptr;
   uint32_t nvocab = 0;
-  size_t built_vocab = 0, built_bigrams = 0;
+  // the context rules in the flat form of contextrules_flat.hpp and the lexicon mask of every vocabulary id (models with rules only)
+  uint32_t* lexindex = nullptr;          // [nlex]: entry 0 is 0 (out of vocabulary)
+  FlatRule* cr_rules = nullptr;
+  FlatElem* cr_elems = nullptr;
+  FlatAtom* cr_atoms = nullptr;
+  uint32_t nlex = 0, nrules = 0;
+  size_t built_vocab = 0, built_bigrams = 0, built_rules = 0;
 };
 
 struct LNode {   // one of the K best paths into a state: 12 B, written for every node
@@ -97,6 +106,12 @@ struct LatArgs {
   const uint32_t* ngram_off; const uint32_t* ngram_ids; uint32_t nvocab;
   uint32_t* out_n;           // per stretch: symbols of the chosen path, 0xFFFFFFFF = not decoded here (host fallback)
   uint32_t* out_syms;        // [LatStretch::out0 ..]
+  // context rules (scored by k_ctx_rules, used by k_lattice_lm); nrules = 0 and null pointers for a model without rules
+  const uint32_t* lexindex; uint32_t nlex;
+  const FlatRule* cr_rules; const FlatElem* cr_elems; const FlatAtom* cr_atoms; uint32_t nrules;
+  uint32_t* ctxseq;          // [node index]: word (r, i) of a stretch = symbol n - 1 - r of final path i (K words per row, nstates rows)
+  double* ctxval;            // [node0 / 2 + i]: log(context score of final path i / the best one's): the rerank's term
+  uint32_t* out_cover;       // beside out_syms: CF_COVERED-less cover word (rule << 8 | position in the rule) of the chosen path's symbols, 0xFFFFFFFF = uncovered
 };
 
 constexpr uint32_t LAT_MAX_STATES = 1024;   // per stretch, virtual end state included
@@ -303,6 +318,95 @@ __global__ __launch_bounds__(64) void k_lattice(LatArgs a) {
   }
 }
 
+// The context rules of a stretch's final paths (src/lib.rs:2501-2578, HostModel::test_context_rules), between k_lattice and
+// k_lattice_lm for models that have rules (its own kernel: k_lattice_lm keeps its registers and a model without rules its launches):
+// a lane per final path, same launch geometry (G lanes per stretch), no LDS.
+// The path's symbols are walked back once into the stretch's scratch rows (row r, column i: symbol n - 1 - r of path i, so the
+// lanes of a group read and write neighbouring words); the rules then run forwards over them: for every begin, for every rule in
+// table order, a rule matches where all its positions are still uncovered and match, and covers them.  A covered position holds
+// CF_COVERED | rule << 8 | position in the rule instead of the vocabulary id (which nothing reads any more).  The score is the f32
+// sum over the positions in order (rule score / 1.0f for an uncovered one) over n, in double: the host's bits.
+template <uint32_t G>
+__global__ __launch_bounds__(64) void k_ctx_rules(LatArgs a) {
+  constexpr uint32_t NG = 64u / G;
+  const uint32_t lane = threadIdx.x, grp = lane / G, gl = lane % G;
+  const uint32_t slot = blockIdx.x * NG + grp;
+  const bool have = slot < a.count;
+  const uint32_t si = a.index[a.first + (have ? slot : 0u)];
+  const bool alive = have && a.out_n[si] != 0xFFFFFFFFu;  // (k_lattice leaves 0xFFFFFFFF for what it hands to the host decoder)
+  const LatStretch S = a.st[si];
+  const uint32_t K = a.K;
+  const uint32_t ns = S.nstates + 1u, end = ns - 1u;
+  const LNode* __restrict__ nodes = a.nodes + (size_t)(S.node0);
+  const uint32_t npaths = alive ? a.cnts[(size_t)(S.node0 / K) + end] : 0u;
+  uint32_t* __restrict__ cseq = a.ctxseq + (size_t)S.node0;
+  double* __restrict__ cval = a.ctxval + (size_t)(S.node0 / 2u);
+  bool handed_back = false;
+  double best_ctx = 0.0;  // the maximum over the paths, with > (search.cpp: a NaN never gets in)
+  for (uint32_t i = gl; i < npaths; i += G) {
+    uint32_t n = 0;
+    bool fits = true;
+    {
+      uint32_t st_ = end, r = i;
+      for (;;) {
+        const LNode nd = nodes[(size_t)st_ * K + r];
+        if (nd.par == 0xFFFFFFFFu) break;
+        if (nd.sym != 0xFFFFFFFFu) {
+          if (n + 1u >= ns) { fits = false; break; }  // (a path has at most one symbol per state it enters: nstates - 1)
+          cseq[(size_t)n * K + i] = a.syms[S.sym0 + nd.sym].vocab_id;
+          ++n;
+        }
+        st_ = nd.par >> 16; r = nd.par & 0xFFFFu;
+      }
+    }
+    if (!fits) { handed_back = true; continue; }
+    auto at = [&](uint32_t p) -> uint32_t& { return cseq[(size_t)(n - 1u - p) * K + i]; };
+    auto lex_of = [&](uint32_t id) { return id != 0u && id < a.nlex ? a.lexindex[id] : 0u; };
+    bool found = false;
+    for (uint32_t begin = 0; begin < n; ++begin) {
+      const uint32_t id0 = at(begin);
+      if (id0 & CF_COVERED) continue;  // no rule starts on a covered position
+      const uint32_t lex0 = lex_of(id0);
+      for (uint32_t r = 0; r < a.nrules; ++r) {
+        const FlatRule rule = a.cr_rules[r];
+        if (begin + rule.len > n) continue;
+        if (!flat_elem_matches(a.cr_elems[rule.elem0], a.cr_atoms, id0, lex0)) continue;
+        bool ok = true;
+        for (uint32_t c = 1; c < rule.len && ok; ++c) {
+          const uint32_t id = at(begin + c);
+          ok = !(id & CF_COVERED) && flat_elem_matches(a.cr_elems[rule.elem0 + c], a.cr_atoms, id, lex_of(id));
+        }
+        if (!ok) continue;
+        found = true;
+        for (uint32_t c = 0; c < rule.len; ++c)
+          if (a.cr_elems[rule.elem0 + c].covers) at(begin + c) = CF_COVERED | (r << 8) | c;
+        if (at(begin) & CF_COVERED) break;  // the rules behind it find their first position covered
+      }
+    }
+    double ctx = 1.0;
+    if (found) {
+      float sum = 0.0f;
+      for (uint32_t p = 0; p < n; ++p) {
+        const uint32_t w = at(p);
+        sum += (w & CF_COVERED) ? a.cr_rules[(w & ~CF_COVERED) >> 8].score : 1.0f;
+      }
+      ctx = (double)sum / (double)n;
+    }
+    cval[i] = ctx;
+    if (ctx > best_ctx) best_ctx = ctx;
+  }
+  // what the rerank adds for a path: log(ctx / best_ctx), the host's expression (rule scores of zero or below: 0 / 0, logs of
+  // non-positive numbers -- the same NaNs and infinities there)
+#pragma unroll
+  for (int o = (int)G / 2; o; o >>= 1) {
+    const double ox = __shfl_xor(best_ctx, o);
+    best_ctx = ox > best_ctx ? ox : best_ctx;
+  }
+  for (uint32_t i = gl; i < npaths; i += G) cval[i] = portable_log(cval[i] / best_ctx);
+  // not decoded here: the host decoder takes the stretch (written after the group's lanes have read "decoded so far" above)
+  if (handed_back) a.out_n[si] = 0xFFFFFFFFu;
+}
+
 // The second half of a stretch's decoding: LM sums of the nodes on the final paths, rerank, the chosen path's symbols.  Same launch
 // geometry as k_lattice (G lanes per stretch), no LDS.
 template <uint32_t G>
@@ -425,7 +529,10 @@ __global__ __launch_bounds__(64) void k_lattice_lm(LatArgs a) {
       __syncthreads();
     }
   }
-  // ---- rerank (src/lib.rs:2318-2425): no context rules here (the host decodes models that have them) -----------------------------
+  // ---- context rules: k_ctx_rules has left the rerank's term of every final path and, in the scratch rows, what covers its symbols -----
+  const uint32_t* __restrict__ cseq = a.nrules ? a.ctxseq + (size_t)S.node0 : nullptr;
+  const double* __restrict__ cval = a.nrules ? a.ctxval + (size_t)(S.node0 / 2u) : nullptr;
+  // ---- rerank (src/lib.rs:2318-2425) -----------------------------------------------------------------------------------------
   double best_ppl = 999999.0;
   float best_cost = S.best_cost_init;
   for (uint32_t i = gl; i < npaths; i += G) {
@@ -445,9 +552,10 @@ __global__ __launch_bounds__(64) void k_lattice_lm(LatArgs a) {
     best_ppl = op < best_ppl ? op : best_ppl;
     best_cost = oc < best_cost ? oc : best_cost;
   }
-  const bool shortcut = !a.use_lm;  // (!have_lm || lm_weight == 0) && no rules
+  const bool shortcut = !a.use_lm && (!a.nrules || a.contextrules_weight == 0.0f);  // (!have_lm || lm_weight == 0) && (no rules || contextrules_weight == 0)
   double my_score = 0.0;
   uint32_t my_i = 0xFFFFFFFFu;
+  bool nan0 = false;  // path 0 has a NaN score: nothing is greater, it stands (first lane of the group only)
   for (uint32_t i = gl; i < npaths; i += G) {
     const LNode& nd = nodes[(size_t)end * K + i];
     double norm_lm = 0.0;
@@ -458,23 +566,27 @@ __global__ __launch_bounds__(64) void k_lattice_lm(LatArgs a) {
       norm_lm = portable_log(best_ppl / ppl);
     }
     const double norm_var = portable_log((double)best_cost / (double)nd.cost);
-    const double norm_ctx = portable_log(1.0 / 1.0);
+    const double norm_ctx = a.nrules ? cval[i] : portable_log(1.0 / 1.0);
     double score;
     if (shortcut) score = norm_var;
     else
       score = ((double)a.lm_weight * norm_lm + (double)a.variantmodel_weight * norm_var + (double)a.contextrules_weight * norm_ctx) /
               ((double)a.lm_weight + (double)a.variantmodel_weight + (double)a.contextrules_weight);
-    if (my_i == 0xFFFFFFFFu || score > my_score) { my_score = score; my_i = i; }  // first maximum of this lane's paths (ascending i)
+    // first maximum of this lane's paths (ascending i).  A NaN score (rule scores of zero or below: 0 / 0, logs of negative numbers)
+    // never wins a comparison, on the host neither: there path 0 is taken first and stands unless a later score is GREATER -- with a
+    // NaN of its own for good, otherwise the NaNs behind it are passed over.
+    if (score != score) { if (i == 0u) nan0 = true; continue; }
+    if (my_i == 0xFFFFFFFFu || score > my_score) { my_score = score; my_i = i; }
   }
-  // first maximum over the group: larger score wins, equal scores: the smaller path index.  (A NaN score never wins a comparison,
-  // on the host neither: path 0 stands unless a later score is greater.)
+  // first maximum over the group: larger score wins, equal scores: the smaller path index (no NaN among the candidates)
 #pragma unroll
   for (int o = (int)G / 2; o; o >>= 1) {
     const double os = __shfl_xor(my_score, o);
     const uint32_t oi = (uint32_t)__shfl_xor((int)my_i, o);
-    const bool take = oi != 0xFFFFFFFFu && (my_i == 0xFFFFFFFFu || os > my_score || (os == my_score && oi < my_i) || (my_score != my_score && oi < my_i && !(os != os)));
+    const bool take = oi != 0xFFFFFFFFu && (my_i == 0xFFFFFFFFu || os > my_score || (os == my_score && oi < my_i));
     if (take) { my_score = os; my_i = oi; }
   }
+  if (nan0) my_i = 0u;
   if (alive && gl == 0) {  // the winner's symbols, walked back over the back-pointers, written in path order
     uint32_t st_ = end, r = my_i, cnt = 0;
     for (;;) {
@@ -492,6 +604,11 @@ __global__ __launch_bounds__(64) void k_lattice_lm(LatArgs a) {
       if (nd.sym != 0xFFFFFFFFu) a.out_syms[S.out0 + --w] = nd.sym;
       st_ = nd.par >> 16; r = nd.par & 0xFFFFu;
     }
+    if (a.nrules)  // what covers the chosen symbols: the host expands the rules' tags from it
+      for (uint32_t p = 0; p < cnt; ++p) {
+        const uint32_t cw = cseq[(size_t)(cnt - 1u - p) * K + my_i];
+        a.out_cover[S.out0 + p] = (cw & CF_COVERED) ? (cw & ~CF_COVERED) : 0xFFFFFFFFu;
+      }
   }
 }
 
@@ -510,7 +627,7 @@ int lt_upload(T** dst, const void* src, size_t count, std::string& err) {
 void lm_free(DeviceLm* d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
-  for (void* p : {(void*)d->bg_key, (void*)d->bg_val, (void*)d->ngram_off, (void*)d->ngram_ids})
+  for (void* p : {(void*)d->bg_key, (void*)d->bg_val, (void*)d->ngram_off, (void*)d->ngram_ids, (void*)d->lexindex, (void*)d->cr_rules, (void*)d->cr_elems, (void*)d->cr_atoms})
     if (p) pool_free(p);
   delete d;
 }
@@ -519,7 +636,9 @@ static int lm_ensure(const HostModel& m, const DeviceLexicon* dl, std::string& e
   std::lock_guard<std::mutex> g(g_lm_mu);
   DeviceLm*& d = dl->dlm;
   if (!d) { d = new DeviceLm(); d->device = dl->device; }
-  if (d->bg_key && d->built_vocab == m.decoder.size() && d->built_bigrams == m.bigrams.size()) return ANX_OK;
+  const FlatRules& fr = m.flat_rules;
+  const size_t nrules = fr.ok ? fr.rules.size() : 0;  // (a rule set that is not flat: the host decodes, nothing is uploaded)
+  if (d->bg_key && d->built_vocab == m.decoder.size() && d->built_bigrams == m.bigrams.size() && d->built_rules == nrules) return ANX_OK;
   // the bigram terms exactly as search.cpp's term() computes them (src/lib.rs:2632-2674), on the host
   uint32_t cap = 64;
   while (cap < 2 * m.bigrams.size() + 16) cap <<= 1;
@@ -546,6 +665,17 @@ static int lm_ensure(const HostModel& m, const DeviceLexicon* dl, std::string& e
   d->nvocab = (uint32_t)(off.size() - 1);
   d->built_vocab = m.decoder.size();
   d->built_bigrams = m.bigrams.size();
+  d->nrules = 0;
+  if (nrules) {  // the rule table and the lexicon masks, only for models that have rules
+    std::vector<uint32_t> lex(std::max<size_t>(m.decoder.size(), 1), 0u);
+    for (size_t id = 1; id < m.decoder.size(); ++id) lex[id] = m.decoder[id].lexindex;
+    if ((rc = lt_upload(&d->lexindex, lex.data(), lex.size(), err)) || (rc = lt_upload(&d->cr_rules, fr.rules.data(), fr.rules.size(), err)) ||
+        (rc = lt_upload(&d->cr_elems, fr.elems.data(), fr.elems.size(), err)) || (rc = lt_upload(&d->cr_atoms, fr.atoms.data(), fr.atoms.size(), err)))
+      return rc;
+    d->nlex = (uint32_t)lex.size();
+    d->nrules = (uint32_t)nrules;
+  }
+  d->built_rules = nrules;
   return ANX_OK;
 }
 
@@ -555,7 +685,7 @@ static int lm_ensure(const HostModel& m, const DeviceLexicon* dl, std::string& e
 // enqueues whatever still has to happen to the arrays on `st` before the kernels run.  Blocks allocated here go to `owned`.
 static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vector<LatStretch>& hst, const std::vector<uint32_t>& maxdeg, LatStretch* d_st,
                           const uint32_t* d_inoff, const LatArc* d_arcs, const LatSym* d_syms, size_t nsyms_cap, const uint32_t* d_boff, const int32_t* d_btok, uint32_t* d_outn,
-                          uint32_t* d_outs, const anx_search_params& p, hipStream_t st, const std::function<int()>& after_stretch_upload, std::vector<void*>& owned,
+                          uint32_t* d_outs, uint32_t* d_outcover, const anx_search_params& p, hipStream_t st, const std::function<int()>& after_stretch_upload, std::vector<void*>& owned,
                           std::string& err) {
   const size_t n = hst.size();
   const DeviceLm* lm = dl->dlm;
@@ -564,7 +694,9 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
   int rc;
   auto dalloc_ = [&](void** p_, size_t bytes) -> int { HIP_TRY(pool_malloc(p_, std::max<size_t>(bytes, 16))); owned.push_back(*p_); return ANX_OK; };
   // node pool: (nstates + 1) * K nodes per stretch; launches of as many stretches as fit the budget
-  const size_t budget_nodes = ((size_t)6 << 30) / sizeof(LNode);
+  // (with context rules a node also owns two words of the rules' scratch: the same bytes hold fewer nodes)
+  const bool rules_on = lm->nrules > 0 && d_outcover;
+  const size_t budget_nodes = ((size_t)6 << 30) / (sizeof(LNode) + (rules_on ? 2 * sizeof(uint32_t) : 0));
   // Launch order: the stretches none of whose states has more than 64 incoming arcs (and whose cost ring fits half the LDS budget)
   // first, by decreasing number of states -- k_lattice<32> decodes them two per wave, neighbours of this order side by side --,
   // then the others (k_lattice<64>: one per wave, up to 128 incoming arcs).
@@ -609,6 +741,9 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
   if ((rc = dalloc_((void**)&d_cnts, (max_pool / K + 1) * sizeof(uint16_t)))) return rc;
   LmSym* d_lmsym = nullptr;
   if (lm_on && (rc = dalloc_((void**)&d_lmsym, (nsyms_cap + 1) * sizeof(LmSym)))) return rc;
+  uint32_t* d_ctxseq = nullptr;
+  double* d_ctxval = nullptr;
+  if (rules_on && ((rc = dalloc_((void**)&d_ctxseq, max_pool * sizeof(uint32_t))) || (rc = dalloc_((void**)&d_ctxval, (max_pool / 2 + 1) * sizeof(double))))) return rc;
   HIP_TRY(hipMemcpyAsync(d_st, hst.data(), n * sizeof(LatStretch), hipMemcpyHostToDevice, st));
   if (after_stretch_upload) { const int rcu = after_stretch_upload(); if (rcu) return rcu; }  // the caller's uploads / kernels that complete the lattice arrays
   LatArgs a;
@@ -617,6 +752,10 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
   a.lm_weight = p.lm_weight; a.variantmodel_weight = p.variantmodel_weight; a.contextrules_weight = p.contextrules_weight;
   a.bg_key = lm->bg_key; a.bg_val = lm->bg_val; a.bg_mask = lm->bg_mask; a.ngram_off = lm->ngram_off; a.ngram_ids = lm->ngram_ids; a.nvocab = lm->nvocab;
   a.out_n = d_outn; a.out_syms = d_outs;
+  a.lexindex = rules_on ? lm->lexindex : nullptr; a.nlex = rules_on ? lm->nlex : 0u;
+  a.cr_rules = rules_on ? lm->cr_rules : nullptr; a.cr_elems = rules_on ? lm->cr_elems : nullptr; a.cr_atoms = rules_on ? lm->cr_atoms : nullptr;
+  a.nrules = rules_on ? lm->nrules : 0u;
+  a.ctxseq = d_ctxseq; a.ctxval = d_ctxval; a.out_cover = rules_on ? d_outcover : nullptr;
   a.index = d_index;
   // LDS ring of cost lists: as many states as the widest arc of the launch's stretches spans (+ 1), capped by 48 KB per wave
   for (const Launch& l : launches) {
@@ -633,6 +772,12 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
     if (l.lanes == 32u) hipLaunchKernelGGL(k_lattice<32>, dim3((l.count + 1u) / 2u), dim3(64), lds, st, a);
     else hipLaunchKernelGGL(k_lattice<64>, dim3(l.count), dim3(64), lds, st, a);
     ktimer_end(kt, st);
+    if (rules_on) {
+      const int ktc = ktimer_begin("k_ctx_rules", st);
+      if (l.lanes == 32u) hipLaunchKernelGGL(k_ctx_rules<32>, dim3((l.count + 1u) / 2u), dim3(64), 0, st, a);
+      else hipLaunchKernelGGL(k_ctx_rules<64>, dim3(l.count), dim3(64), 0, st, a);
+      ktimer_end(ktc, st);
+    }
     const int kt2 = ktimer_begin("k_lattice_lm", st);
     if (l.lanes == 32u) hipLaunchKernelGGL(k_lattice_lm<32>, dim3((l.count + 1u) / 2u), dim3(64), 0, st, a);
     else hipLaunchKernelGGL(k_lattice_lm<64>, dim3(l.count), dim3(64), 0, st, a);
@@ -668,7 +813,11 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& w
   int rc = lm_ensure(m, dl, err);
   if (rc) return rc;
   const uint32_t K = std::max<uint32_t>(1u, p.max_seq);
-  if (K > 4096u) {  // node pools of (states x K) and the LDS cost ring are sized for the reference's default of 250: the host decoder takes these
+  const bool rules = !m.context_rules.empty();
+  // The host decoder takes all of them when K is beyond what the node pools of (states x K) and the LDS cost ring are sized for (the
+  // reference's default is 250), and, for a model with context rules, when its rule set is not in the flat table, the caller has no
+  // array for the cover words, or a vocabulary id would not fit beside the CF_COVERED bit of a scratch word.
+  if (K > 4096u || (rules && (!m.flat_rules.ok || !whole.out_cover || m.decoder.size() >= CF_COVERED))) {
     for (size_t i = 0; i < count; ++i) out_n[i] = 0xFFFFFFFFu;
     return ANX_OK;
   }
@@ -685,6 +834,8 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& w
       (rc = dalloc_((void**)&d_boff, in.nboff * 4)) || (rc = dalloc_((void**)&d_btok, in.nbtok * 4)) ||
       (rc = dalloc_((void**)&d_outn, n * 4)) || (rc = dalloc_((void**)&d_outs, nout * 4)))
     return rc;
+  uint32_t* d_outcover = nullptr;
+  if (rules && (rc = dalloc_((void**)&d_outcover, nout * 4))) return rc;
   std::vector<LatStretch> hst(in.st, in.st + n);
   std::vector<uint32_t> maxdeg(n, 0u);
   for (size_t j = 0; j < n; ++j) {  // indices relative to the uploaded parts
@@ -701,10 +852,11 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& w
     if (in.nbtok) HIP_TRY(hipMemcpyAsync(d_btok, in.btok, in.nbtok * 4, hipMemcpyHostToDevice, st));
     return ANX_OK;
   };
-  if ((rc = lattice_launch(m, dl, hst, maxdeg, d_st, d_inoff, d_arcs, d_syms, in.nsyms, d_boff, d_btok, d_outn, d_outs, p, st, uploads, owned, err))) return rc;
+  if ((rc = lattice_launch(m, dl, hst, maxdeg, d_st, d_inoff, d_arcs, d_syms, in.nsyms, d_boff, d_btok, d_outn, d_outs, d_outcover, p, st, uploads, owned, err))) return rc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_n, d_outn, n * 4, hipMemcpyDeviceToHost, st));
   if (nout) HIP_TRY(hipMemcpyAsync(out_syms, d_outs, nout * 4, hipMemcpyDeviceToHost, st));
+  if (nout && rules) HIP_TRY(hipMemcpyAsync(whole.out_cover + s0.out0, d_outcover, nout * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return ANX_OK;
 }
@@ -1006,8 +1158,10 @@ int search_onepass_finish(const HostModel& m, const DeviceLexicon* dl, OnePassSt
   const size_t nsym_cap = nres + n_uni + 16, narc_cap = nsym_cap + (in.ngroup - in.nmatch) + 16;
   if (narc_cap >= ((size_t)1 << 32)) { err = "more than 2^32 lattice arcs in one part"; return ANX_ELIMIT; }
   a.narc_cap = (uint32_t)narc_cap; a.nsym_cap = (uint32_t)nsym_cap;
-  uint32_t *d_outn = nullptr, *d_outs = nullptr, *d_boff = nullptr;
+  uint32_t *d_outn = nullptr, *d_outs = nullptr, *d_boff = nullptr, *d_outcover = nullptr;
   int32_t* d_btok = nullptr;
+  const bool rules = !m.context_rules.empty();  // (the caller has checked that they are in the flat table)
+  if (rules && (rc = dalloc_((void**)&d_outcover, in.out_total * 4))) return rc;
   if ((rc = dalloc_((void**)&a.mc, ((size_t)a.nmatch + 1) * 4)) || (rc = dalloc_((void**)&a.gc, ((size_t)a.ngroup + 1) * 4)) || (rc = dalloc_((void**)&a.mflag, (size_t)a.nmatch + 4)) ||
       (rc = dalloc_((void**)&a.sym_off, ((size_t)a.nmatch + 1) * 4)) || (rc = dalloc_((void**)&a.arc_off, ((size_t)a.ngroup + 1) * 4)) ||
       (rc = dalloc_((void**)&a.st, (size_t)a.nst * sizeof(LatStretch))) || (rc = dalloc_((void**)&a.in_off, (size_t)a.nin * 4)) ||
@@ -1039,7 +1193,7 @@ int search_onepass_finish(const HostModel& m, const DeviceLexicon* dl, OnePassSt
       hipLaunchKernelGGL(k_op_stfix, dim3((a.nst + 255) / 256), dim3(256), 0, st, a);
       return ANX_OK;
     };
-    if ((rc = lattice_launch(m, dl, hst, maxdeg, a.st, a.in_off, a.arcs, a.syms, nsym_cap, d_boff, d_btok, d_outn, d_outs, p, st, fix, S->owned, err))) return rc;
+    if ((rc = lattice_launch(m, dl, hst, maxdeg, a.st, a.in_off, a.arcs, a.syms, nsym_cap, d_boff, d_btok, d_outn, d_outs, d_outcover, p, st, fix, S->owned, err))) return rc;
   }
   lap("k_lattice");
   // the matches on the chosen paths and their rows
@@ -1053,17 +1207,19 @@ int search_onepass_finish(const HostModel& m, const DeviceLexicon* dl, OnePassSt
   if (a.nst) hipLaunchKernelGGL(k_op_emit_rows, dim3((a.nst + 255) / 256), dim3(256), 0, st, a);
   // download: per lattice the symbols of its path; per out slot (match, variant, first row); then the rows themselves
   const size_t o_n = 0, o_m = o_n + ((size_t)a.nst * 4 + 63) / 64 * 64, o_s = o_m + ((in.out_total + 1) * 4 + 63) / 64 * 64, o_r = o_s + ((in.out_total + 1) * 4 + 63) / 64 * 64,
-               o_end = o_r + ((in.out_total + 1) * 4 + 63) / 64 * 64 + 64;
+               o_c = o_r + ((in.out_total + 1) * 4 + 63) / 64 * 64, o_end = o_c + (rules ? ((in.out_total + 1) * 4 + 63) / 64 * 64 : 0) + 64;
   char* blk = static_cast<char*>(host_result_alloc(o_end));
   if (!blk) { err = "out of memory"; return ANX_EINVAL; }
   out.block = blk;
   out.out_n = reinterpret_cast<uint32_t*>(blk + o_n); out.e_match = reinterpret_cast<uint32_t*>(blk + o_m);
   out.e_sel = reinterpret_cast<uint32_t*>(blk + o_s); out.e_row0 = reinterpret_cast<uint32_t*>(blk + o_r);
+  out.cover = rules ? reinterpret_cast<uint32_t*>(blk + o_c) : nullptr;
   uint32_t* h_over = reinterpret_cast<uint32_t*>(blk + o_end - 64);
   if (a.nst) HIP_TRY(hipMemcpyAsync(out.out_n, d_outn, (size_t)a.nst * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(out.e_match, a.e_match, (in.out_total + 1) * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(out.e_sel, a.e_sel, (in.out_total + 1) * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(out.e_row0, a.e_row0, (in.out_total + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (rules && in.out_total) HIP_TRY(hipMemcpyAsync(out.cover, d_outcover, in.out_total * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(h_over, a.overflow, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());

@@ -48,6 +48,9 @@ namespace {
 using anx::HostModel;
 std::atomic<uint64_t> g_lat_ns[6];  // ANX_SEARCH_TIMING: time inside most_likely_sequence by part, all threads
 #define g_lat_timing (anx::switches().search_timing != 0)
+// anx_debug_search_lattice_stats: lattices decoded on the device / by the host decoder / on the device with context rules scored,
+// parts that completed as one pass (process totals)
+std::atomic<uint64_t> g_lat_device{0}, g_lat_host{0}, g_lat_device_rules{0}, g_parts_onepass{0};
 inline uint64_t lat_now() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 struct LatLap { uint64_t t; LatLap() : t(g_lat_timing ? lat_now() : 0) {} void lap(int i) { if (g_lat_timing) { const uint64_t n = lat_now(); g_lat_ns[i] += n - t; t = n; } } };
 
@@ -292,6 +295,19 @@ struct OutSym {  // OutputSymbol, src/search.rs:133-150
 // shortest_path(nshortest = max_seq) over a lattice whose states are the boundaries; this is the exact k-best over the
 // same DAG.  The order among equal-cost paths is rustfst-internal in the reference and is not pinned.
 typedef std::vector<std::pair<uint16_t, uint8_t>> TagPool;
+// the tags of one symbol of a path the device decoder chose, from its cover word (rule << 8 | position in the rule, 0xFFFFFFFF =
+// uncovered): what test_context_rules leaves at a covered position and most_likely_sequence copies to the pool
+inline void cover_tags(const HostModel& m, uint32_t cw, TagPool& pool) {
+  if (cw == 0xFFFFFFFFu || (cw >> 8) >= m.context_rules.size()) return;
+  const anx::ContextRule& rule = m.context_rules[cw >> 8];
+  const unsigned c = cw & 0xFFu;
+  for (size_t t = 0; t < rule.tag.size() && t < rule.tagoffset.size(); ++t) {
+    const unsigned b = rule.tagoffset[t].first, l = rule.tagoffset[t].second;
+    if (c >= b && c < b + l) pool.emplace_back(rule.tag[t], (uint8_t)(c - b));
+  }
+}
+// models with context rules reach the device decoder when every rule is in the flat table (contextrules_flat.hpp)
+inline bool rules_on_device(const HostModel& m) { return m.context_rules.empty() || (m.flat_rules.ok && m.decoder.size() < anx::CF_COVERED); }
 void most_likely_sequence(const HostModel& m, const char* text, std::vector<Span>& matches, const Span* bs, size_t nb,
                           size_t end_offset, const anx_search_params& p, std::vector<Span>& out, TagPool& tagpool, uint32_t stretch_index) {
   LatLap lat;
@@ -331,6 +347,7 @@ void most_likely_sequence(const HostModel& m, const char* text, std::vector<Span
   }
   for (size_t i = 0; i < nb; ++i) arcs[i].push_back(Arc{100.0f, i + 1, -1});  // failsafe epsilon transitions
   if (symbols.size() == 1 || finals.empty()) { out.insert(out.end(), matches.begin(), matches.end()); return; }
+  g_lat_host.fetch_add(1, std::memory_order_relaxed);
   lat.lap(0);
   // k-best paths into every state, kept as back-pointers (source state, rank there, symbol).  Arcs only run forward, so the
   // states are in topological order by index and best[s] is final before any state behind it is built.
@@ -886,6 +903,23 @@ static void write_part(const PartOut& po, const char* const* texts, size_t n, co
 // had to fall back to writing it at the end although early output was eligible
 static std::atomic<uint64_t> g_search_multi_calls{0}, g_search_early_kept{0}, g_search_early_dropped{0};
 int anx_debug_search_stats(uint64_t* out) { if (!out) return ANX_EINVAL; out[0] = g_search_multi_calls.load(); out[1] = g_search_early_kept.load(); out[2] = g_search_early_dropped.load(); out[3] = 0; return ANX_OK; }
+int anx_debug_search_lattice_stats(uint64_t* out) {
+  if (!out) return ANX_EINVAL;
+  out[0] = g_lat_device.load(); out[1] = g_lat_host.load(); out[2] = g_lat_device_rules.load(); out[3] = g_parts_onepass.load();
+  return ANX_OK;
+}
+// test hook: one pattern element of a context rule on (vocab id, lexindex), as PatternMatch::matches (flat = 0) or as the flattened
+// element the device decoder evaluates (flat = 1); host code only
+int anx_debug_contextrule_match(const anx_model* model, size_t rule, size_t position, uint64_t vocab_id, uint32_t lexindex, int flat, int* out) {
+  if (!model || !out) return anx_fail(ANX_EINVAL, "NULL argument");
+  const HostModel& m = anx_host_of(model);
+  if (rule >= m.context_rules.size() || position >= m.context_rules[rule].pattern.size()) return anx_fail(ANX_EINVAL, "no such context rule element");
+  if (!flat) { *out = m.context_rules[rule].pattern[position].matches(vocab_id, lexindex) ? 1 : 0; return ANX_OK; }
+  const anx::FlatRules& fr = m.flat_rules;
+  if (!fr.ok || rule >= fr.rules.size() || vocab_id >= anx::CF_COVERED) return anx_fail(ANX_ELIMIT, "the rule set is not in the flat form");
+  *out = anx::flat_elem_matches(fr.elems[fr.rules[rule].elem0 + position], fr.atoms.data(), (uint32_t)vocab_id, lexindex) ? 1 : 0;
+  return ANX_OK;
+}
 int anx_find_all_matches_batch(const anx_model* model, const char* const* texts, size_t n, const anx_search_params* sp,
                                anx_match** out_matches, size_t** out_offsets, anx_result** out_rows, size_t* out_n_rows,
                                anx_match_tag** out_tags) {
@@ -1383,12 +1417,22 @@ static int onepass_part(const anx_model* model, const HostModel& m, const char* 
         r.has_variants = true;
         r.variants = RowView{out.rows + out.e_row0[slot], (size_t)(out.e_row0[slot + 1] - out.e_row0[slot])};
         r.selected = out.e_sel[slot] == 0xFFFFFFFFu ? -1 : (int)out.e_sel[slot];
+        if (out.cover) {  // (as most_likely_sequence fills them)
+          TagPool& pool = po.tagpools[si];
+          r.tag0 = (uint32_t)pool.size();
+          r.tag_stretch = (uint32_t)si;
+          cover_tags(m, out.cover[slot], pool);
+          r.ntags = (uint32_t)pool.size() - r.tag0;
+        }
         o.push_back(r);
       }
       done[si] = 1;
     }
   });
   for (size_t si = 0; si < NS; ++si) if (!has_lat[si]) done[si] = 1;  // (no matches: checked above)
+  g_lat_device.fetch_add(NL, std::memory_order_relaxed);
+  if (out.cover) g_lat_device_rules.fetch_add(NL, std::memory_order_relaxed);
+  g_parts_onepass.fetch_add(1, std::memory_order_relaxed);
   rc = anx::search_onepass_rows_wait(stp, err);  // the rows came down under the loop above (the views only point at them)
   if (rc != ANX_OK) return anx_fail(rc, err);
   lap("one pass: output");
@@ -1446,11 +1490,12 @@ static int find_all_part(const anx_model* model, const char* const* texts, size_
   std::vector<uint8_t> done(stretches.size(), 0);
   bool onepass_done = false;
   {
-    // round 5: the whole part in one device pass (onepass_part) where the device decodes the lattices anyway: one replica, no context
-    // rules (the host decoder applies them), rows final on the device (no host-side confusable rescoring), max_seq within the
-    // decoder's node pools
+    // round 5: the whole part in one device pass (onepass_part) where the device decodes the lattices anyway: one replica, context
+    // rules (if any) in the flat table the device scores, rows final on the device (no host-side confusable rescoring), max_seq
+    // within the decoder's node pools
     const bool lattice_needed = sp->max_ngram > 1 || m.have_lm;
-    const bool eligible = anx::switches().search_onepass && one_replica && lattice_needed && m.context_rules.empty() && !anx::switches().lattice_host &&
+    po.tagpools.assign(m.context_rules.empty() ? 0 : stretches.size(), TagPool());
+    const bool eligible = anx::switches().search_onepass && one_replica && lattice_needed && rules_on_device(m) && !anx::switches().lattice_host &&
                           !(anx::switches().confusables_host && !m.confusables.empty()) && sp->max_seq <= 4096u && sp->max_ngram >= 1 && sp->max_ngram <= 100u &&
                           !stretches.empty();
     if (eligible) {
@@ -1461,6 +1506,7 @@ static int find_all_part(const anx_model* model, const char* const* texts, size_
       if (fb) {  // the classic path starts from clean stretches
         for (Stretch& st : stretches) st.matches.clear();
         for (auto& d : decoded) d.clear();
+        for (TagPool& tp : po.tagpools) tp.clear();
         std::fill(done.begin(), done.end(), 0);
       }
     }
@@ -1615,14 +1661,15 @@ static int find_all_part(const anx_model* model, const char* const* texts, size_
     for (int i = 0; i < 5; ++i) fprintf(stderr, "[anx search]   segments part %-15s %8.2f ms\n", names[i], seg_part[i] * 1e3);
   }
   // consolidate per stretch: the lattices are independent.  Default: all of them in one go on the device (lattice.hip: one wave per
-  // stretch); models with context rules, ANX_LATTICE=host, and the lattices the device hands back are decoded by the host threads
+  // stretch, context rules included); ANX_LATTICE=host, rule sets outside the flat form and the lattices the device hands back are
+  // decoded by the host threads
   // (the reference: rayon over the segments and a sequential loop over the stretches, src/lib.rs:1821-1940).
   std::vector<TagPool>& tagpools = po.tagpools;
-  tagpools.assign(m.context_rules.empty() ? 0 : stretches.size(), TagPool());
   TagPool no_tags;
   const bool need_lattice = sp->max_ngram > 1 || m.have_lm || !m.context_rules.empty();  // src/lib.rs:1912
   const anx::DeviceLexicon* lat_dev = anx_replica_of(model, 0);
-  const bool on_device = !onepass_done && need_lattice && m.context_rules.empty() && !anx::switches().lattice_host && lat_dev && !stretches.empty();
+  const bool on_device = !onepass_done && need_lattice && rules_on_device(m) && !anx::switches().lattice_host && lat_dev && !stretches.empty();
+  const bool dev_rules = on_device && !m.context_rules.empty();
   if (on_device) {
     const bool use_lm = m.have_lm && sp->lm_weight > 0.0f;
     // Chunks of stretches build their lattices side by side, straight into the call's arrays: ONE pinned block (the result cache of
@@ -1667,7 +1714,7 @@ static int find_all_part(const anx_model* model, const char* const* texts, size_
     auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
     const size_t o_st = 0, o_in = o_st + al(max_st * sizeof(anx::LatStretch)), o_arc = o_in + al(T.in * 4), o_sym = o_arc + al(T.arc * sizeof(anx::LatArc)),
                  o_boff = o_sym + al(T.sym * sizeof(anx::LatSym)), o_btok = o_boff + al(T.boff * 4), o_outn = o_btok + al(std::max<size_t>(1, T.btok) * 4),
-                 o_outs = o_outn + al(max_st * 4), o_end = o_outs + al(std::max<size_t>(1, T.out) * 4);
+                 o_outs = o_outn + al(max_st * 4), o_cov = o_outs + al(std::max<size_t>(1, T.out) * 4), o_end = o_cov + (dev_rules ? al(std::max<size_t>(1, T.out) * 4) : 0);
     char* blk = static_cast<char*>(anx::host_result_alloc(o_end));
     if (!blk) { free_kept(); return anx_fail(ANX_EINVAL, "out of memory"); }
     struct BlkFree { char* p; ~BlkFree() { anx::host_result_free(p); } } blk_free{blk};
@@ -1679,6 +1726,7 @@ static int find_all_part(const anx_model* model, const char* const* texts, size_
     int32_t* g_btok = reinterpret_cast<int32_t*>(blk + o_btok);
     uint32_t* out_n = reinterpret_cast<uint32_t*>(blk + o_outn);
     uint32_t* out_syms = reinterpret_cast<uint32_t*>(blk + o_outs);
+    uint32_t* out_cover = dev_rules ? reinterpret_cast<uint32_t*>(blk + o_cov) : nullptr;  // models with context rules: what covers each chosen symbol
     // (plain arrays, not zero-filled vectors: 20 MB of zeroes per part otherwise)
     std::unique_ptr<SymRef[]> osym(new SymRef[std::max<size_t>(1, T.sym)]);
     std::unique_ptr<uint32_t[]> lat_of(new uint32_t[std::max<size_t>(1, max_st)]);  // lattice -> stretch
@@ -1712,7 +1760,7 @@ static int find_all_part(const anx_model* model, const char* const* texts, size_
     }
     struct { size_t st, in, arc, sym, boff, btok, out; } const TT{nlat, T.in, T.arc, T.sym, T.boff, T.btok, T.out};
     lap("lattice input");
-    const anx::LatView L{g_st, TT.st, g_in, TT.in, g_arc, TT.arc, g_sym, TT.sym, g_boff, TT.boff, g_btok, TT.btok, TT.out};
+    const anx::LatView L{g_st, TT.st, g_in, TT.in, g_arc, TT.arc, g_sym, TT.sym, g_boff, TT.boff, g_btok, TT.btok, TT.out, out_cover};
     {  // every replica of the model decodes a contiguous share of the lattices (balanced by lattice nodes), each from a thread of its own
       size_t nrep = 0;
       while (anx_replica_of(model, nrep)) ++nrep;
@@ -1751,9 +1799,18 @@ static int find_all_part(const anx_model* model, const char* const* texts, size_
           const SymRef& o = osym[S.sym0 + out_syms[S.out0 + j]];
           Span r = stretches[si].matches[o.match_index];
           r.selected = o.variant_index;
+          if (out_cover) {  // (as most_likely_sequence fills them)
+            TagPool& pool = tagpools[si];
+            r.tag0 = (uint32_t)pool.size();
+            r.tag_stretch = (uint32_t)si;
+            cover_tags(m, out_cover[S.out0 + j], pool);
+            r.ntags = (uint32_t)pool.size() - r.tag0;
+          }
           out.push_back(std::move(r));
         }
         done[si] = 1;
+        g_lat_device.fetch_add(1, std::memory_order_relaxed);
+        if (out_cover) g_lat_device_rules.fetch_add(1, std::memory_order_relaxed);
       }
     });
   }

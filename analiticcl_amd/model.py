@@ -856,6 +856,21 @@ class VariantModel:
         L.check(L.lib().anx_debug_learn_times(out))
         return dict(zip(("batch", "device_fold", "host_fold", "host_apply", "build", "upload"), list(out)))
 
+    @staticmethod
+    def search_lattice_stats() -> dict:
+        """anx_debug_search_lattice_stats: lattices decoded on the device / by the host decoder / on the device with context rules
+        scored, and parts of search calls that completed as one pass (process totals)."""
+        out = (C.c_uint64 * 4)()
+        L.check(L.lib().anx_debug_search_lattice_stats(out))
+        return {"device": out[0], "host": out[1], "device_rules": out[2], "onepass_parts": out[3]}
+
+    def contextrule_element_matches(self, rule: int, position: int, vocab_id: int, lexindex: int, flat: bool = False) -> bool:
+        """Test hook (anx_debug_contextrule_match): element `position` of context rule `rule` on (vocab_id, lexindex), evaluated as
+        the parsed pattern (flat=False) or as the flattened element the device decoder reads (flat=True)."""
+        out = C.c_int(0)
+        L.check(L.lib().anx_debug_contextrule_match(self.h, rule, position, vocab_id, lexindex, 1 if flat else 0, C.byref(out)))
+        return bool(out.value)
+
     def add_contextrule(self, pattern: str, score: float, tag: Sequence[str] = (), tagoffset: Sequence[str] = ()):
         t = (C.c_char_p * max(1, len(tag)))(*[_b(x) for x in tag])
         o = (C.c_char_p * max(1, len(tagoffset)))(*[_b(x) for x in tagoffset])

@@ -32,7 +32,9 @@ extern "C" {
  *    Added later within version 3 (additive, no struct changed): learn mode (anx_learn_*, anx_model_variants, anx_model_vocab_type,
  *    anx_format_variant_list, anx_debug_learn_stats / _times); the test hook anx_debug_learn_fold_rows and the test switch
  *    ANX_LEARN_HASH_BITS; compact records with `via` for models with variant lists (anx_batch_fetch_compact_via,
- *    anx_compact_to_results_via, anx_pipeline_next_via: additive, anx_topk_record and every existing call unchanged). */
+ *    anx_compact_to_results_via, anx_pipeline_next_via: additive, anx_topk_record and every existing call unchanged);
+ *    anx_debug_search_lattice_stats and the test hook anx_debug_contextrule_match (models with context rules are decoded on the
+ *    device: additive, results unchanged). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -357,6 +359,15 @@ int anx_debug_kernel_time(const char *name, double *total_ms, uint64_t *launches
  * calls whose output arrays were written while later parts were still on the device, out[2] = calls that were eligible for that but
  * had to write at the end (an upper bound did not hold), out[3] = 0 (reserved). */
 int anx_debug_search_stats(uint64_t out[4]);
+/* Where search mode's lattices were decoded since the library was loaded: out[0] = lattices decoded on the device, out[1] = lattices
+ * decoded by the host decoder (ANX_LATTICE=host, lattices beyond the device decoder's limits, rule sets outside its flat form),
+ * out[2] = of out[0], those of models with context rules (the device scored the rules of every final path), out[3] = parts of calls
+ * that completed as one device pass. */
+int anx_debug_search_lattice_stats(uint64_t out[4]);
+/* Test hook: element `position` of context rule `rule` of the model on (vocab_id, lexindex) -- flat = 0: as the parsed pattern
+ * (PatternMatch::matches, what the host decoder evaluates), flat = 1: as the flattened element the device decoder evaluates.  *out = 0 / 1.
+ * Host code only.  ANX_EINVAL: no such element; ANX_ELIMIT (flat = 1): the model's rule set is not in the flat form. */
+int anx_debug_contextrule_match(const anx_model *model, size_t rule, size_t position, uint64_t vocab_id, uint32_t lexindex, int flat, int *out);
 /* The small call: anx_find_variants_batch answers calls of at most 4096 inputs of at most 64 bytes each (single-device models without
  * variant lists, confusables or StopAtExactMatch) through a path of nine launches and one host wait with preallocated buffers (the
  * reference's own granularity: one string per call, src/lib.rs:972; 1 000 per batch, src/bin/analiticcl.rs:416) instead of the batch
