@@ -115,12 +115,6 @@ struct anx_batch {
   std::vector<uint32_t> in_off;   // n + 1 offsets into in_text
 };
 
-// anx::batch_fetch_compact_via_into as compact_via_capi.cpp hands it over (see anx_compact_fetch)
-using anx_compact_via_into = int (*)(const anx::Batch*, anx_topk_record*, uint32_t*, uint32_t*, uint32_t, bool, std::string&);
-struct anx_pipeline;
-int anx_compact_fetch(const anx_batch* b, anx_topk_record** rows, uint32_t** offs, uint32_t** via, anx_compact_via_into via_into);
-int anx_pipeline_take(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, uint32_t** via, size_t* n);
-
 static thread_local std::string g_err;
 static thread_local int g_code = 0;
 static int fail(int code, const std::string& msg) {
@@ -1339,7 +1333,7 @@ int anx_batch_run(const anx_model* m, anx_batch* b, void* stream) {
 // their rows to where they belong.  Row = anx_result / anx_topk_record, Off = size_t / uint32_t.  via_out (compact records of a
 // model with variant lists): one more word per row, which takes the same way; fetch_into gets nullptr for it otherwise.
 template <typename Row, typename Off, typename FetchFn>
-static int scatter_fetch(const anx_batch* b, Row* out, Off* off, const FetchFn& fetch_into, uint32_t* via_out = nullptr) {
+static int scatter_fetch(const anx_batch* b, Row* out, Off* off, uint32_t* via_out, const FetchFn& fetch_into) {
   const size_t n = b->n_input, S = b->shards.size();
   std::vector<Row*> rows(S, nullptr);
   std::vector<uint32_t*> vias(S, nullptr);
@@ -1351,7 +1345,7 @@ static int scatter_fetch(const anx_batch* b, Row* out, Off* off, const FetchFn& 
     if (via_out) vias[g] = static_cast<uint32_t*>(anx::host_result_alloc(std::max<size_t>(1, anx::batch_n_results(s.b)) * sizeof(uint32_t)));
     if (!rows[g] || (via_out && !vias[g])) { err = "out of memory"; return (int)ANX_EINVAL; }
     loff[g].assign(s.n + 1, 0);
-    return fetch_into(s.b, rows[g], loff[g].data(), vias[g], err);
+    return fetch_into(s.b, rows[g], loff[g].data(), vias[g], (Off)0, err);
   });
   if (rc) { release(); return rc; }
   for (size_t i = 0; i <= n; ++i) off[i] = 0;
@@ -1377,37 +1371,42 @@ static bool scattered(const anx_batch* b) {
   for (const Shard& s : b->shards) if (!s.idx.empty()) return true;
   return false;
 }
+static size_t total_results(const anx_batch* b) {
+  size_t total = 0;
+  for (const Shard& s : b->shards) total += anx::batch_n_results(s.b);
+  return total;
+}
+// Rows of a batch of every shard layout in the call's input order: out[0 .. total_results), off[0 .. n_input], via_out (or nullptr)
+// alike.  One shard or consecutive shards: every shard downloads straight into its slice of the call's arrays (the sizes are known
+// since the run); scattered shards: scatter_fetch.  fetch_into(shard, rows, offsets, via, first row, err) is the engine's fetch.
+template <typename Row, typename Off, typename FetchFn>
+static int fetch_shards(const anx_batch* b, Row* out, Off* off, uint32_t* via_out, const FetchFn& fetch_into) {
+  if (scattered(b)) return scatter_fetch(b, out, off, via_out, fetch_into);
+  const size_t S = b->shards.size();
+  std::vector<size_t> base(S + 1, 0);
+  for (size_t g = 0; g < S; ++g) base[g + 1] = base[g] + anx::batch_n_results(b->shards[g].b);
+  const int rc = on_shards(b, [&](size_t g, std::string& err) {
+    const Shard& s = b->shards[g];
+    std::vector<Off> tmp;  // a shard writes n + 1 offsets; its last one is the next shard's first (same value): keep the slices disjoint
+    Off* dst = off + s.lo;
+    if (g + 1 < S) { tmp.resize(s.n + 1); dst = tmp.data(); }
+    const int r = fetch_into(s.b, out + base[g], dst, via_out ? via_out + base[g] : nullptr, (Off)base[g], err);
+    if (r == ANX_OK && g + 1 < S && s.n) memcpy(off + s.lo, tmp.data(), s.n * sizeof(Off));
+    return r;
+  });
+  if (rc == ANX_OK) off[b->n_input] = (Off)base[S];
+  return rc;
+}
 extern "C" {
 int anx_batch_fetch(const anx_batch* b, anx_result** rows, size_t** offs) {
   if (!b || !rows || !offs) return fail(ANX_EINVAL, "NULL argument");
-  // one row array for the whole call; every shard downloads straight into its slice (the sizes are known since the run)
-  const size_t n = b->n_input, S = b->shards.size();
-  std::vector<size_t> base(S + 1, 0);
-  for (size_t g = 0; g < S; ++g) base[g + 1] = base[g] + anx::batch_n_results(b->shards[g].b);
-  size_t* off = static_cast<size_t*>(malloc((n + 1) * sizeof(size_t)));
-  anx_result* out = static_cast<anx_result*>(anx::host_result_alloc(std::max<size_t>(1, base[S]) * sizeof(anx_result)));
+  size_t* off = static_cast<size_t*>(malloc((b->n_input + 1) * sizeof(size_t)));
+  anx_result* out = static_cast<anx_result*>(anx::host_result_alloc(std::max<size_t>(1, total_results(b)) * sizeof(anx_result)));
   if (!off || !out) { free(off); anx::host_result_free(out); return fail(ANX_EINVAL, "out of memory"); }
-  if (scattered(b)) {
-    const int rcs = scatter_fetch<anx_result, size_t>(b, out, off, [](const anx::Batch* sb, anx_result* r, size_t* o, uint32_t*, std::string& err) {
-      return anx::batch_fetch_into(sb, r, o, 0, err);
-    });
-    if (rcs) { free(off); anx::host_result_free(out); return rcs; }
-    if (b->rescore) rescore_with_confusables(b->model->host, b->in_text, b->in_off, b->params, out, off);
-    *rows = out;
-    *offs = off;
-    return ANX_OK;
-  }
-  const int rc = on_shards(b, [&](size_t g, std::string& err) {
-    const Shard& s = b->shards[g];
-    std::vector<size_t> tmp;  // a shard writes n + 1 offsets; its last one is the next shard's first (same value): keep the slices disjoint
-    size_t* dst = off + s.lo;
-    if (g + 1 < S) { tmp.resize(s.n + 1); dst = tmp.data(); }
-    const int r = anx::batch_fetch_into(s.b, out + base[g], dst, base[g], err);
-    if (r == ANX_OK && g + 1 < S && s.n) memcpy(off + s.lo, tmp.data(), s.n * sizeof(size_t));
-    return r;
+  const int rc = fetch_shards(b, out, off, nullptr, [](const anx::Batch* sb, anx_result* r, size_t* o, uint32_t*, size_t at, std::string& err) {
+    return anx::batch_fetch_into(sb, r, o, at, err);
   });
   if (rc) { free(off); anx::host_result_free(out); return rc; }
-  off[n] = base[S];
   if (b->rescore) rescore_with_confusables(b->model->host, b->in_text, b->in_off, b->params, out, off);
   *rows = out;
   *offs = off;
@@ -1415,79 +1414,65 @@ int anx_batch_fetch(const anx_batch* b, anx_result** rows, size_t** offs) {
 }
 }  // extern "C"
 static const char kCompactNoVia[] = "variant lists are loaded: compact records carry no `via`, use anx_batch_fetch";
-// Compact records of every shard layout (one shard, contiguous shards, scattered shards) in ONE pinned block of the result cache.
-// via == nullptr: [rows | offsets], filled by anx::batch_fetch_compact_into.  Else [rows | via | offsets], filled by via_into, the
-// engine's fetch that also writes the `via` words: compact_via_capi.cpp hands it in (anx_batch_fetch_compact_via) or installs it
-// for the pipeline's fetch stage, so that this file refers to no engine symbol the CPU harness' stub engine lacks.
-int anx_compact_fetch(const anx_batch* b, anx_topk_record** rows, uint32_t** offs, uint32_t** via, anx_compact_via_into via_into) {
-  if (b->rescore) return fail(ANX_EINVAL, "confusables are loaded: results are rescored on the host, use anx_batch_fetch");
-  if (via && !via_into) return fail(ANX_EINVAL, kCompactNoVia);
-  const bool plain = !b->model->host.lex.any_variants;
-  const size_t n = b->n_input, S = b->shards.size();
-  std::vector<size_t> base(S + 1, 0);
-  for (size_t g = 0; g < S; ++g) base[g + 1] = base[g] + anx::batch_n_results(b->shards[g].b);
-  if (base[S] >= ((size_t)1 << 32)) return fail(ANX_ELIMIT, "more than 2^32 result rows: use anx_batch_fetch");
-  // (the offsets are pinned as well: they are a D2H target)
-  const size_t row_bytes = (std::max<size_t>(1, base[S]) * sizeof(anx_topk_record) + 63) & ~(size_t)63;
-  const size_t via_bytes = via ? (std::max<size_t>(1, base[S]) * sizeof(uint32_t) + 63) & ~(size_t)63 : 0;
+// Compact records live in ONE pinned block of the result cache, [rows | via | offsets] or [rows | offsets]: rows and via rounded to
+// 64 bytes, n + 2 offset words (the offsets are pinned as well: they are a D2H target).  rows == nullptr: out of memory.
+struct CompactBlock { anx_topk_record* rows; uint32_t* via; uint32_t* offs; };
+static CompactBlock compact_block(size_t total, size_t n, bool with_via) {
+  const size_t row_bytes = (std::max<size_t>(1, total) * sizeof(anx_topk_record) + 63) & ~(size_t)63;
+  const size_t via_bytes = with_via ? (std::max<size_t>(1, total) * sizeof(uint32_t) + 63) & ~(size_t)63 : 0;
   char* blk = static_cast<char*>(anx::host_result_alloc(row_bytes + via_bytes + (n + 2) * sizeof(uint32_t)));
-  if (!blk) return fail(ANX_EINVAL, "out of memory");
-  anx_topk_record* out = reinterpret_cast<anx_topk_record*>(blk);
-  uint32_t* vout = via ? reinterpret_cast<uint32_t*>(blk + row_bytes) : nullptr;
-  uint32_t* off = reinterpret_cast<uint32_t*>(blk + row_bytes + via_bytes);
-  auto fetch_into = [&](const anx::Batch* sb, anx_topk_record* r, uint32_t* o, uint32_t* v, uint32_t at, std::string& err) {
-    return v ? via_into(sb, r, o, v, at, plain, err) : anx::batch_fetch_compact_into(sb, r, o, at, err);
-  };
-  if (scattered(b)) {
-    const int rcs = scatter_fetch<anx_topk_record, uint32_t>(b, out, off, [&](const anx::Batch* sb, anx_topk_record* r, uint32_t* o, uint32_t* v, std::string& err) {
-      return fetch_into(sb, r, o, v, 0u, err);
-    }, vout);
-    if (rcs) { anx::host_result_free(blk); return rcs; }
-    *rows = out;
-    *offs = off;
-    if (via) *via = vout;
-    return ANX_OK;
-  }
-  const int rc = on_shards(b, [&](size_t g, std::string& err) {
-    const Shard& s = b->shards[g];
-    std::vector<uint32_t> tmp;  // the last offset of a shard is the first of the next: keep the slices disjoint
-    uint32_t* dst = off + s.lo;
-    if (g + 1 < S) { tmp.resize(s.n + 1); dst = tmp.data(); }
-    const int r = fetch_into(s.b, out + base[g], dst, vout ? vout + base[g] : nullptr, (uint32_t)base[g], err);
-    if (r == ANX_OK && g + 1 < S && s.n) memcpy(off + s.lo, tmp.data(), s.n * sizeof(uint32_t));
-    return r;
+  if (!blk) return CompactBlock{nullptr, nullptr, nullptr};
+  return CompactBlock{reinterpret_cast<anx_topk_record*>(blk), with_via ? reinterpret_cast<uint32_t*>(blk + row_bytes) : nullptr,
+                      reinterpret_cast<uint32_t*>(blk + row_bytes + via_bytes)};
+}
+// Compact records of every shard layout; via != nullptr: with the `via` words (a model without variant lists: all 0xFFFFFFFF)
+static int anx_compact_fetch(const anx_batch* b, anx_topk_record** rows, uint32_t** offs, uint32_t** via) {
+  if (b->rescore) return fail(ANX_EINVAL, "confusables are loaded: results are rescored on the host, use anx_batch_fetch");
+  const bool plain = !b->model->host.lex.any_variants;
+  const size_t total = total_results(b);
+  if (total >= ((size_t)1 << 32)) return fail(ANX_ELIMIT, "more than 2^32 result rows: use anx_batch_fetch");
+  const CompactBlock k = compact_block(total, b->n_input, via != nullptr);
+  if (!k.rows) return fail(ANX_EINVAL, "out of memory");
+  const int rc = fetch_shards(b, k.rows, k.offs, k.via, [&](const anx::Batch* sb, anx_topk_record* r, uint32_t* o, uint32_t* v, uint32_t at, std::string& err) {
+    return anx::batch_fetch_compact_into(sb, r, o, v, at, plain, err);
   });
-  if (rc) { anx::host_result_free(blk); return rc; }
-  off[n] = (uint32_t)base[S];
-  *rows = out;
-  *offs = off;
-  if (via) *via = vout;
+  if (rc) { anx::host_result_free(k.rows); return rc; }
+  *rows = k.rows;
+  *offs = k.offs;
+  if (via) *via = k.via;
   return ANX_OK;
 }
-// what compact_via_capi.cpp installs when it is part of the library: the pipeline's fetch stage serves variant-list models with it
-static anx_compact_via_into g_via_into = nullptr;
-void anx_compact_via_install(anx_compact_via_into f) { g_via_into = f; }
+static void compact_to_results(const anx_topk_record* rows, const uint32_t* via, size_t n_rows, anx_result* out) {
+  auto work = [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i)
+      out[i] = anx_result{rows[i].vocab_id, rows[i].dist_score, (double)rows[i].freq_score, !via || via[i] == 0xFFFFFFFFu ? ANX_NO_VIA : (uint64_t)via[i]};
+  };
+  const unsigned nthreads = n_rows < (1u << 16) ? 1u : std::max(1u, std::min(16u, anx::usable_hw_threads()));
+  if (nthreads == 1) { work(0, n_rows); return; }
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < nthreads; ++t) th.emplace_back(work, n_rows * t / nthreads, n_rows * (t + 1) / nthreads);
+  for (auto& x : th) x.join();
+}
 extern "C" {
 int anx_batch_fetch_compact(const anx_batch* b, anx_topk_record** rows, uint32_t** offs) {
   if (!b || !rows || !offs) return fail(ANX_EINVAL, "NULL argument");
   if (b->rescore) return fail(ANX_EINVAL, "confusables are loaded: results are rescored on the host, use anx_batch_fetch");
   if (b->model->host.lex.any_variants) return fail(ANX_EINVAL, kCompactNoVia);
-  return anx_compact_fetch(b, rows, offs, nullptr, nullptr);
+  return anx_compact_fetch(b, rows, offs, nullptr);
+}
+int anx_batch_fetch_compact_via(const anx_batch* b, anx_topk_record** rows, uint32_t** offs, uint32_t** via) {
+  if (!b || !rows || !offs || !via) return fail(ANX_EINVAL, "NULL argument");
+  return anx_compact_fetch(b, rows, offs, via);
 }
 void anx_compact_free(anx_topk_record* rows, uint32_t* offsets) {
   (void)offsets;  // one block: the offsets live behind the rows
   anx::host_result_free(rows);
 }
 void anx_compact_to_results(const anx_topk_record* rows, size_t n_rows, anx_result* out) {
-  if (!rows || !out) return;
-  auto work = [&](size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi; ++i) out[i] = anx_result{rows[i].vocab_id, rows[i].dist_score, (double)rows[i].freq_score, ANX_NO_VIA};
-  };
-  unsigned nthreads = n_rows < (1u << 16) ? 1u : std::max(1u, std::min(16u, anx::usable_hw_threads()));
-  if (nthreads == 1) { work(0, n_rows); return; }
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nthreads; ++t) th.emplace_back(work, n_rows * t / nthreads, n_rows * (t + 1) / nthreads);
-  for (auto& x : th) x.join();
+  if (rows && out) compact_to_results(rows, nullptr, n_rows, out);
+}
+void anx_compact_to_results_via(const anx_topk_record* rows, const uint32_t* via, size_t n_rows, anx_result* out) {
+  if (rows && via && out) compact_to_results(rows, via, n_rows, out);
 }
 int anx_batch_fetch_pairs(const anx_batch* b, anx_pair** out, size_t* n) {
   if (!b || !out || !n) return fail(ANX_EINVAL, "NULL argument");
@@ -1746,11 +1731,9 @@ static void pipeline_stage(anx_pipeline* pl, int stage) {
       } else {
         if (pl->fetch_stream)  // the run has been waited for: its rows are downloaded on the pipeline's download stream
           for (Shard& s_ : job->b->shards) anx::batch_set_last_stream(s_.b, pl->fetch_stream);
-        // a model with variant lists needs the fetch that carries `via` (compact_via_capi.cpp installs it); without it
-        // anx_batch_fetch_compact refuses such a model
-        if (g_via_into && (pl->m->host.lex.any_variants || pl->want_via.load()))
-          job->rc = anx_compact_fetch(job->b, &job->rows, &job->offs, &job->via, g_via_into);
-        else job->rc = anx_batch_fetch_compact(job->b, &job->rows, &job->offs);
+        // a model with variant lists is fetched with `via` (the records alone would drop it), a plain one once the caller has asked
+        const bool with_via = pl->m->host.lex.any_variants || pl->want_via.load();
+        job->rc = anx_compact_fetch(job->b, &job->rows, &job->offs, with_via ? &job->via : nullptr);
         if (job->rc) job->err = g_err;
       }
     }
@@ -1818,16 +1801,12 @@ int anx_pipeline_pending(const anx_pipeline* pl) {
   std::lock_guard<std::mutex> lk(const_cast<anx_pipeline*>(pl)->mu);
   return (int)pl->jobs.size();
 }
-int anx_pipeline_next(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, size_t* n) {
-  if (!pl || !rows || !offs) return fail(ANX_EINVAL, "NULL argument");
-  return anx_pipeline_take(pl, rows, offs, nullptr, n);
-}
 }  // extern "C"
 // The oldest job's results, or its error.  via == nullptr (anx_pipeline_next): a job of a model with variant lists is refused as the
 // fetch stage refused it before it could carry `via` (the records alone would drop it silently).  via != nullptr
-// (anx_pipeline_next_via, compact_via_capi.cpp): a job fetched without `via` -- a plain model, before the caller first asked --
-// moves into a block with room for it, every word 0xFFFFFFFF.
-int anx_pipeline_take(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, uint32_t** via, size_t* n) {
+// (anx_pipeline_next_via): a job fetched without `via` -- a plain model, before the caller first asked -- moves into a block with
+// room for it, every word 0xFFFFFFFF.
+static int anx_pipeline_take(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, uint32_t** via, size_t* n) {
   if (via) pl->want_via.store(true);
   std::shared_ptr<PipeJob> job;
   {
@@ -1845,17 +1824,15 @@ int anx_pipeline_take(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs,
   }
   if (via && !job->via) {
     const size_t total = job->offs[job->n];
-    const size_t row_bytes = (std::max<size_t>(1, total) * sizeof(anx_topk_record) + 63) & ~(size_t)63;
-    const size_t via_bytes = (std::max<size_t>(1, total) * sizeof(uint32_t) + 63) & ~(size_t)63;
-    char* blk = static_cast<char*>(anx::host_result_alloc(row_bytes + via_bytes + (job->n + 2) * sizeof(uint32_t)));
-    if (!blk) { anx_compact_free(job->rows, job->offs); return fail(ANX_EINVAL, "out of memory"); }
-    memcpy(blk, job->rows, total * sizeof(anx_topk_record));
-    memset(blk + row_bytes, 0xFF, total * sizeof(uint32_t));
-    memcpy(blk + row_bytes + via_bytes, job->offs, (job->n + 1) * sizeof(uint32_t));
+    const CompactBlock k = compact_block(total, job->n, true);
+    if (!k.rows) { anx_compact_free(job->rows, job->offs); return fail(ANX_EINVAL, "out of memory"); }
+    memcpy(k.rows, job->rows, total * sizeof(anx_topk_record));
+    memset(k.via, 0xFF, total * sizeof(uint32_t));
+    memcpy(k.offs, job->offs, (job->n + 1) * sizeof(uint32_t));
     anx_compact_free(job->rows, job->offs);
-    job->rows = reinterpret_cast<anx_topk_record*>(blk);
-    job->via = reinterpret_cast<uint32_t*>(blk + row_bytes);
-    job->offs = reinterpret_cast<uint32_t*>(blk + row_bytes + via_bytes);
+    job->rows = k.rows;
+    job->via = k.via;
+    job->offs = k.offs;
   }
   *rows = job->rows;
   *offs = job->offs;
@@ -1864,6 +1841,14 @@ int anx_pipeline_take(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs,
   return ANX_OK;
 }
 extern "C" {
+int anx_pipeline_next(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, size_t* n) {
+  if (!pl || !rows || !offs) return fail(ANX_EINVAL, "NULL argument");
+  return anx_pipeline_take(pl, rows, offs, nullptr, n);
+}
+int anx_pipeline_next_via(anx_pipeline* pl, anx_topk_record** rows, uint32_t** offs, uint32_t** via, size_t* n) {
+  if (!pl || !rows || !offs || !via) return fail(ANX_EINVAL, "NULL argument");
+  return anx_pipeline_take(pl, rows, offs, via, n);
+}
 void anx_pipeline_free(anx_pipeline* pl) {
   if (!pl) return;
   for (;;) {  // the jobs in flight finish; their results are dropped

@@ -60,7 +60,6 @@ int batch_wait(const HostModel& m, const DeviceLexicon* dl, Batch* b, std::strin
 void batch_set_last_stream(Batch* b, void* stream);  // where the fetches / exports of a FINISHED run are enqueued from now on
 int batch_fetch(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_result** rows, size_t** offs,
                 std::string& err);
-// the same into caller-provided storage: rows[0 .. batch_n_results) and offs[0 .. batch_n_input] = base + CSR offsets
 // The small call (small_path.hpp): find_variants for at most 4096 inputs of at most 64 bytes in eleven launches and one host wait,
 // no allocation.  0: done (*rows: a block of the pinned result cache, *offs: malloc'd, as batch_fetch returns them); 1: not taken
 // (too many / too long inputs, StopAtExactMatch, a fixed capacity exceeded): use the batch path; negative: device error.
@@ -69,11 +68,13 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
 void small_stats(uint64_t* out);  // out[0] = calls the small path answered, out[1] = calls it handed to the batch path after a capacity overflow
 size_t batch_n_results(const Batch* b);
 size_t batch_n_input(const Batch* b);
+// batch_fetch into caller-provided storage: rows[0 .. batch_n_results) and offs[0 .. batch_n_input] = base + CSR offsets (a shard
+// of a multi-device batch fills its slice of the whole call's arrays)
 int batch_fetch_into(const Batch* b, anx_result* rows, size_t* offs, size_t base, std::string& err);
-int batch_fetch_compact_into(const Batch* b, anx_topk_record* rows, uint32_t* offs, uint32_t base, std::string& err);
-// the same plus via[0 .. batch_n_results): the vocabulary id of the variant a row was reached through, 0xFFFFFFFF = none
-// (plain: a model without variant lists -- the words are written on the host, nothing more crosses PCIe)
-int batch_fetch_compact_via_into(const Batch* b, anx_topk_record* rows, uint32_t* offs, uint32_t* via, uint32_t base, bool plain, std::string& err);
+// the same as 16-byte records with u32 offsets.  via (may be null): via[0 .. batch_n_results), the vocabulary id of the variant a
+// row was reached through, 0xFFFFFFFF = none; plain: a model without variant lists -- the words are written on the host, nothing
+// more crosses PCIe
+int batch_fetch_compact_into(const Batch* b, anx_topk_record* rows, uint32_t* offs, uint32_t* via, uint32_t base, bool plain, std::string& err);
 int batch_fetch_pairs(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_pair** out, size_t* n,
                       std::string& err);
 int batch_pair_counts(const HostModel& m, const DeviceLexicon* dl, Batch* b, uint32_t** out, std::string& err);

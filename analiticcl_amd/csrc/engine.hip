@@ -1702,127 +1702,73 @@ void batch_set_last_stream(Batch* b, void* stream) { if (b && !b->launched) b->l
 size_t batch_n_results(const Batch* b) { return b->ran ? (size_t)b->n_results : 0; }
 size_t batch_n_input(const Batch* b) { return b->n_input; }
 
-// Downloads the ranked rows of the batch into caller-provided storage: out[0 .. n_results) and off[0 .. n_input] = base + the
-// CSR offsets (a shard of a multi-device batch writes its slice of the whole call's arrays).
-int batch_fetch_into(const Batch* b, anx_result* out, size_t* off, size_t base, std::string& err) {
+// The way of the ranked rows into the CALLER's input order, enqueued on st -- what every fetch and the compact export share: the
+// counts scattered to the original indices (d_cnt[n_input]), an exclusive scan over them (d_off[n_input + 1]; d_tmp: the scan's
+// block sums, scan_tmp_bytes), and the row copy through `emit` (kernels_rank.hpp) to where the offsets say.
+static size_t scan_tmp_bytes(size_t n) { return ((n + SCAN_TILE - 1) / SCAN_TILE + 2) * sizeof(uint32_t); }
+template <typename Emit>
+static int enqueue_rows(const Batch* b, uint32_t* d_cnt, uint32_t* d_off, uint32_t* d_tmp, hipStream_t st, const Emit& emit, std::string& err) {
+  const uint32_t n32 = (uint32_t)b->n_input, nq32 = (uint32_t)b->nq;
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, n32 * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
+  exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
+  hipLaunchKernelGGL(k_emit_rows<Emit>, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->soff, b->r_count, b->r_rows, b->q_orig, d_off, emit);
+  return ANX_OK;
+}
+
+// Downloads the ranked rows of the batch into caller-provided storage: out[0 .. n_results), off[0 .. n_input] = base + the CSR
+// offsets (a shard of a multi-device batch writes its slice of the whole call's arrays) and, where via is given, via[0 .. n_results).
+// The device lays the rows out in input order (enqueue_rows with make_emit(d_out, d_via)), so the host only copies: the offsets
+// (u32) and the finished arrays.  Runs on the stream of the batch's last run; every exit frees the temporaries.
+template <typename Row, typename Off, typename MakeEmit>
+static int fetch_rows(const Batch* b, Row* out, Off* off, uint32_t* via, Off base, const MakeEmit& make_emit, std::string& err) {
   if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
   HIP_TRY(hipSetDevice(b->device));
   const size_t n = b->n_input;
-  int rc = ANX_OK;
-  if (b->nq && b->n_results) {
-    // the device lays the rows out in the caller's input order (counts scattered to the original indices, exclusive
-    // scan, row copy), so the host only copies: offsets (u32) and the finished anx_result array.  Runs on the stream of
-    // the batch's last run; every exit frees the temporaries.
-    uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr;
-    anx_result* d_out = nullptr;
-    hipStream_t st = reinterpret_cast<hipStream_t>(b->last_stream);
-    auto body = [&]() -> int {
-      const uint32_t n32 = (uint32_t)n, nq32 = (uint32_t)b->nq;
-      const size_t nblk = (n + SCAN_TILE - 1) / SCAN_TILE + 2;
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), nblk * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_out), b->n_results * sizeof(anx_result)));
-      HIP_TRY(hipMemsetAsync(d_cnt, 0, n * sizeof(uint32_t), st));
-      hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
-      exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
-      hipLaunchKernelGGL(k_fetch_rows, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->soff, b->r_count, b->r_rows, b->q_orig, d_off, d_out);
-      std::vector<uint32_t> h_off(n + 1);
-      HIP_TRY(hipMemcpyAsync(h_off.data(), d_off, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out, d_out, b->n_results * sizeof(anx_result), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      for (size_t i = 0; i <= n; ++i) off[i] = base + h_off[i];
-      return ANX_OK;
-    };
-    rc = body();
-    if (rc) (void)hipStreamSynchronize(st);  // nothing of this call may still be in flight when its blocks return to the pool
-    for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_out}) pool_free(p);
-  } else {
+  if (!b->nq || !b->n_results) {
     for (size_t i = 0; i <= n; ++i) off[i] = base;
+    return ANX_OK;
   }
+  uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr, *d_via = nullptr;
+  Row* d_out = nullptr;
+  hipStream_t st = reinterpret_cast<hipStream_t>(b->last_stream);
+  auto body = [&]() -> int {
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), scan_tmp_bytes(n)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_out), b->n_results * sizeof(Row)));
+    if (via) HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_via), b->n_results * sizeof(uint32_t)));
+    if (const int rc = enqueue_rows(b, d_cnt, d_off, d_tmp, st, make_emit(d_out, d_via), err)) return rc;
+    std::vector<uint32_t> staged;  // u32 offsets land in the caller's array, wider ones are widened from a copy
+    uint32_t* h_off;
+    if constexpr (sizeof(Off) == sizeof(uint32_t)) h_off = off;
+    else { staged.resize(n + 1); h_off = staged.data(); }
+    HIP_TRY(hipMemcpyAsync(h_off, d_off, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out, d_out, b->n_results * sizeof(Row), hipMemcpyDeviceToHost, st));
+    if (via) HIP_TRY(hipMemcpyAsync(via, d_via, b->n_results * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (base || !staged.empty())
+      for (size_t i = 0; i <= n; ++i) off[i] = base + h_off[i];
+    return ANX_OK;
+  };
+  const int rc = body();
+  if (rc) (void)hipStreamSynchronize(st);  // nothing of this call may still be in flight when its blocks return to the pool
+  for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_out, (void*)d_via}) pool_free(p);
   return rc;
+}
+
+int batch_fetch_into(const Batch* b, anx_result* out, size_t* off, size_t base, std::string& err) {
+  return fetch_rows(b, out, off, nullptr, base, [](anx_result* d_out, uint32_t*) { return EmitResult{d_out}; }, err);
 }
 
 // The same rows as 16-byte anx_topk_record {vocab u32, freq f32, dist f64} with u32 offsets: half the bytes over PCIe (config 2:
-// 70 MB instead of 141 MB per million queries).  out[0 .. n_results), off[0 .. n_input] = base + CSR offsets.
-int batch_fetch_compact_into(const Batch* b, anx_topk_record* out, uint32_t* off, uint32_t base, std::string& err) {
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t n = b->n_input;
-  int rc = ANX_OK;
-  if (b->nq && b->n_results) {
-    uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr;
-    anx_topk_record* d_out = nullptr;
-    hipStream_t st = reinterpret_cast<hipStream_t>(b->last_stream);
-    auto body = [&]() -> int {
-      const uint32_t n32 = (uint32_t)n, nq32 = (uint32_t)b->nq;
-      const size_t nblk = (n + SCAN_TILE - 1) / SCAN_TILE + 2;
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), nblk * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_out), b->n_results * sizeof(anx_topk_record)));
-      HIP_TRY(hipMemsetAsync(d_cnt, 0, n * sizeof(uint32_t), st));
-      hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
-      exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
-      hipLaunchKernelGGL(k_export_rows, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->soff, b->r_count, b->r_rows, b->q_orig, d_off, d_out);
-      HIP_TRY(hipMemcpyAsync(off, d_off, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out, d_out, b->n_results * sizeof(anx_topk_record), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (base)
-        for (size_t i = 0; i <= n; ++i) off[i] += base;
-      return ANX_OK;
-    };
-    rc = body();
-    if (rc) (void)hipStreamSynchronize(st);
-    for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_out}) pool_free(p);
-  } else {
-    for (size_t i = 0; i <= n; ++i) off[i] = base;
-  }
-  return rc;
-}
-
-// The same plus via[0 .. n_results): one word per row, 0xFFFFFFFF = none (k_export_rows_via).  plain: the model has no variant
-// lists -- every word is 0xFFFFFFFF, written on the host: the device and PCIe see what batch_fetch_compact_into does.
-int batch_fetch_compact_via_into(const Batch* b, anx_topk_record* out, uint32_t* off, uint32_t* via, uint32_t base, bool plain, std::string& err) {
-  if (plain) {
-    const int rc = batch_fetch_compact_into(b, out, off, base, err);
-    if (rc == ANX_OK && b->n_results) memset(via, 0xFF, (size_t)b->n_results * sizeof(uint32_t));
-    return rc;
-  }
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t n = b->n_input;
-  int rc = ANX_OK;
-  if (b->nq && b->n_results) {
-    uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr, *d_via = nullptr;
-    anx_topk_record* d_out = nullptr;
-    hipStream_t st = reinterpret_cast<hipStream_t>(b->last_stream);
-    auto body = [&]() -> int {
-      const uint32_t n32 = (uint32_t)n, nq32 = (uint32_t)b->nq;
-      const size_t nblk = (n + SCAN_TILE - 1) / SCAN_TILE + 2;
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), nblk * sizeof(uint32_t)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_out), b->n_results * sizeof(anx_topk_record)));
-      HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_via), b->n_results * sizeof(uint32_t)));
-      HIP_TRY(hipMemsetAsync(d_cnt, 0, n * sizeof(uint32_t), st));
-      hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
-      exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
-      hipLaunchKernelGGL(k_export_rows_via, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->soff, b->r_count, b->r_rows, b->q_orig, d_off, d_out, d_via);
-      HIP_TRY(hipMemcpyAsync(off, d_off, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out, d_out, b->n_results * sizeof(anx_topk_record), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(via, d_via, b->n_results * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (base)
-        for (size_t i = 0; i <= n; ++i) off[i] += base;
-      return ANX_OK;
-    };
-    rc = body();
-    if (rc) (void)hipStreamSynchronize(st);
-    for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_out, (void*)d_via}) pool_free(p);
-  } else {
-    for (size_t i = 0; i <= n; ++i) off[i] = base;
-  }
+// 70 MB instead of 141 MB per million queries).  via (may be null): one word per row, 0xFFFFFFFF = none.  plain: the model has no
+// variant lists -- every word is 0xFFFFFFFF, written on the host: the device and PCIe see what the call without via does.
+int batch_fetch_compact_into(const Batch* b, anx_topk_record* out, uint32_t* off, uint32_t* via, uint32_t base, bool plain, std::string& err) {
+  if (via && !plain)
+    return fetch_rows(b, out, off, via, base, [](anx_topk_record* d_out, uint32_t* d_via) { return EmitRecordVia{d_out, d_via}; }, err);
+  const int rc = fetch_rows(b, out, off, nullptr, base, [](anx_topk_record* d_out, uint32_t*) { return EmitRecord{d_out}; }, err);
+  if (rc == ANX_OK && via && b->n_results) memset(via, 0xFF, (size_t)b->n_results * sizeof(uint32_t));
   return rc;
 }
 
@@ -1938,15 +1884,10 @@ int batch_export_compact(const DeviceLexicon* dl, const Batch* b, void* dst, siz
   anx_topk_record* d_rows = reinterpret_cast<anx_topk_record*>(static_cast<char*>(dst) + off_bytes);
   if (n == 0 || b->nq == 0) { HIP_TRY(hipMemsetAsync(d_off, 0, off_bytes, st)); return ANX_OK; }
   if (!b->x_cnt) {
-    const size_t nblk = (n + SCAN_TILE - 1) / SCAN_TILE + 2;
     HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_cnt), n * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_tmp), nblk * sizeof(uint32_t)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_tmp), scan_tmp_bytes(n)));
   }
-  const uint32_t n32 = (uint32_t)n, nq32 = (uint32_t)b->nq;
-  HIP_TRY(hipMemsetAsync(b->x_cnt, 0, n * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, b->x_cnt);
-  exclusive_scan(b->x_cnt, n32, d_off, b->x_tmp, st);
-  hipLaunchKernelGGL(k_export_rows, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->soff, b->r_count, b->r_rows, b->q_orig, d_off, d_rows);
+  if (const int rc = enqueue_rows(b, b->x_cnt, d_off, b->x_tmp, st, EmitRecord{d_rows}, err)) return rc;
   HIP_TRY(hipGetLastError());
   return ANX_OK;
 }

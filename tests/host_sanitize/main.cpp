@@ -13,6 +13,16 @@
 static int checks = 0;
 #define CHECK(c) do { ++checks; if (!(c)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #c, anx_last_error()); return 1; } } while (0)
 
+// compact records with `via` of rows that carry none == the anx_result rows, up to the float32 freq_score of a record
+static bool same_rows_no_via(const anx_topk_record* cr, const uint32_t* via, const anx_result* rows, size_t n) {
+  std::vector<anx_result> view(n + 1);
+  anx_compact_to_results_via(cr, via, n, view.data());
+  for (size_t i = 0; i < n; ++i)
+    if (via[i] != 0xFFFFFFFFu || view[i].vocab_id != rows[i].vocab_id || view[i].dist_score != rows[i].dist_score ||
+        view[i].freq_score != (double)(float)rows[i].freq_score || view[i].via != rows[i].via) return false;
+  return true;
+}
+
 // Multi-replica sharding of the batch calls against the fake devices of stub_engine.cpp (ANX_STUB_FAKE=1): the results of a call
 // must not depend on the number of replicas or on the form the inputs are passed in.
 static int shards_mode(const std::string& alphabet, const std::string& lexicon) {
@@ -162,10 +172,18 @@ static int shards_mode(const std::string& alphabet, const std::string& lexicon) 
           anx_compact_to_results(cr, off[in.size()], view.data());
           for (size_t i = 0; i <= in.size(); ++i) CHECK(co[i] == off[i]);
           CHECK(memcmp(view.data(), rows, off[in.size()] * sizeof(anx_result)) == 0);
+          // the same with `via` (the fake rows carry none): rows and offsets byte-equal, every word 0xFFFFFFFF, and the anx_result
+          // view equal to the fetched rows up to the float32 freq_score
+          anx_topk_record* vr = nullptr; uint32_t* vo = nullptr; uint32_t* vv = nullptr;
+          CHECK(anx_batch_fetch_compact_via(b, &vr, &vo, &vv) == ANX_OK);
+          CHECK(memcmp(vo, co, (in.size() + 1) * sizeof(uint32_t)) == 0 && memcmp(vr, cr, off[in.size()] * sizeof(anx_topk_record)) == 0);
+          CHECK(same_rows_no_via(vr, vv, rows, off[in.size()]));
+          anx_compact_free(vr, vo);
           anx_compact_free(cr, co);
         } else {
-          anx_topk_record* cr = nullptr; uint32_t* co = nullptr;
+          anx_topk_record* cr = nullptr; uint32_t* co = nullptr; uint32_t* cv = nullptr;
           CHECK(anx_batch_fetch_compact(b, &cr, &co) == ANX_EINVAL);
+          CHECK(anx_batch_fetch_compact_via(b, &cr, &co, &cv) == ANX_EINVAL);
         }
         size_t used = 0;
         if (anx_batch_num_shards(b) > 1) CHECK(anx_batch_export_compact(b, &used, 8, nullptr, &used) == ANX_EINVAL);
@@ -189,6 +207,23 @@ static int shards_mode(const std::string& alphabet, const std::string& lexicon) 
           anx_compact_free(cr, co);
           CHECK(anx_pipeline_next(pl, &cr, &co, &cn) == ANX_EINVAL);
           CHECK(anx_pipeline_next(pl, &cr, &co, &cn) == ANX_EINVAL && anx_pipeline_pending(pl) == 0);  // nothing in flight
+          // `via` asked for only after the pipeline has fetched a job without it: the job moves into a block with room for the words
+          // (the pause lets the second job reach the end of the pipeline first; the rows are the same if it has not).  From then on
+          // the fetch stage leaves the room itself.
+          for (int j = 0; j < 2; ++j) CHECK(anx_pipeline_submit_packed(pl, packed.data(), packed.size(), in.size(), &p) == ANX_OK);
+          CHECK(anx_pipeline_next(pl, &cr, &co, &cn) == ANX_OK && cn == in.size());
+          anx_compact_free(cr, co);
+          usleep(200000);
+          CHECK(anx_pipeline_submit_packed(pl, packed.data(), packed.size(), in.size(), &p) == ANX_OK);
+          for (int j = 0; j < 2; ++j) {
+            uint32_t* cv = nullptr;
+            cn = 0;
+            CHECK(anx_pipeline_next_via(pl, &cr, &co, &cv, &cn) == ANX_OK && cn == in.size());
+            samep = true;
+            for (size_t i = 0; i <= in.size() && samep; ++i) samep = co[i] == off[i];
+            CHECK(samep && same_rows_no_via(cr, cv, rows, off[in.size()]));
+            anx_compact_free(cr, co);
+          }
           CHECK(anx_pipeline_submit_packed(pl, packed.data(), packed.size(), in.size(), &p) == ANX_OK);  // left in flight: freed with the pipeline
           anx_pipeline_free(pl);
         }

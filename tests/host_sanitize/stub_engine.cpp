@@ -92,8 +92,9 @@ int batch_fetch_into(const Batch* b, anx_result* rows, size_t* offs, size_t base
   for (size_t i = 0; i < b->off.size(); ++i) offs[i] = base + b->off[i];
   return ANX_OK;
 }
-int batch_fetch_compact_into(const Batch* b, anx_topk_record* rows, uint32_t* offs, uint32_t base, std::string& err) {
+int batch_fetch_compact_into(const Batch* b, anx_topk_record* rows, uint32_t* offs, uint32_t* via, uint32_t base, bool, std::string& err) {
   if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
+  if (via && !b->rows.empty()) memset(via, 0xFF, b->rows.size() * sizeof(uint32_t));  // the fake rows carry ANX_NO_VIA
   for (size_t i = 0; i < b->rows.size(); ++i) rows[i] = anx_topk_record{(uint32_t)b->rows[i].vocab_id, (float)b->rows[i].freq_score, b->rows[i].dist_score};
   for (size_t i = 0; i < b->off.size(); ++i) offs[i] = base + (uint32_t)b->off[i];
   return ANX_OK;
@@ -128,7 +129,7 @@ int batch_gather_compact(const DeviceLexicon* dl, const Batch* b, int, void* dst
   if (!dl || !b || !b->ran) { err = "stub"; return ANX_ENODEVICE; }
   if (capacity < batch_compact_bytes(b)) { err = "gather buffer too small"; return ANX_ELIMIT; }
   const size_t off_bytes = ((b->in.size() + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
-  return batch_fetch_compact_into(b, reinterpret_cast<anx_topk_record*>(static_cast<char*>(dst) + off_bytes), static_cast<uint32_t*>(dst), 0, err);
+  return batch_fetch_compact_into(b, reinterpret_cast<anx_topk_record*>(static_cast<char*>(dst) + off_bytes), static_cast<uint32_t*>(dst), nullptr, 0, true, err);
 }
 // search mode's one-pass path: the fake device hands every part back to the classic path (after the host has built its tables)
 struct OnePassState { int unused; };
