@@ -605,32 +605,46 @@ __global__ __launch_bounds__(256) void k_small_tiles(GatherArgs g, TileArgs t, S
   for (uint32_t part = nparts; part < slots; ++part) t.tiles[(size_t)part * t.nq + s].nq = 0u;  // an unused slot: k_scan_small only looks at nq
 }
 
+// ---- kernel arguments: what both host drivers below fill the same way (buffers and per-path fields stay with them) ------------------------
+static EncArgs enc_args_of(const HostModel& m, const DeviceLexicon* dl, const anx_params& p) {  // the model and lexicon part, thresholds
+  EncArgs ea{};
+  ea.al = dl->alpha; ea.A = m.alphabet.size(); ea.NP = dl->nplanes;
+  ea.bits_ok = (dl->nsym <= 32 && !switches().scan_sad) ? 1 : 0;
+  ea.ngroups = sig_group_count(m.lex.sym_group);
+  ea.kth = p.max_anagram_distance; ea.dth = p.max_edit_distance;
+  return ea;
+}
+static GatherArgs gather_args_of(const DeviceLexicon* dl) {  // the lexicon part
+  GatherArgs ga{};
+  ga.NP = dl->nplanes;
+  ga.sigtab = dl->sig; ga.siglen_begin = dl->alpha.siglen_begin; ga.cls_planes = dl->cls_planes; ga.cstride = dl->cstride;
+  return ga;
+}
+static TileArgs tile_args_of(const DeviceLexicon* dl) {  // where a tile's signatures come from: window, ball probe or adjacency list
+  TileArgs ta{};
+  ta.siglen_begin = dl->alpha.siglen_begin;
+  ta.ball_tab = dl->ball_tab; ta.probe = probe_enabled() ? 1 : 0;
+  ta.adj_hash = dl->adj_hash; ta.adj_mask = switches().scan_adj ? dl->adj_mask : 0u;
+  return ta;
+}
+
 int small_encode_launch(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n, uint32_t qw,
                         const anx_params& p, const SmallZero& z, uint32_t slots, bool stage_lds, const uint32_t* host_off, hipStream_t st, std::string& err) {
-  const int NP = dl->nplanes;
-  EncArgs ea;
-  ea.blob = blob; ea.off = off; ea.n = n; ea.al = dl->alpha; ea.A = m.alphabet.size(); ea.NP = NP;
-  ea.bits_ok = (dl->nsym <= 32 && !switches().scan_sad) ? 1 : 0;
-  ea.ngroups = 1;
-  for (uint8_t g : m.lex.sym_group) ea.ngroups = std::max(ea.ngroups, (int)g + 1);
-  ea.kth = p.max_anagram_distance; ea.dth = p.max_edit_distance;
+  EncArgs ea = enc_args_of(m, dl, p);
+  ea.blob = blob; ea.off = off; ea.n = n;
   ea.codes = e.codes; ea.meta = e.meta; ea.bits = e.bits; ea.sig = e.sig; ea.kind = e.kind; ea.cv = e.cv; ea.key = e.key; ea.blk = e.blk;
-  ea.dbg = 0;
   ea.zero_cv = 1;
   for (uint32_t bk = 0; bk <= 16u; ++bk) ea.stage_off[bk] = host_off ? host_off[std::min<uint32_t>(bk * 256u, n)] : 0u;
   const dim3 gn((n + 255) / 256);
   if (stage_lds && host_off && n <= 4096u) hipLaunchKernelGGL(k_enc_strings<true>, gn, dim3(256), 0, st, ea);
   else hipLaunchKernelGGL(k_enc_strings<false>, gn, dim3(256), 0, st, ea);
-  GatherArgs ga;
-  ga.nq = n; ga.qw = qw; ga.NP = NP; ga.want_exact = 0;
+  GatherArgs ga = gather_args_of(dl);
+  ga.nq = n; ga.qw = qw; ga.want_exact = 0;
   ga.perm = e.perm; ga.off = off; ga.codes = e.codes; ga.meta = e.meta; ga.bits = e.bits; ga.kind = e.kind; ga.cv = e.cv; ga.sig = e.sig;
   ga.q_rec = e.q_rec; ga.q_rows = e.q_rows; ga.q_bits = e.q_bits; ga.q_cv = e.q_cv; ga.q_meta = e.q_meta; ga.q_orig = e.q_orig;
   ga.qexact = e.qexact; ga.s_kind = e.s_kind; ga.s_sig = e.s_sig;
-  ga.sigtab = dl->sig; ga.siglen_begin = dl->alpha.siglen_begin; ga.cls_planes = dl->cls_planes; ga.cstride = dl->cstride;
-  TileArgs ta;
-  ta.tq = 1; ta.nq = n; ta.q_meta = e.q_meta; ta.s_kind = e.s_kind; ta.s_sig = e.s_sig; ta.siglen_begin = dl->alpha.siglen_begin; ta.ctr = nullptr;
-  ta.ball_tab = dl->ball_tab; ta.probe = probe_enabled() ? 1 : 0;
-  ta.adj_hash = dl->adj_hash; ta.adj_mask = switches().scan_adj ? dl->adj_mask : 0u;
+  TileArgs ta = tile_args_of(dl);
+  ta.tq = 1; ta.nq = n; ta.q_meta = e.q_meta; ta.s_kind = e.s_kind; ta.s_sig = e.s_sig; ta.ctr = nullptr;
   ta.head = nullptr; ta.tcount = nullptr; ta.tiles = e.tiles; ta.tkey = nullptr;
   hipLaunchKernelGGL(k_small_tiles, gn, dim3(256), 0, st, ga, ta, z, slots, dl->adj_hdr);
   HIP_TRY(hipGetLastError());
@@ -727,8 +741,8 @@ int batch_encode_device(const HostModel& m, const DeviceLexicon* dl, Batch* b, c
     HIP_TRY(e1);
   }
   HIP_TRY(hipMemcpyAsync(d_blob, blob, blob_len, blob_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-  const int bits_ok = (dl->nsym <= 32 && !switches().scan_sad) ? 1 : 0;
-  if (!bits_ok) HIP_TRY(hipMemsetAsync(d_cv, 0, n * (size_t)NP * 4, st));
+  EncArgs ea = enc_args_of(m, dl, p);
+  if (!ea.bits_ok) HIP_TRY(hipMemsetAsync(d_cv, 0, n * (size_t)NP * 4, st));
   HIP_TRY(hipMemsetAsync(d_ctr, 0, 8 * sizeof(uint32_t), st));
   if (off) {
     HIP_TRY(hipMemcpyAsync(d_off, off, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -748,14 +762,8 @@ int batch_encode_device(const HostModel& m, const DeviceLexicon* dl, Batch* b, c
     HIP_TRY(hipStreamSynchronize(st));
     if (have < n) { err = "packed inputs hold fewer strings than announced"; return ANX_EINVAL; }
   }
-  EncArgs ea;
-  ea.blob = d_blob; ea.off = d_off; ea.n = n32; ea.al = dl->alpha; ea.A = m.alphabet.size(); ea.NP = NP;
-  ea.bits_ok = bits_ok;
-  ea.ngroups = 1;
-  for (uint8_t g : m.lex.sym_group) ea.ngroups = std::max(ea.ngroups, (int)g + 1);
-  ea.kth = p.max_anagram_distance; ea.dth = p.max_edit_distance;
+  ea.blob = d_blob; ea.off = d_off; ea.n = n32;
   ea.codes = d_codes; ea.meta = d_meta; ea.bits = d_bits; ea.sig = d_sig; ea.kind = d_kind; ea.cv = d_cv; ea.key = d_key; ea.blk = d_blk;
-  ea.dbg = 0;
   ea.zero_cv = 0;
 #ifdef ANX_DEBUG_SWITCHES
   { const char* e = getenv("ANX_ENC_DBG"); ea.dbg = e ? atoi(e) : 0; }
@@ -797,21 +805,18 @@ int batch_encode_device(const HostModel& m, const DeviceLexicon* dl, Batch* b, c
     HIP_TRY(hipStreamSynchronize(st));
     return ANX_OK;
   }
-  GatherArgs ga;
-  ga.nq = nq; ga.qw = b->qw; ga.NP = NP; ga.want_exact = p.stop_at_exact_match ? 1 : 0;
+  GatherArgs ga = gather_args_of(dl);
+  ga.nq = nq; ga.qw = b->qw; ga.want_exact = p.stop_at_exact_match ? 1 : 0;
   ga.perm = perm; ga.off = d_off; ga.codes = d_codes; ga.meta = d_meta; ga.bits = d_bits; ga.kind = d_kind; ga.cv = d_cv; ga.sig = d_sig;
   ga.q_rec = b->q_rec; ga.q_rows = b->q_rows; ga.q_bits = b->q_bits; ga.q_cv = b->q_cv; ga.q_meta = b->q_meta; ga.q_orig = b->q_orig;
   ga.qexact = b->qexact; ga.s_kind = s_kind; ga.s_sig = s_sig;
-  ga.sigtab = dl->sig; ga.siglen_begin = dl->alpha.siglen_begin; ga.cls_planes = dl->cls_planes; ga.cstride = dl->cstride;
   const dim3 gq((nq + 255) / 256);
   hipLaunchKernelGGL(k_enc_gather, gq, dim3(256), 0, st, ga);
   lap("k_enc_gather");
   // ---- tiles --------------------------------------------------------------------------------------------------------------
-  TileArgs ta;
-  ta.tq = switches().scan_tq ? (uint32_t)switches().scan_tq : default_scan_tq(ea.ngroups);
-  ta.nq = nq; ta.q_meta = b->q_meta; ta.s_kind = s_kind; ta.s_sig = s_sig; ta.siglen_begin = dl->alpha.siglen_begin; ta.ctr = d_ctr;
-  ta.ball_tab = dl->ball_tab; ta.probe = probe_enabled() ? 1 : 0;
-  ta.adj_hash = dl->adj_hash; ta.adj_mask = switches().scan_adj ? dl->adj_mask : 0u;
+  TileArgs ta = tile_args_of(dl);
+  ta.tq = scan_tq_of(ea.ngroups);
+  ta.nq = nq; ta.q_meta = b->q_meta; ta.s_kind = s_kind; ta.s_sig = s_sig; ta.ctr = d_ctr;
   uint32_t *d_head = nullptr, *d_tcount = nullptr;
   if ((rc = sc.get(&d_head, nq, err)) || (rc = sc.get(&d_tcount, (size_t)nq + 1, err))) return rc;
   ta.head = d_head; ta.tcount = d_tcount; ta.tiles = nullptr; ta.tkey = nullptr;

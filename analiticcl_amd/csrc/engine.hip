@@ -865,9 +865,7 @@ static int encode_host(const HostModel& m, const DeviceLexicon* dl, Batch* b, co
     const int lo = std::max<int>(1, (int)lq - (int)k), hi = std::min<int>(kMaxSymbols, (int)lq + (int)k);
     // aligned to whole 64-signature blocks (the neighbours inside the edge blocks belong to charcounts outside the window)
     const uint32_t s0 = m.lex.siglen_begin[lo] & ~63u, s1 = (m.lex.siglen_begin[hi + 1] + 63u) & ~63u;
-    uint32_t ngroups_ = 1;
-    for (uint8_t g_ : m.lex.sym_group) ngroups_ = std::max<uint32_t>(ngroups_, (uint32_t)g_ + 1u);
-    const uint32_t tq = switches().scan_tq ? (uint32_t)switches().scan_tq : default_scan_tq((int)ngroups_);
+    const uint32_t tq = scan_tq_of(sig_group_count(m.lex.sym_group));
     // The count-vector (SAD) tiles are rare (queries with a symbol more than NBITPLANES times) and run as a launch of
     // their own: a handful of waves whose time is the latency of ONE wave walking the whole signature window.  Their
     // windows are therefore split over several waves (disjoint signature ranges = disjoint classes: same pairs).
@@ -1165,6 +1163,8 @@ bool kernel_timer_read(const char* name, double* total_ms, uint64_t* launches) {
   return true;
 }
 
+#include "launch_plan.hpp"
+
 template <int NP>
 static void launch_scan(ScanArgs A, uint32_t nadj, uint32_t nbits, uint32_t nsad, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   // tiles: [bit-plane tiles with an adjacency list | other bit-plane tiles | SAD kind]
@@ -1227,6 +1227,29 @@ static int ensure_surv(Batch* b, size_t cap, std::string& err) {
   b->surv_cap = cap;
   return ANX_OK;
 }
+// survivor records of the scoring kernels, `need` per region
+static int ensure_surv_records(Batch* b, size_t need, std::string& err) {
+  if (need <= b->surv_region_cap) return ANX_OK;
+  if (b->surv) pool_free(b->surv);
+  b->surv = nullptr;
+  b->surv_region_cap = 0;
+  int rc;
+  if ((rc = dalloc(&b->surv, need * SCAN_REGIONS, err))) return rc;
+  b->surv_region_cap = need;
+  return ANX_OK;
+}
+// the three slot lists (SlotLists, launch_plan.hpp), `need` entries per region each
+static int ensure_slot_lists(Batch* b, size_t need, std::string& err) {
+  if (need <= b->list_cap) return ANX_OK;
+  for (void* p : {(void*)b->list8, (void*)b->listg, (void*)b->listw})
+    if (p) pool_free(p);
+  b->list8 = b->listg = b->listw = nullptr;
+  b->list_cap = 0;
+  int rc;
+  if ((rc = dalloc(&b->list8, need * SCAN_REGIONS, err)) || (rc = dalloc(&b->listg, need * SCAN_REGIONS, err)) || (rc = dalloc(&b->listw, need * SCAN_REGIONS, err))) return rc;
+  b->list_cap = need;
+  return ANX_OK;
+}
 
 // ---- one run of the pipeline = batch_launch (everything enqueued on the stream, NO host round trip in between) + batch_finish
 // (wait for the read-back, check the capacities the launch assumed, statistics).  The launch sizes its grids and buffers from the
@@ -1236,8 +1259,6 @@ static int ensure_surv(Batch* b, size_t cap, std::string& err) {
 // ANX_CAP_DIV=n (tests): the first-run capacity ESTIMATES are divided by n, so that the overflow -> regrow -> repeat path runs
 static size_t cap_div() { return (size_t)switches().cap_div; }
 
-// k_rank<true> for models without variant lists at freq_weight == 0, k_rank<false> otherwise (ra = the RankArgs of the launch)
-#define ANX_RANK_LAUNCH(...) do { if (!ra.any_variants && ra.freq_weight == 0.0f) hipLaunchKernelGGL(k_rank<true>, __VA_ARGS__); else hipLaunchKernelGGL(k_rank<false>, __VA_ARGS__); } while (0)
 // Per-query survivor segments (SurvOut::seg): C = ANX_SURV_SEG survivors per query go from the scoring kernels straight to sseg[q * C ..],
 // where k_rank reads them; only the surplus (a query's survivors beyond C) takes the region lists and k_compact_grouped.  The path of
 // models without variant lists at freq_weight == 0 (k_rank<true>), without early device confusables (they re-weight c_rows before
@@ -1305,52 +1326,54 @@ static void hints_record(const DeviceLexicon* dl, const Batch* b, uint32_t maxfi
   h.valid = true;
 }
 
-static int batch_launch(const HostModel& m, const DeviceLexicon* dl, Batch* b, void* stream, std::string& err) {
-  if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
-  if (b->nq >= (1u << 27) || dl->nentries >= (1u << 26)) { err = "more than 2^27 queries per batch or 2^26 lexicon entries (32-bit record offsets, packed pair records)"; return ANX_ELIMIT; }
-  HIP_TRY(hipSetDevice(dl->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const uint32_t nq = (uint32_t)b->nq;
-  if (b->launched) {  // a run enqueued with anx_batch_run_async and never waited for: its events and read-back buffer are reused
-    HIP_TRY(hipEventSynchronize(b->ev_done));
-    b->launched = false;
-  }
-  b->last_stream = stream;
-  b->ran = false;
-  b->ran_keep_all = b->keep_all_pairs;  // the run that also stores the per-slot outputs the debug fetch of every pair reads
-  b->n_pairs = b->n_results = b->n_surv = 0;
-  b->n_raw = 0;
-  if (nq == 0) { b->ran = true; return ANX_OK; }
-  const int stop = b->params.stop_at_exact_match ? 1 : 0;
+// ---- the stages of batch_launch: each enqueues its part of the run on the stream ------------------------------------------------------
+namespace {
+struct Run {  // one batch_launch: what its stages share
+  const HostModel& m;
+  const DeviceLexicon* dl;
+  Batch* b;
+  hipStream_t st;
+  std::string& err;
+  uint32_t nq;
+  int stop;                               // StopAtExactMatch
+  uint32_t region_cap = 0, fill_cap = 0;  // setup: slots per region of the pair list / of them the scoring grid covers
+  SurvOut so{};                           // score: the survivor lists and segments k_rank reads
+  int setup(), scan(), score(), compact_rank(), readback();
+};
+}  // namespace
+
+// sizes from the previous run of the batch or from the hints of the last batch (first run: estimates), the pair list
+int Run::setup() {
   int rc;
   hints_apply(dl, b);
   if (b->raw_cap == 0 && b->hinted && (rc = ensure_raw(b, (size_t)b->prev_maxfill + (b->prev_maxfill >> 3) + 4096, err))) return rc;
   if (b->raw_cap == 0 && (rc = ensure_raw(b, (nq * (size_t)140 + (size_t)b->ntiles * SCAN_CHUNK) / SCAN_REGIONS / cap_div() + 4096, err)))
     return rc;
-  const uint32_t region_cap = 1u << b->region_shift;
+  region_cap = 1u << b->region_shift;
   // slots per region the scoring grid covers: the previous fill + 1/8 (first run: the whole region; blocks beyond a region's
   // fill return at once)
-  const uint32_t fill_cap = b->prev_maxfill ? (uint32_t)std::min<size_t>(region_cap, (size_t)b->prev_maxfill + (b->prev_maxfill >> 3) + FS_BLK) : region_cap;
+  fill_cap = b->prev_maxfill ? (uint32_t)std::min<size_t>(region_cap, (size_t)b->prev_maxfill + (b->prev_maxfill >> 3) + FS_BLK) : region_cap;
   b->fill_cap_launched = fill_cap;
   HIP_TRY(hipEventRecord(b->ev[0], st));
-  // ---- scan ------------------------------------------------------------------------------------------
+  return ANX_OK;
+}
+
+int Run::scan() {
+  int rc;
   HIP_TRY(hipMemsetAsync(b->counters, 0, CTR_N * sizeof(uint32_t), st));
   HIP_TRY(hipMemsetAsync(b->rctr, 0, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), st));
   if (b->ntiles == 0) { HIP_TRY(hipEventRecord(b->ev_scan0, st)); HIP_TRY(hipEventRecord(b->ev[5], st)); }
   if (b->ntiles) {
-    ScanArgs A;
+    ScanArgs A = scan_args_of(dl);
     A.tiles = b->d_tiles; A.ntiles = b->ntiles; A.q_bits = b->q_bits; A.q_cv = b->q_cv;
-    A.cls_bits = dl->cls_bits; A.cls_planes = dl->cls_planes; A.scan_rec = dl->scan_rec; A.scan_rec34 = dl->scan_rec34; A.pad_rec = dl->nentries; A.cstride = dl->cstride; A.pad_class = dl->nclasses;
-    A.cls_len = dl->cls_len; A.cls_off = dl->cls_off; A.sig = dl->sig; A.sig_e = dl->sig_e; A.sig_cbeg = dl->sig_cbeg; A.sighash = dl->sighash; A.sighash_e = dl->sighash_e; A.hash_mask = dl->hash_mask; A.ball = dl->ball;
-    A.adj_hdr = dl->adj_hdr; A.adj_planes = dl->adj_planes; A.adj_ids = dl->adj_ids;
-    A.chunk = SCAN_CHUNK;
+    A.chunk = SCAN_CHUNK;  // (the small call: 64 / 32)
     A.chunk_fused = switches().scan_chunk_fused ? (uint32_t)switches().scan_chunk_fused : SCAN_CHUNK_FUSED;
 #ifdef ANX_DEBUG_SWITCHES
     { const char* e = getenv("ANX_SCAN_CHUNK"); const int v = e ? atoi(e) : 0; if (v >= 32 && v <= 1024) A.chunk = (uint32_t)v; }
 #endif
     A.raw = b->raw; A.region_cap = region_cap; A.rctr = b->rctr; A.qexact = b->qexact; A.want_exact = stop;
     A.drop_len = (!stop && !b->keep_all_pairs) ? 1 : 0;
-    A.q_rec = b->q_rec; A.e_rec = dl->e_rec;
+    A.q_rec = b->q_rec;
     // the band-match bound where the pair is born (not in the run that materialises every pair for the debug view, and not with
     // StopAtExactMatch, whose dropped pairs are counted by the scoring kernel from the materialised list)
     A.fuse = (switches().fuse_prefilter && switches().prefilter && A.drop_len) ? 1 : 0;
@@ -1365,148 +1388,79 @@ static int batch_launch(const HostModel& m, const DeviceLexicon* dl, Batch* b, v
     { const char* e = getenv("ANX_SCAN_DBG"); A.dbg = e ? atoi(e) : 0; }  // read per run: tools/scan_probe.py switches it between runs
 #endif
     const uint32_t nsad = b->n_sad_tiles, nbits = A.ntiles - nsad, nadj = std::min(b->n_adj_tiles, nbits);
-    switch (dl->nplanes) {
-      case 8: launch_scan<8>(A, nadj, nbits, nsad, st, b->ev_scan0, b->ev[5]); break;
-      case 16: launch_scan<16>(A, nadj, nbits, nsad, st, b->ev_scan0, b->ev[5]); break;
-      case 24: launch_scan<24>(A, nadj, nbits, nsad, st, b->ev_scan0, b->ev[5]); break;
-      case 32: launch_scan<32>(A, nadj, nbits, nsad, st, b->ev_scan0, b->ev[5]); break;
-      default: launch_scan<42>(A, nadj, nbits, nsad, st, b->ev_scan0, b->ev[5]); break;
-    }
+    with_nplanes(dl->nplanes, [&](auto np) { launch_scan<decltype(np)::value>(A, nadj, nbits, nsad, st, b->ev_scan0, b->ev[5]); });
   }
   HIP_TRY(hipMemcpyAsync(b->h_read + HR_RCTR, b->rctr, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipEventRecord(b->ev[1], st));
   b->n_raw = (uint32_t)(SCAN_REGIONS << b->region_shift);  // slot space (regions are sparse)
-  // ---- score -----------------------------------------------------------------------------------------
+  return ANX_OK;
+}
+
+int Run::score() {
+  int rc;
   HIP_TRY(hipMemsetAsync(b->qsurv, 0, nq * sizeof(uint32_t), st));
   HIP_TRY(hipMemsetAsync(b->qmaxfreq, 0, nq * sizeof(uint32_t), st));
   if (dl->any_variants) HIP_TRY(hipMemsetAsync(b->qexpand, 0, nq * sizeof(uint32_t), st));
-  ScoreArgs sa;
-  sa.dbg = 0;
+  ScorePlan plan = score_plan_of(m, dl, b->params.score_threshold, b->qw, b->dmax);
+  ScoreArgs& sa = plan.sa;
 #ifdef ANX_DEBUG_SWITCHES
   { const char* e = getenv("ANX_SCORE_DBG"); sa.dbg = e ? atoi(e) : 0; }
 #endif
-  sa.quot = dl->quot;
   sa.store_pairs = b->keep_all_pairs ? 1 : 0;
   if (sa.store_pairs && (rc = ensure_pair_outputs(b, err))) return rc;
-  sa.w_ld = m.weights.ld; sa.w_lcs = m.weights.lcs; sa.w_prefix = m.weights.prefix; sa.w_suffix = m.weights.suffix;
-  sa.w_case = m.weights.casew;
-  sa.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;  // src/types.rs:69-73
-  sa.score_threshold = b->params.score_threshold;
-  sa.have_freq = m.have_freq ? 1 : 0;
-  sa.any_variants = dl->any_variants;
-  sa.lqp = b->qw * 16;
-  sa.lcp = (dl->max_len + 15) / 16 * 16;
-  const uint32_t d = b->dmax;
-  uint32_t stride = sa.lqp + sa.lcp + (d + 2) * (2 * d + 3);
-  stride = (stride + 3) / 4;
-  if ((stride & 1) == 0) stride++;
-  sa.stride = stride * 4;
-  sa.qw = b->qw;
-  uint32_t threads = 256;
-  while (threads > 64 && (size_t)threads * sa.stride > 64 * 1024) threads >>= 1;
-  if ((size_t)threads * sa.stride > 64 * 1024) { err = "per-lane scoring state exceeds the LDS budget"; return ANX_ELIMIT; }
-  // fused prefilter + register DL (ANX_PREFILTER=0 disables the filter: every length-compatible pair goes to the DL)
-  SurvOut so{nullptr, b->sctr, 0, nullptr, 0};
-  const bool have_long_q = b->qw > 1;
+  if (!plan.fits()) { err = "per-lane scoring state exceeds the LDS budget"; return ANX_ELIMIT; }  // (the small call hands such a call to this path)
+  const int fastD = plan.fastD;
+  // survivor records: region r of the survivor list takes the survivors of region r of the pair list.  Sized from the
+  // previous run (first run: half the slots the grid covers -- ~10 % of the slots survive on config 2); an overflow is
+  // detected by batch_finish and the run repeated with the measured size
+  if ((rc = ensure_surv_records(b, b->prev_surv_fill ? (size_t)b->prev_surv_fill + (b->prev_surv_fill >> 3) + 256 : (size_t)fill_cap / 2 / cap_div() + 256, err))) return rc;
+  so = SurvOut{b->surv, b->sctr, (uint32_t)b->surv_region_cap, nullptr, seg_capacity(dl, b)};
+  so.seg = so.seg_cap ? b->sseg : nullptr;
+  // slot lists for the pairs the fused kernel cannot score inline: strings of 17..32 symbols (8-word kernel) and everything
+  // else (longer strings, d > 3).  Only a batch that can have such pairs allocates and walks them (the small call: fixed buffers, always)
+  const bool need_lists = !fastD || plan.have_long_q || dl->max_len > 16;
+  // without the inline DL (d > 3) every length-compatible pair goes to the general list; else the prefilter passes ~1/3
+  if (need_lists && (rc = ensure_slot_lists(b, b->prev_list_fill ? (size_t)b->prev_list_fill + (b->prev_list_fill >> 3) + 256 : (fastD ? (size_t)fill_cap / 2 : (size_t)fill_cap) / cap_div() + 256, err)))
+    return rc;
+  HIP_TRY(hipMemsetAsync(b->sctr, 0, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(b->lctr, 0, 3 * SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), st));
+  const SlotLists sl = slot_lists_of(b->list8, b->listg, b->listw, b->lctr, (uint32_t)b->list_cap);
+  const PairArgs pa = pair_args_of(dl, b->raw, b->q_meta, b->q_rows, b->q_rec, b->p_score, b->p_meta, b->qmaxfreq, b->qsurv, b->qexpand);
+  FilterArgs fa;
+  fa.region_shift = b->region_shift; fa.rctr = b->rctr; fa.qexact = b->qexact; fa.stop = stop; fa.enable = plan.enable_filter;
+  // pairs with a string of 17..32 symbols go to the 8-word register DL also when no QUERY is that long (the few 17..19-symbol candidates
+  // of a short-query batch): until round 6 those went to the general LDS kernel, whose one round cost 0.05 ms (scoring stage of BASELINE
+  // configs[1] 0.555 -> 0.53 ms; the three slot-list kernels as ONE launch, k_small_lists, on top of that: 0.527, not kept)
+  // (the small call: only when k_small_lists runs, threads == 256)
+  fa.use_nw8 = (plan.have_long_q || fastD > 0) ? 1 : 0; fa.counters = b->counters; fa.stat_ctr = b->sctr; fa.fill_cap = fill_cap; fa.blk = FS_BLK;
+  const dim3 fgrid(((fill_cap + FS_BLK - 1) / FS_BLK) * SCAN_REGIONS);
   {
-    const int enable_filter = switches().prefilter, enable_fast = switches().score_fast;
-    const int fastD = (enable_fast && d >= 1 && d <= 3) ? (int)d : 0;
-    // survivor records: region r of the survivor list takes the survivors of region r of the pair list.  Sized from the
-    // previous run (first run: half the slots the grid covers -- ~10 % of the slots survive on config 2); an overflow is
-    // detected by batch_finish and the run repeated with the measured size
-    {
-      const size_t need = b->prev_surv_fill ? (size_t)b->prev_surv_fill + (b->prev_surv_fill >> 3) + 256 : (size_t)fill_cap / 2 / cap_div() + 256;
-      if (need > b->surv_region_cap) {
-        if (b->surv) pool_free(b->surv);
-        b->surv = nullptr;
-        b->surv_region_cap = 0;
-        if ((rc = dalloc(&b->surv, need * SCAN_REGIONS, err))) return rc;
-        b->surv_region_cap = need;
-      }
-    }
-    so.list = b->surv;
-    so.region_cap = (uint32_t)b->surv_region_cap;
-    so.seg_cap = seg_capacity(dl, b);
-    so.seg = so.seg_cap ? b->sseg : nullptr;
-    // slot lists for the pairs the fused kernel cannot score inline: strings of 17..32 symbols (8-word kernel) and everything
-    // else (longer strings, d > 3)
-    const bool need_lists = !fastD || have_long_q || dl->max_len > 16;
-    if (need_lists) {
-      // without the inline DL (d > 3) every length-compatible pair goes to the general list; else the prefilter passes ~1/3
-      const size_t need = b->prev_list_fill ? (size_t)b->prev_list_fill + (b->prev_list_fill >> 3) + 256 : (fastD ? (size_t)fill_cap / 2 : (size_t)fill_cap) / cap_div() + 256;
-      if (need > b->list_cap) {
-        for (void* p : {(void*)b->list8, (void*)b->listg, (void*)b->listw})
-          if (p) pool_free(p);
-        b->list8 = b->listg = b->listw = nullptr;
-        b->list_cap = 0;
-        if ((rc = dalloc(&b->list8, need * SCAN_REGIONS, err)) || (rc = dalloc(&b->listg, need * SCAN_REGIONS, err)) ||
-            (rc = dalloc(&b->listw, need * SCAN_REGIONS, err))) return rc;
-        b->list_cap = need;
-      }
-    }
-    HIP_TRY(hipMemsetAsync(b->sctr, 0, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), st));
-    HIP_TRY(hipMemsetAsync(b->lctr, 0, 3 * SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), st));
-    const SlotList l8{b->list8, b->lctr, (uint32_t)b->list_cap}, lg{b->listg, b->lctr + SCAN_REGIONS * RC_STRIDE, (uint32_t)b->list_cap},
-                   lw{b->listw, b->lctr + 2 * SCAN_REGIONS * RC_STRIDE, (uint32_t)b->list_cap};
-    const PairArgs pa{b->raw, b->q_meta, b->q_rows, b->q_rec, dl->e_rec, dl->ent_meta, dl->ent_rowoff, dl->rows, dl->ent_freq, dl->ent_var_off,
-                      b->p_score, b->p_meta, b->qmaxfreq, b->qsurv, b->qexpand, dl->e_planes};
-    FilterArgs fa;
-    fa.region_shift = b->region_shift; fa.rctr = b->rctr; fa.qexact = b->qexact; fa.stop = stop; fa.enable = enable_filter;
-    // pairs with a string of 17..32 symbols go to the 8-word register DL also when no QUERY is that long (the few 17..19-symbol candidates
-    // of a short-query batch): until round 6 those went to the general LDS kernel, whose one round cost 0.05 ms (scoring stage of BASELINE
-    // configs[1] 0.555 -> 0.53 ms; the three slot-list kernels as ONE launch, k_small_lists, on top of that: 0.527, not kept)
-    fa.use_nw8 = (have_long_q || fastD > 0) ? 1 : 0; fa.counters = b->counters; fa.stat_ctr = b->sctr; fa.fill_cap = fill_cap; fa.blk = FS_BLK;
-    const dim3 fgrid(((fill_cap + FS_BLK - 1) / FS_BLK) * SCAN_REGIONS);
-    {
-      FsCold* cold = reinterpret_cast<FsCold*>(reinterpret_cast<char*>(b->h_read) + HR_COLD_OFF);  // pinned: a truly asynchronous copy
-      *cold = FsCold{sa, so, l8, lg, lw};
-      if (!b->d_cold && (rc = dalloc(reinterpret_cast<char**>(&b->d_cold), sizeof(FsCold), err))) return rc;
-      HIP_TRY(hipMemcpyAsync(b->d_cold, cold, sizeof(FsCold), hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipEventRecord(b->ev_fs0, st));  // ev_fs0 .. ev_fs1 = k_filter_score alone (anx_batch_stats.ms_filter_score_kernel)
-    // the 8-word prefilter of the wide pairs (a string of 17..32 symbols) runs in k_filter_wide: its state inline costs the fused
-    // kernel 105 instead of 70 VGPRs.  Round 6: for batches with long queries as well (BASELINE configs[2]: 9.68 -> 9.52 ms per pass,
-    // configs[3]'s share: 6.73 -> 6.42 ms per 1 M queries)
-    const bool split_wide = switches().fs_split != 0;
-    // the one-add zero test of the prefilter needs every symbol code (classes, unknown = A + 1) below the masked paddings 0x7E / 0x7F
-    const int enable_b7 = switches().fs_b7;
-    const bool b7 = enable_b7 && m.alphabet.size() + 1 < 0x7E;
-    // symbol planes instead of byte rows for the inline DL and its tail (codes + 1 in six bits)
-    const bool planes = b7 && switches().fs_planes && (int)m.alphabet.size() <= kSymbolPlanesMaxA;
-#define ANX_FS_LAUNCH(DD, WW, BB) hipLaunchKernelGGL((k_filter_score<DD, WW, BB>), fgrid, dim3(256), 0, st, fa, pa, static_cast<const FsCold*>(b->d_cold))
-#define ANX_FS_PICK(WW, BB)                      \
-  do {                                           \
-    if (fastD == 1) ANX_FS_LAUNCH(1, WW, BB);    \
-    else if (fastD == 2) ANX_FS_LAUNCH(2, WW, BB); \
-    else if (fastD == 3) ANX_FS_LAUNCH(3, WW, BB); \
-    else ANX_FS_LAUNCH(0, WW, BB);               \
-  } while (0)
-    if (split_wide) { if (planes) ANX_FS_PICK(false, 2); else if (b7) ANX_FS_PICK(false, 1); else ANX_FS_PICK(false, 0); }
-    else { if (b7) ANX_FS_PICK(true, 1); else ANX_FS_PICK(true, 0); }   // (ANX_FS_SPLIT=0, A/B: byte rows)
-#undef ANX_FS_PICK
-#undef ANX_FS_LAUNCH
-    HIP_TRY(hipEventRecord(b->ev_fs1, st));
-    if (need_lists) {  // the list fills are only known on the device: fixed grids walk the lists in strides
-      const dim3 lgrid(LIST_P * SCAN_REGIONS);
-      if (split_wide && enable_filter) hipLaunchKernelGGL(k_filter_wide, lgrid, dim3(256), 0, st, lw, fa, pa, sa, fastD, l8, lg);
-      if (fastD) {
-        if (fastD == 1) hipLaunchKernelGGL(k_score_fast8<1>, lgrid, dim3(256), 0, st, l8, pa, sa, so);
-        else if (fastD == 2) hipLaunchKernelGGL(k_score_fast8<2>, lgrid, dim3(256), 0, st, l8, pa, sa, so);
-        else hipLaunchKernelGGL(k_score_fast8<3>, lgrid, dim3(256), 0, st, l8, pa, sa, so);
-      }
-      hipLaunchKernelGGL(k_score_pairs, dim3(LIST_P * SCAN_REGIONS), dim3(threads), threads * sa.stride, st,
-                         lg, pa, sa, so);
-    }
+    // k_filter_score's rarely used arguments: uploaded with every run (the small call keeps them on the device until they change)
+    FsCold* cold = reinterpret_cast<FsCold*>(reinterpret_cast<char*>(b->h_read) + HR_COLD_OFF);  // pinned: a truly asynchronous copy
+    *cold = FsCold{sa, so, sl.l8, sl.lg, sl.lw};
+    if (!b->d_cold && (rc = dalloc(reinterpret_cast<char**>(&b->d_cold), sizeof(FsCold), err))) return rc;
+    HIP_TRY(hipMemcpyAsync(b->d_cold, cold, sizeof(FsCold), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipEventRecord(b->ev_fs0, st));  // ev_fs0 .. ev_fs1 = k_filter_score alone (anx_batch_stats.ms_filter_score_kernel)
+  // (split_wide, round 6: for batches with long queries as well -- BASELINE configs[2]: 9.68 -> 9.52 ms per pass, configs[3]'s share:
+  // 6.73 -> 6.42 ms per 1 M queries)
+  launch_filter_score(plan, fgrid, st, fa, pa, static_cast<const FsCold*>(b->d_cold));
+  HIP_TRY(hipEventRecord(b->ev_fs1, st));
+  if (need_lists) {  // the list fills are only known on the device: fixed grids walk the lists in strides
+    const dim3 lgrid(LIST_P * SCAN_REGIONS);
+    if (plan.split_wide && plan.enable_filter) hipLaunchKernelGGL(k_filter_wide, lgrid, dim3(256), 0, st, sl.lw, fa, pa, sa, fastD, sl.l8, sl.lg);
+    if (fastD) launch_score_fast8(fastD, lgrid, st, sl.l8, pa, sa, so);  // (the small call's separate launches: only with long queries)
+    hipLaunchKernelGGL(k_score_pairs, lgrid, dim3(plan.threads), plan.lds_bytes(), st, sl.lg, pa, sa, so);
   }
   HIP_TRY(hipEventRecord(b->ev[2], st));
-  // ---- compact survivors + rank -----------------------------------------------------------------------
-  RankArgs ra;
+  return ANX_OK;
+}
+
+int Run::compact_rank() {
+  int rc;
   // confusables weighted on the device, late mode: k_rank crops without the cutoff, conf.hip re-ranks and cuts off afterwards
-  ra.cutoff_threshold = b->conf_mode == 1 ? 0.0 : b->params.cutoff_threshold;
-  ra.max_matches = b->params.max_matches;
-  ra.freq_weight = b->params.freq_weight;
-  ra.have_freq = m.have_freq ? 1 : 0;
-  ra.any_variants = dl->any_variants;
+  // (the small call takes no confusables: always the caller's cutoff)
+  const RankArgs ra = rank_args_of(m, dl, b->params, b->conf_mode == 1 ? 0.0 : b->params.cutoff_threshold);
   exclusive_scan(b->qsurv, nq, b->soff, b->scan_tmp, st, nullptr, b->qcur);  // + qcur = soff: the cursors of the compaction
   if (dl->any_variants) {
     // variant lists: a survivor expands to several rows; the row buffer and the grid of k_compact come from the survivor
@@ -1528,30 +1482,28 @@ static int batch_launch(const HostModel& m, const DeviceLexicon* dl, Batch* b, v
                          (uint32_t)b->surv_region_cap, ca, b->qcur, dl->ent_rec, dl->ent_var_off, dl->var_target,
                          dl->var_target_freq, dl->var_score, b->c_rows);
     }
-    HIP_TRY(hipEventRecord(b->ev[3], st));
-    if (b->conf_mode == 2 && (rc = conf_launch(m, dl, b, st, true, (uint32_t)std::min<size_t>(b->surv_cap, 0xFFFFFFFFu), err))) return rc;
-    ANX_RANK_LAUNCH( dim3((nq + 4 * RANK_QPW - 1) / (4 * RANK_QPW)), dim3(256), 0, st, nq, b->soff, b->c_rows, b->qmaxfreq,
-                       b->qexpand, ra, b->t_key, b->r_rows, b->r_count, 0xFFFFFFFFu, b->counters + CTR_OVERFLOW, SegRows{nullptr, 0u, nullptr});
-    if (b->conf_mode == 1 && (rc = conf_launch(m, dl, b, st, false, (uint32_t)std::min<size_t>(b->surv_cap, 0xFFFFFFFFu), err))) return rc;
-  } else {
-    // No host round trip between scoring and ranking: the row buffers keep the size of the previous run (first run:
-    // an estimate), the kernels check the total on the device, and batch_finish repeats the run if it did not fit.
-    // With segments the region lists hold only the surplus: row j of it for query q goes to c_rows[soff[q] + j].
-    if (b->surv_cap == 0 && (rc = ensure_surv(b, b->hint_rows ? b->hint_rows : (size_t)nq * 16 / cap_div() + 1024, err))) return rc;
-    const uint32_t row_cap = (uint32_t)std::min<size_t>(b->surv_cap, 0xFFFFFFFFu);
+  } else if (b->surv_cap == 0 && (rc = ensure_surv(b, b->hint_rows ? b->hint_rows : (size_t)nq * 16 / cap_div() + 1024, err))) return rc;
+  const uint32_t row_cap = (uint32_t)std::min<size_t>(b->surv_cap, 0xFFFFFFFFu);
+  // No host round trip between scoring and ranking: the row buffers keep the size of the previous run (first run:
+  // an estimate), the kernels check the total on the device, and batch_finish repeats the run if it did not fit.
+  // With segments the region lists hold only the surplus: row j of it for query q goes to c_rows[soff[q] + j].
+  if (!dl->any_variants)
     hipLaunchKernelGGL(k_compact_grouped, dim3(COMPACT_P * SCAN_REGIONS), dim3(COMPACT_B), 0, st, b->surv, b->sctr,
                        (uint32_t)b->surv_region_cap, m.have_freq ? 1 : 0, b->qcur, dl->ent_rec, b->c_rows, b->soff + nq, row_cap,
                        b->counters + CTR_OVERFLOW);
-    HIP_TRY(hipEventRecord(b->ev[3], st));
-    if (b->conf_mode == 2 && (rc = conf_launch(m, dl, b, st, true, row_cap, err))) return rc;
-    ANX_RANK_LAUNCH( dim3((nq + 4 * RANK_QPW - 1) / (4 * RANK_QPW)), dim3(256), 0, st, nq, b->soff, b->c_rows, b->qmaxfreq,
-                       b->qexpand, ra, b->t_key, b->r_rows, b->r_count, row_cap, b->counters + CTR_OVERFLOW,
-                       SegRows{so.seg, so.seg_cap, dl->ent_rec});
-    if (b->conf_mode == 1 && (rc = conf_launch(m, dl, b, st, false, row_cap, err))) return rc;
-  }
+  HIP_TRY(hipEventRecord(b->ev[3], st));
+  if (b->conf_mode == 2 && (rc = conf_launch(m, dl, b, st, true, row_cap, err))) return rc;
+  // (k_compact's rows were sized from the survivor counts on the host: k_rank has no total to check; and no segments with variant lists)
+  launch_rank(ra, st, nq, b->soff, b->c_rows, b->qmaxfreq, b->qexpand, b->t_key, b->r_rows, b->r_count, dl->any_variants ? 0xFFFFFFFFu : row_cap, b->counters + CTR_OVERFLOW,
+              dl->any_variants ? SegRows{nullptr, 0u, nullptr} : SegRows{so.seg, so.seg_cap, dl->ent_rec});
+  if (b->conf_mode == 1 && (rc = conf_launch(m, dl, b, st, false, row_cap, err))) return rc;
   exclusive_scan(b->r_count, nq, b->r_off, b->scan_tmp, st, b->counters + CTR_MAXROWS);
   HIP_TRY(hipEventRecord(b->ev[4], st));
-  // ---- the read-back of the run --------------------------------------------------------------------------
+  return ANX_OK;
+}
+
+// the fills and totals batch_finish reads, behind everything else of the run
+int Run::readback() {
   HIP_TRY(hipMemcpyAsync(b->h_read + HR_SCTR, b->sctr, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(b->h_read + HR_LCTR, b->lctr, 3 * SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(b->h_read + HR_CTR, b->counters, CTR_N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -1561,6 +1513,26 @@ static int batch_launch(const HostModel& m, const DeviceLexicon* dl, Batch* b, v
   if (b->conf_mode && b->cf_ctr) HIP_TRY(hipMemcpyAsync(b->h_read + HR_CONF, b->cf_ctr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipEventRecord(b->ev_done, st));
   HIP_TRY(hipGetLastError());
+  return ANX_OK;
+}
+
+static int batch_launch(const HostModel& m, const DeviceLexicon* dl, Batch* b, void* stream, std::string& err) {
+  if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
+  if (b->nq >= (1u << 27) || dl->nentries >= (1u << 26)) { err = "more than 2^27 queries per batch or 2^26 lexicon entries (32-bit record offsets, packed pair records)"; return ANX_ELIMIT; }
+  HIP_TRY(hipSetDevice(dl->device));
+  if (b->launched) {  // a run enqueued with anx_batch_run_async and never waited for: its events and read-back buffer are reused
+    HIP_TRY(hipEventSynchronize(b->ev_done));
+    b->launched = false;
+  }
+  b->last_stream = stream;
+  b->ran = false;
+  b->ran_keep_all = b->keep_all_pairs;  // the run that also stores the per-slot outputs the debug fetch of every pair reads
+  b->n_pairs = b->n_results = b->n_surv = 0;
+  b->n_raw = 0;
+  if (b->nq == 0) { b->ran = true; return ANX_OK; }
+  Run r{m, dl, b, reinterpret_cast<hipStream_t>(stream), err, (uint32_t)b->nq, b->params.stop_at_exact_match ? 1 : 0};
+  int rc;
+  if ((rc = r.setup()) || (rc = r.scan()) || (rc = r.score()) || (rc = r.compact_rank()) || (rc = r.readback())) return rc;
   b->launched = true;
   return ANX_OK;
 }

@@ -185,6 +185,8 @@ struct LexiconImage {
 constexpr int kSigGroupsWide = 8;
 constexpr size_t kSigGroupsWideMax = 500000;
 inline uint32_t default_scan_tq(int ngroups) { return ngroups >= 8 ? 32u : 48u; }  // queries per scan tile the encoders cut groups into (ANX_SCAN_TQ overrides)
+inline uint32_t scan_tq_of(int ngroups) { return switches().scan_tq ? (uint32_t)switches().scan_tq : default_scan_tq(ngroups); }
+inline int sig_group_count(const std::vector<uint8_t>& sym_group) { int n = 1; for (uint8_t g : sym_group) n = std::max(n, (int)g + 1); return n; }  // signature groups in use
 constexpr int kSigGroups = 7;  // measured (round 2, hash-probe walk): eng.aspell k=3 d=2, 1 M queries: 6 groups 5.45 k record tests per
                                // query, 37.8 k tiles, 3.33 ms per step; 7: 4.14 k tests, 56.6 k tiles, 3.22 ms; 8: 2.35 k tests,
                                // 96 k tiles, 3.48 ms.  1 M-entry lexicon, 1.25 M queries: 13.5 / 12.2 / 13.8 ms

@@ -1,5 +1,6 @@
 // small_path.hpp -- the small call: find_variants for a handful of inputs at the reference's own granularity
 // Part of the single translation unit engine.hip (included inside namespace anx, after the batch pipeline); gfx950 only.
+// How the chain is launched -- kernel arguments, the scoring plan, every template dispatch -- is launch_plan.hpp, shared with batch_launch.
 //
 // The reference's callers hand find_variants ONE string (/root/reference/src/lib.rs:972) and fan out in batches of 1 000
 // (src/bin/analiticcl.rs:416,445-448; bindings/python/src/lib.rs:704-749).  The batch pipeline above is built for a million queries:
@@ -161,7 +162,14 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   const size_t row_cap = std::min<size_t>(c->row_cap, n * (size_t)SMALL_ROWS_PER_Q + 64);
   anx_result* rows = static_cast<anx_result*>(host_result_alloc(row_cap * sizeof(anx_result)));
   if (!rows) return 1;
-  if (!host_result_is_pinned(rows)) { host_result_free(rows); return 1; }  // (pinning failed: the kernel could not write into it)
+  // Every exit but the successful one gives the block back; once kernels may have been enqueued (`drain`) the stream is waited for first:
+  // a failed launch must not let the block and the context (rel, destroyed after this) return to their pools while a kernel enqueued
+  // before it still writes to them
+  struct RowsGuard {
+    anx_result* rows; hipStream_t st; bool drain;
+    ~RowsGuard() { if (!rows) return; if (drain) (void)hipStreamSynchronize(st); host_result_free(rows); }
+  } guard{rows, st, false};
+  if (!host_result_is_pinned(rows)) return 1;  // (pinning failed: the kernel could not write into it)
   SmallCtl* h_ctl = reinterpret_cast<SmallCtl*>(c->h_out);
   unsigned long long* h_off64 = reinterpret_cast<unsigned long long*>(c->h_out + 64);
   h_ctl->rows = 0xFFFFFFFEu;
@@ -180,127 +188,71 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   // (a list of R rows is cut into min(slots, R / 8) parts: 2-3 for the typical list; every unused slot is still a wave that starts and
   // returns: 1 000 inputs 164 -> 156 us with 8 instead of 32 slots per query)
   const uint32_t slots = n32 <= 128u ? 32u : n32 <= 512u ? 16u : 8u;
+  guard.drain = true;
   int rc = small_encode_launch(m, dl, c->enc, in_blob, in_off, n32, qw, p, z, slots, true, h_off, st, err);
-  if (rc) { host_result_free(rows); return rc; }
+  if (rc) return rc;
   // ---- scan -----------------------------------------------------------------------------------------------------------------------------
   const uint32_t region_cap = 1u << SMALL_SHIFT;
   {
-    ScanArgs A;
+    ScanArgs A = scan_args_of(dl);
     A.tiles = c->enc.tiles; A.ntiles = slots * n32; A.q_bits = c->enc.q_bits; A.q_cv = c->enc.q_cv;
-    A.cls_bits = dl->cls_bits; A.cls_planes = dl->cls_planes; A.scan_rec = dl->scan_rec; A.scan_rec34 = dl->scan_rec34; A.pad_rec = dl->nentries; A.cstride = dl->cstride; A.pad_class = dl->nclasses;
-    A.cls_len = dl->cls_len; A.cls_off = dl->cls_off; A.sig = dl->sig; A.sig_e = dl->sig_e; A.sig_cbeg = dl->sig_cbeg; A.sighash = dl->sighash; A.sighash_e = dl->sighash_e; A.hash_mask = dl->hash_mask; A.ball = dl->ball;
-    A.adj_hdr = dl->adj_hdr; A.adj_planes = dl->adj_planes; A.adj_ids = dl->adj_ids;
     A.chunk = 64; A.chunk_fused = 32;  // (SCAN_CHUNK / SCAN_CHUNK_FUSED of the batch path: 256 / 128 -- a wave here holds a share of ONE query's pairs)
     A.raw = c->raw; A.region_cap = region_cap; A.rctr = c->rctr; A.qexact = c->enc.qexact; A.want_exact = 0; A.drop_len = 1;
-    A.q_rec = c->enc.q_rec; A.e_rec = dl->e_rec;
-
-    A.fuse = (switches().fuse_prefilter && switches().prefilter) ? 1 : 0;
+    A.q_rec = c->enc.q_rec;
+    A.fuse = (switches().fuse_prefilter && switches().prefilter) ? 1 : 0;  // (the batch path: only with drop_len, which is always 1 here)
     A.qpairs = nullptr; A.dbg = 0;
     const dim3 grid((A.ntiles + 3) / 4);
-    switch (dl->nplanes) {
-      case 8: hipLaunchKernelGGL(k_scan_small<8>, grid, dim3(256), 0, st, A); break;
-      case 16: hipLaunchKernelGGL(k_scan_small<16>, grid, dim3(256), 0, st, A); break;
-      case 24: hipLaunchKernelGGL(k_scan_small<24>, grid, dim3(256), 0, st, A); break;
-      case 32: hipLaunchKernelGGL(k_scan_small<32>, grid, dim3(256), 0, st, A); break;
-      default: hipLaunchKernelGGL(k_scan_small<42>, grid, dim3(256), 0, st, A); break;
-    }
+    with_nplanes(dl->nplanes, [&](auto np) { hipLaunchKernelGGL(k_scan_small<decltype(np)::value>, grid, dim3(256), 0, st, A); });
   }
-  // ---- score (the launch logic of batch_launch, fixed capacities) -----------------------------------------------------------------------
-  ScoreArgs sa;
-  sa.dbg = 0;
-  sa.quot = dl->quot;
-  sa.store_pairs = 0;
-  sa.w_ld = m.weights.ld; sa.w_lcs = m.weights.lcs; sa.w_prefix = m.weights.prefix; sa.w_suffix = m.weights.suffix; sa.w_case = m.weights.casew;
-  sa.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;
-  sa.score_threshold = p.score_threshold;
-  sa.have_freq = m.have_freq ? 1 : 0;
-  sa.any_variants = dl->any_variants;  // the scoring kernels count a survivor's EXPANDED rows into qsurv and set qexpand
-  sa.lqp = qw * 16;
-  sa.lcp = (dl->max_len + 15) / 16 * 16;
-  uint32_t stride = sa.lqp + sa.lcp + (d + 2) * (2 * d + 3);
-  stride = (stride + 3) / 4;
-  if ((stride & 1) == 0) stride++;
-  sa.stride = stride * 4;
-  sa.qw = qw;
-  uint32_t threads = 256;
-  while (threads > 64 && (size_t)threads * sa.stride > 64 * 1024) threads >>= 1;
-  if ((size_t)threads * sa.stride > 64 * 1024) { host_result_free(rows); (void)hipStreamSynchronize(st); return 1; }
+  // ---- score: the plan of the batch path (launch_plan.hpp) at fixed capacities ------------------------------------------------------------
+  ScorePlan plan = score_plan_of(m, dl, p.score_threshold, qw, d);
+  plan.sa.dbg = 0; plan.sa.store_pairs = 0;
+  if (!plan.fits()) return 1;  // per-lane scoring state beyond the LDS budget: the batch path reports it (ANX_ELIMIT)
+  const ScoreArgs& sa = plan.sa;
+  const uint32_t threads = plan.threads;
+  const int fastD = plan.fastD;
   const SurvOut so{c->surv, c->sctr, SMALL_SURV_CAP, nullptr, 0u};
-  const bool have_long_q = qw > 1;
-  const int enable_filter = switches().prefilter, enable_fast = switches().score_fast;
-  const int fastD = (enable_fast && d >= 1 && d <= 3) ? (int)d : 0;
-  const SlotList l8{c->list8, c->lctr, SMALL_SURV_CAP}, lg{c->listg, c->lctr + SCAN_REGIONS * RC_STRIDE, SMALL_SURV_CAP}, lw{c->listw, c->lctr + 2 * SCAN_REGIONS * RC_STRIDE, SMALL_SURV_CAP};
-  const PairArgs pa{c->raw, c->enc.q_meta, c->enc.q_rows, c->enc.q_rec, dl->e_rec, dl->ent_meta, dl->ent_rowoff, dl->rows, dl->ent_freq, dl->ent_var_off,
-                    nullptr, nullptr, c->qmaxfreq, c->qsurv, c->qexpand, dl->e_planes};
+  const SlotLists sl = slot_lists_of(c->list8, c->listg, c->listw, c->lctr, SMALL_SURV_CAP);  // (fixed buffers: always present)
+  const PairArgs pa = pair_args_of(dl, c->raw, c->enc.q_meta, c->enc.q_rows, c->enc.q_rec, nullptr, nullptr, c->qmaxfreq, c->qsurv, c->qexpand);
   // slots per region the scoring grid covers: the whole region from a few hundred inputs on, less for the smallest calls (a region filled
   // beyond it hands the call to the batch path, like every other capacity)
   uint32_t fs_cap = 2048;
   while (fs_cap < region_cap && fs_cap < n32 * 12u + 2048u) fs_cap *= 2u;
   FilterArgs fa;
-  fa.region_shift = SMALL_SHIFT; fa.rctr = c->rctr; fa.qexact = c->enc.qexact; fa.stop = 0; fa.enable = enable_filter;
+  fa.region_shift = SMALL_SHIFT; fa.rctr = c->rctr; fa.qexact = c->enc.qexact; fa.stop = 0; fa.enable = plan.enable_filter;
   // pairs with a string of 17..32 symbols go to the 8-word register DL also when no QUERY is that long (the batch path leaves a short-query
   // batch's few long candidates to the general LDS kernel: there its extra launch costs more than it saves; here both run inside k_small_lists and
   // one round of the general kernel is 25 us of a 170 us call)
   const bool use8 = fastD > 0 && threads == 256;
-  fa.use_nw8 = (have_long_q || use8) ? 1 : 0; fa.counters = c->counters; fa.stat_ctr = c->sctr; fa.fill_cap = fs_cap; fa.blk = SMALL_FS_BLK;
+  fa.use_nw8 = (plan.have_long_q || use8) ? 1 : 0; fa.counters = c->counters; fa.stat_ctr = c->sctr; fa.fill_cap = fs_cap; fa.blk = SMALL_FS_BLK;
   {
     // k_filter_score's rarely used arguments live in device memory (FsCold): uploaded again only when they change (another model,
     // other weights / thresholds / row width) -- compared field by field (struct padding is not).  any_variants is part of the key: a
-    // model with variant lists and one without share the context pool of a device
+    // model with variant lists and one without share the context pool of a device.  (The batch path uploads its pinned copy with every run.)
     const double key[12] = {sa.w_ld, sa.w_lcs, sa.w_prefix, sa.w_suffix, sa.w_case, sa.w_sum, sa.score_threshold, (double)sa.have_freq + 2.0 * (double)sa.any_variants, (double)sa.lqp, (double)sa.lcp, (double)sa.stride,
                             (double)sa.qw + 1e3 * (double)(reinterpret_cast<uintptr_t>(sa.quot) & 0xFFFFFFFFu)};
     if (!c->cold_valid || memcmp(key, c->cold_key, sizeof key) != 0) {
       memcpy(c->cold_key, key, sizeof key);
-      c->h_cold_last = FsCold{sa, so, l8, lg, lw};
+      c->h_cold_last = FsCold{sa, so, sl.l8, sl.lg, sl.lw};
       if (hipMemcpyAsync(c->d_cold, &c->h_cold_last, sizeof(FsCold), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        host_result_free(rows);
         err = "small path: argument upload";
         return ANX_ENODEVICE;
       }
       c->cold_valid = true;
     }
   }
-  const dim3 fgrid(((fs_cap + SMALL_FS_BLK - 1) / SMALL_FS_BLK) * SCAN_REGIONS);
-  const bool split_wide = switches().fs_split != 0;
-  const bool b7 = switches().fs_b7 && m.alphabet.size() + 1 < 0x7E;
-  const bool planes = b7 && switches().fs_planes && (int)m.alphabet.size() <= kSymbolPlanesMaxA;
-#define ANX_FS_LAUNCH(DD, WW, BB) hipLaunchKernelGGL((k_filter_score<DD, WW, BB>), fgrid, dim3(256), 0, st, fa, pa, static_cast<const FsCold*>(c->d_cold))
-#define ANX_FS_PICK(WW, BB)                        \
-  do {                                             \
-    if (fastD == 1) ANX_FS_LAUNCH(1, WW, BB);      \
-    else if (fastD == 2) ANX_FS_LAUNCH(2, WW, BB); \
-    else if (fastD == 3) ANX_FS_LAUNCH(3, WW, BB); \
-    else ANX_FS_LAUNCH(0, WW, BB);                 \
-  } while (0)
-  if (split_wide) { if (planes) ANX_FS_PICK(false, 2); else if (b7) ANX_FS_PICK(false, 1); else ANX_FS_PICK(false, 0); }
-  else { if (b7) ANX_FS_PICK(true, 1); else ANX_FS_PICK(true, 0); }
-#undef ANX_FS_PICK
-#undef ANX_FS_LAUNCH
-  if (threads == 256) {  // the slot-list kernels as one launch, a block per region (k_small_lists)
-    SmallListArgs L{lw, l8, lg, (split_wide && enable_filter) ? 1 : 0, (fastD && (have_long_q || use8)) ? 1 : 0, fastD};
-    const dim3 lgrid(SCAN_REGIONS);
-    const size_t dyn = (size_t)threads * sa.stride;
-    if (fastD == 1) hipLaunchKernelGGL(k_small_lists<1>, lgrid, dim3(256), dyn, st, L, fa, pa, sa, so);
-    else if (fastD == 2) hipLaunchKernelGGL(k_small_lists<2>, lgrid, dim3(256), dyn, st, L, fa, pa, sa, so);
-    else if (fastD == 3) hipLaunchKernelGGL(k_small_lists<3>, lgrid, dim3(256), dyn, st, L, fa, pa, sa, so);
-    else hipLaunchKernelGGL(k_small_lists<0>, lgrid, dim3(256), dyn, st, L, fa, pa, sa, so);
-  } else {
+  launch_filter_score(plan, dim3(((fs_cap + SMALL_FS_BLK - 1) / SMALL_FS_BLK) * SCAN_REGIONS), st, fa, pa, static_cast<const FsCold*>(c->d_cold));
+  const int do_wide = (plan.split_wide && plan.enable_filter) ? 1 : 0;
+  if (threads == 256) {  // the slot-list kernels as one launch, a block per region (k_small_lists): k_score_fast8's part also for the long candidates of short queries
+    launch_small_lists(plan, st, SmallListArgs{sl.lw, sl.l8, sl.lg, do_wide, (fastD && (plan.have_long_q || use8)) ? 1 : 0, fastD}, fa, pa, so);
+  } else {  // the per-lane state of k_score_pairs does not fit 256 lanes: the three kernels one by one, SMALL_LIST_BLOCKS blocks per region
     const dim3 lgrid(SMALL_LIST_BLOCKS * SCAN_REGIONS);
-    if (split_wide && enable_filter) hipLaunchKernelGGL(k_filter_wide, lgrid, dim3(256), 0, st, lw, fa, pa, sa, fastD, l8, lg);
-    if (fastD && have_long_q) {
-      if (fastD == 1) hipLaunchKernelGGL(k_score_fast8<1>, lgrid, dim3(256), 0, st, l8, pa, sa, so);
-      else if (fastD == 2) hipLaunchKernelGGL(k_score_fast8<2>, lgrid, dim3(256), 0, st, l8, pa, sa, so);
-      else hipLaunchKernelGGL(k_score_fast8<3>, lgrid, dim3(256), 0, st, l8, pa, sa, so);
-    }
-    hipLaunchKernelGGL(k_score_pairs, lgrid, dim3(threads), threads * sa.stride, st, lg, pa, sa, so);
+    if (do_wide) hipLaunchKernelGGL(k_filter_wide, lgrid, dim3(256), 0, st, sl.lw, fa, pa, sa, fastD, sl.l8, sl.lg);
+    if (fastD && plan.have_long_q) launch_score_fast8(fastD, lgrid, st, sl.l8, pa, sa, so);  // (use_nw8 follows have_long_q alone here; the batch path: whenever fastD)
+    hipLaunchKernelGGL(k_score_pairs, lgrid, dim3(threads), plan.lds_bytes(), st, sl.lg, pa, sa, so);
   }
   // ---- compact + rank + the rows into the caller's block ---------------------------------------------------------------------------------
-  RankArgs ra;
-  ra.cutoff_threshold = p.cutoff_threshold;
-  ra.max_matches = p.max_matches;
-  ra.freq_weight = p.freq_weight;
-  ra.have_freq = m.have_freq ? 1 : 0;
-  ra.any_variants = dl->any_variants;
+  const RankArgs ra = rank_args_of(m, dl, p, p.cutoff_threshold);  // (the caller's cutoff: no device confusables on this path)
   const uint32_t crow_cap = (uint32_t)c->row_cap;
   hipLaunchKernelGGL(k_small_offsets, dim3(1), dim3(SMALL_T), 0, st, c->qsurv, n32, c->soff, c->qcur);
   if (dl->any_variants)  // variant lists: a survivor expands to a row per VariantOf reference (+ itself), within the same fixed capacity
@@ -309,25 +261,25 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   else
     hipLaunchKernelGGL(k_compact_grouped, dim3(SCAN_REGIONS), dim3(COMPACT_B), 0, st, c->surv, c->sctr, SMALL_SURV_CAP, m.have_freq ? 1 : 0, c->qcur, dl->ent_rec, c->c_rows,
                        c->soff + n32, crow_cap, c->counters + CTR_OVERFLOW);
-  ANX_RANK_LAUNCH(dim3((n32 + 4 * RANK_QPW - 1) / (4 * RANK_QPW)), dim3(256), 0, st, n32, c->soff, c->c_rows, c->qmaxfreq, c->qexpand, ra, c->t_key, c->r_rows, c->r_count, crow_cap,
-                  c->counters + CTR_OVERFLOW, SegRows{nullptr, 0u, nullptr});
+  launch_rank(ra, st, n32, c->soff, c->c_rows, c->qmaxfreq, c->qexpand, c->t_key, c->r_rows, c->r_count, crow_cap, c->counters + CTR_OVERFLOW, SegRows{nullptr, 0u, nullptr});
   hipLaunchKernelGGL(k_small_fetch, dim3(n32 > 256u ? SMALL_FETCH_BLOCKS : 1u), dim3(SMALL_T), 0, st, n32, c->soff, c->r_count, c->r_rows, c->rctr, c->sctr, c->lctr, c->counters, h_off64, rows, (uint32_t)row_cap, crow_cap, h_ctl);
+  // one check for the whole chain (the batch path: HIP_TRY per call)
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    host_result_free(rows);
     err = std::string("small path: ") + hipGetErrorString(hipGetLastError());
     return ANX_ENODEVICE;
   }
+  guard.drain = false;  // (nothing in flight any more)
   // ---- did the run fit the fixed capacities? -----------------------------------------------------------------------------------------------
   const SmallCtl ctl = *h_ctl;
   if (ctl.rows > row_cap || ctl.maxfill > fs_cap || ctl.surv_fill > SMALL_SURV_CAP || ctl.list_fill > SMALL_SURV_CAP || ctl.total_surv > crow_cap || ctl.overflow) {
-    host_result_free(rows);
     g_small_overflow.fetch_add(1, std::memory_order_relaxed);
     return 1;  // the batch path sizes its buffers from what it measures
   }
   size_t* offs = static_cast<size_t*>(malloc((n + 1) * sizeof(size_t)));
-  if (!offs) { host_result_free(rows); err = "out of memory"; return ANX_EINVAL; }
+  if (!offs) { err = "out of memory"; return ANX_EINVAL; }
   static_assert(sizeof(size_t) == sizeof(unsigned long long), "offsets are copied as they are");
   memcpy(offs, h_off64, (n + 1) * sizeof(size_t));
+  guard.rows = nullptr;  // the caller's now
   *out_rows = rows;
   *out_offs = offs;
   g_small_taken.fetch_add(1, std::memory_order_relaxed);

@@ -177,3 +177,85 @@ def test_concurrent_small_calls(eng):
         t.join()
     assert not errors, errors
     assert want[0][0] == o.find_variants(sets[0][0], op)
+
+
+# ---- the launch plan the small call shares with the batch pipeline (analiticcl_amd/csrc/launch_plan.hpp) ---------------------------------
+_WIDE_SETS = {}
+
+
+def _wide_reference(eng, d):
+    """300 queries of up to 24 bytes (some rows are two words wide): the small call and the batch path without any switch, once per d."""
+    if d not in _WIDE_SETS:
+        g, _o, words = eng
+        p = A.SearchParameters(max_anagram_distance=3, max_edit_distance=d, max_matches=10)
+        qs = synth.make_queries(words, 300, max_len=24, seed=4242)
+        assert any(len(q.encode("utf-8")) > 16 for q in qs)
+        _WIDE_SETS[d] = (qs, p, call(g, qs, p), via_batch_path(g, qs, p))
+    return _WIDE_SETS[d]
+
+
+@pytest.mark.parametrize("d", [2, 3])
+@pytest.mark.parametrize("switch", ["ANX_FS_SPLIT", "ANX_FS_B7", "ANX_FS_PLANES", "ANX_SCORE_FAST", "ANX_PREFILTER", "ANX_SCAN_FUSE", "ANX_SCAN_ADJ"])
+def test_small_call_under_result_neutral_switches(eng, switch, d):
+    """Every A/B switch of the scoring and scan launches, on the small call: the same rows as without it and as the batch path."""
+    g, _o, _words = eng
+    qs, p, plain, batch = _wide_reference(eng, d)
+    assert plain == batch
+    try:
+        A.set_switch(switch, "0")
+        t0 = small_stats()
+        got = call(g, qs, p)
+        assert sum(small_stats()) == sum(t0) + 1, "the small path did not take the call"
+    finally:
+        A.set_switch(switch, None)
+    assert got == plain
+    assert got == batch
+
+
+@pytest.fixture(scope="module")
+def long_entries(data_dir, tmp_path_factory):
+    """About 2 000 words of 3..12 symbols and three entries of 240 symbols: the lexicon's longest entry sets the per-lane LDS of k_score_pairs."""
+    rng = random.Random(31)
+    letters = "abcdefghijklmnopqrstuvwxyz"
+    short = sorted({"".join(rng.choice(letters[:12]) for _ in range(rng.randrange(3, 13))) for _ in range(2000)})
+    vocab = short + ["".join(rng.choice(letters) for _ in range(240)) for _ in range(3)]
+    lex = tmp_path_factory.mktemp("longlex") / "long.lexicon"
+    lex.write_text("".join(f"{w}\n" for w in vocab), encoding="utf-8")
+    alpha = os.path.join(data_dir, "simple.alphabet.tsv")
+    g = A.VariantModel(alpha, A.Weights(), device=0)
+    g.read_lexicon(str(lex))
+    g.build()
+    o = O.OracleModel(alphabet_path=alpha)
+    o.read_lexicon(str(lex))
+    o.build()
+    return g, o, short
+
+
+@pytest.mark.parametrize("k,d,long_queries", [(3, 2, False), (3, 2, True), (5, 4, True)])
+def test_fewer_than_256_scoring_threads(long_entries, k, d, long_queries):
+    """k_score_pairs keeps, per lane, the query row, the candidate row and the DL rows in LDS:
+        16 * qw + 16 * ceil(max_len / 16) + (d + 2) * (2 * d + 3) bytes, rounded up to an odd number of dwords.
+    With a lexicon entry of 240 symbols:
+        d = 2, qw = 1: 16 + 240 + 4 * 7  = 284 B = 71 dwords (odd)        -> 284 B per lane, 256 lanes = 72 704 B > 64 KB, 128 lanes = 36 352 B
+        d = 4, qw = 2: 32 + 240 + 6 * 11 = 338 B -> 85 dwords (odd) = 340 B per lane, 256 lanes = 87 040 B > 64 KB, 128 lanes = 43 520 B
+    so the plan falls to 128 threads: the small call launches k_filter_wide / k_score_fast8 / k_score_pairs one by one instead of
+    k_small_lists, and the batch path launches k_score_pairs with 128 threads.  The three cases: d = 2 with every query <= 16 bytes
+    (no k_score_fast8), d = 2 with a few queries of 17..24 bytes (with k_score_fast8), d = 4 with such queries (no inline DL: fastD = 0)."""
+    g, o, short = long_entries
+    p = A.SearchParameters(max_anagram_distance=k, max_edit_distance=d, max_matches=10)
+    op = O.make_params(("abs", k), ("abs", d), 10, 0.25, 2.0)
+    qs = synth.make_queries(short, 200, max_len=12, seed=60 + d)
+    assert max(len(q) for q in qs) <= 16
+    if long_queries:  # two short words in a row, cut to 17..24 bytes
+        rng = random.Random(d)
+        for i in range(0, 200, 25):
+            w = rng.choice(short) + rng.choice(short) + rng.choice(short) + rng.choice(short)
+            qs[i] = (w + w)[:rng.randrange(17, 25)]
+        assert sum(1 for q in qs if 17 <= len(q) <= 24) == 8
+    t0 = small_stats()
+    got = call(g, qs, p)
+    assert sum(small_stats()) == sum(t0) + 1, "the small path did not take the call"
+    assert got == via_batch_path(g, qs, p)
+    for q, r in zip(qs, got):
+        assert r == o.find_variants(q, op), q
+    assert sum(len(r) for r in got) > 0
