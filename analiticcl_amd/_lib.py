@@ -182,6 +182,7 @@ def lib():
         "anx_debug_learn_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
         "anx_debug_learn_times": (C.c_int, [C.POINTER(C.c_double)]),
         "anx_debug_small_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+        "anx_debug_small_conf_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
         "anx_batch_run": (C.c_int, [vp, vp, vp]),
         "anx_batch_run_async": (C.c_int, [vp, vp, vp]),
         "anx_batch_wait": (C.c_int, [vp, vp]),

@@ -1610,13 +1610,13 @@ int anx_find_variants_batch(const anx_model* m, const char* const* utf8, size_t 
   // consecutive rounds of ANX_MAX_BATCH inputs per replica and their CSR results concatenated.
   const size_t per_round = (size_t)anx::switches().max_batch * std::max<size_t>(1, m ? m->replicas.size() : 1);
   // the small call (engine small_path.hpp): the reference's own granularity -- one string per call, 1 000 per batch
-  // (src/lib.rs:972, src/bin/analiticcl.rs:416) -- in eleven launches and one host wait instead of the batch pipeline
+  // (src/lib.rs:972, src/bin/analiticcl.rs:416) -- in nine launches and one host wait instead of the batch pipeline.  A model with
+  // confusables is taken when they are weighted on the device (thirteen launches): small_find gets the caller's own parameters then, as
+  // anx_batch_encode's dev_conf batches do, and derives late / early from the model; host-side weighting stays with the batch path
   if (m && utf8 && p && n >= 1 && n <= 4096 && m->host.built && m->replicas.size() == 1 && m->replicas[0].dev && anx::switches().small_path) {
-    bool rescore = false;
-    const anx_params dp = device_params(m, p, &rescore);
-    if (!rescore) {   // (confusables: weighted by the batch path)
+    if (m->host.confusables.empty() || !anx::switches().confusables_host) {
       std::string err;
-      const int rc = anx::small_find(m->host, m->replicas[0].dev, utf8, n, dp, out_rows, out_offsets, err);
+      const int rc = anx::small_find(m->host, m->replicas[0].dev, utf8, n, *p, out_rows, out_offsets, err);
       if (rc == ANX_OK) return ANX_OK;
       if (rc < 0) return fail(rc, err);
     }

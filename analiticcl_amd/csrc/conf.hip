@@ -223,11 +223,9 @@ __global__ void k_conf_iota(uint32_t* p, uint32_t n) {
 // all (the clean-up passes walk the diff list).  Sorting the list by that key puts rows of one route side by side in the waves.
 // Only an ordering hint: computed on the input's BYTES against the candidate's code points, it stops at the first non-ASCII
 // character, and nothing but the order in which rows are processed depends on it.
-__global__ __launch_bounds__(256) void k_conf_key(ConfArgs a) {
-  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= a.row_cap) return;
-  uint32_t key = 0x1FFFu;  // behind the list: sorts last
-  if (k < a.ctr[0]) {
+__device__ inline uint32_t conf_shape_key(const ConfArgs& a, uint32_t k) {  // of list entry k < ctr[0]: 13 bits
+  uint32_t key;
+  {
     const uint32_t slot = a.need[k].x, s = a.need[k].y, id = row_item(a, slot);
     const uint32_t i = a.q_orig[s], t0 = a.textoff[i], nin = a.textoff[i + 1] - 1u - t0;
     const uint32_t c0 = a.v_off[id], ncand = a.v_off[id + 1] - c0;
@@ -248,8 +246,61 @@ __global__ __launch_bounds__(256) void k_conf_key(ConfArgs a) {
     key = ((ma < 6u ? ma : 6u) << 5) | ((mb < 6u ? mb : 6u) << 2) | (p ? 2u : 0u) | (sfx ? 1u : 0u);  // < 0xFF
     key = key << 5 | (nin < 31u ? nin : 31u);  // then by length: the loops of a route run as long as the strings
   }
-  a.key[k] = key;
+  return key;
 }
+__global__ __launch_bounds__(256) void k_conf_key(ConfArgs a) {
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.row_cap) return;
+  a.key[k] = k < a.ctr[0] ? conf_shape_key(a, k) : 0x1FFFu;  // behind the list: sorts last
+}
+
+// The small call's ordering of the list: k_conf_key + k_conf_iota + the device radix sort as ONE single-block launch, a counting sort
+// in LDS.  The list length is only known here (ctr[0]): the block strides over it.  Pass 1: the shape key of every entry (kept in
+// a.key: the strings are walked once) and a histogram of the 8192 keys (32 KB of LDS); then an exclusive scan of the bins, eight
+// consecutive bins per thread; pass 2: every entry takes the next position of its bin.  Entries of equal key land in the order their
+// atomics are served -- the order is a hint for the divergence of k_conf_script's waves and nothing else -- but every position
+// 0 .. ctr[0] - 1 is written exactly once (a bin's positions are its count, handed out one by one): a permutation.
+constexpr uint32_t CF_KEYS = 1u << 13, CF_ORDER_T = 1024;
+__global__ __launch_bounds__(CF_ORDER_T) void k_small_conf_order(ConfArgs a, uint32_t* __restrict__ order) {
+  __shared__ uint32_t s_bin[CF_KEYS];
+  __shared__ uint32_t s_w[CF_ORDER_T / 64];
+  static_assert(CF_KEYS == 8u * CF_ORDER_T, "eight bins per thread");
+  const uint32_t n = min(a.ctr[0], a.row_cap);  // (the list never outgrows the rows; the host discards a run that reports otherwise)
+  if (n == 0) return;  // (uniform)
+  for (uint32_t x = threadIdx.x; x < CF_KEYS; x += CF_ORDER_T) s_bin[x] = 0u;
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < n; k += CF_ORDER_T) {
+    const uint32_t key = conf_shape_key(a, k) & (CF_KEYS - 1u);
+    a.key[k] = key;
+    atomicAdd(&s_bin[key], 1u);
+  }
+  __syncthreads();
+  uint32_t v[8], sum = 0;
+#pragma unroll
+  for (uint32_t x = 0; x < 8u; ++x) { v[x] = s_bin[threadIdx.x * 8u + x]; sum += v[x]; }
+  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+  uint32_t inc = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t up = (uint32_t)__shfl_up((int)inc, o);
+    if ((int)lane >= o) inc += up;
+  }
+  if (lane == 63u) s_w[wid] = inc;
+  __syncthreads();
+  uint32_t base = inc - sum;
+  for (uint32_t w = 0; w < wid; ++w) base += s_w[w];
+#pragma unroll
+  for (uint32_t x = 0; x < 8u; ++x) { s_bin[threadIdx.x * 8u + x] = base; base += v[x]; }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < n; k += CF_ORDER_T) order[atomicAdd(&s_bin[a.key[k]], 1u)] = k;
+}
+#ifdef ANX_DEBUG_SWITCHES
+// ANX_SMALL_CONF_ORDER=identity (timing A/B of k_small_conf_order, tools/small_conf_bench.py): the list in the order k_conf_screen left it
+__global__ __launch_bounds__(CF_ORDER_T) void k_small_conf_identity(ConfArgs a, uint32_t* __restrict__ order) {
+  const uint32_t n = min(a.ctr[0], a.row_cap);
+  for (uint32_t k = threadIdx.x; k < n; k += CF_ORDER_T) order[k] = k;
+}
+#endif
 
 __global__ __launch_bounds__(CF_THREADS) void k_conf_script(ConfArgs a) {
   const uint32_t n = a.ctr[0];
@@ -462,6 +513,40 @@ int conf_launch(const HostModel& m, const DeviceLexicon* dl, Batch* b, hipStream
   ktimer_end(kt, st);
   if (early) { if (nblk) hipLaunchKernelGGL(k_conf_apply_early, dim3(nblk), dim3(256), 0, st, a); }
   else hipLaunchKernelGGL(k_conf_apply_late, dim3((nq + 255u) / 256u), dim3(256), 0, st, a, b->r_count);
+  HIP_TRY(hipGetLastError());
+  return ANX_OK;
+}
+
+// ---- the small call -------------------------------------------------------------------------------------------------------------
+size_t conf_small_work_bytes(uint32_t blocks) { return (size_t)blocks * CF_WORDS * 64u * sizeof(uint32_t); }
+
+// conf_launch for small_find: the same kernels on the context's fixed buffers.  conf_ensure's uploads are synchronous, but happen only
+// on the first call after the model's patterns or vocabulary changed.  cb.ctr was cleared by k_small_tiles earlier on `st`.
+int conf_launch_small(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, const SmallConf& cb, const SmallConfRun& r, uint32_t* r_count, std::string& err) {
+  const int rc = conf_ensure(m, dl, err);
+  if (rc) return rc;
+  const DeviceConf* dc = dl->dconf;
+  ConfArgs a;
+  a.nq = r.nq; a.row_cap = r.row_cap; a.early = r.early ? 1 : 0; a.soff = r.soff; a.r_count = r.r_count; a.c_rows = r.c_rows; a.r_rows = r.r_rows;
+  a.overflow = r.overflow;
+  a.q_orig = r.q_orig; a.text = r.text; a.textoff = r.textoff; a.weight = cb.weight; a.need = cb.need; a.ctr = cb.ctr;
+  a.P.conf = dc->conf; a.P.nconf = dc->nconf; a.P.ops = dc->ops; a.P.opts = dc->opts; a.P.pool = dc->pool;
+  a.v_pool = dc->v_pool; a.v_off = dc->v_off; a.v_cs = dc->v_cs; a.nvocab = dc->nvocab;
+  a.alpha = dc->alpha; a.nalpha = dc->nalpha; a.work = cb.work;
+  a.key = cb.key; a.order = cb.order;
+  a.cutoff_threshold = r.cutoff_threshold; a.freq_weight = r.freq_weight;
+  hipLaunchKernelGGL(k_conf_screen, dim3((r.nq + 255u) / 256u), dim3(256), 0, st, a);
+#ifdef ANX_DEBUG_SWITCHES
+  static const bool identity = [] { const char* e = getenv("ANX_SMALL_CONF_ORDER"); return e && strcmp(e, "identity") == 0; }();
+  if (identity) hipLaunchKernelGGL(k_small_conf_identity, dim3(1), dim3(CF_ORDER_T), 0, st, a, cb.order);
+  else
+#endif
+  hipLaunchKernelGGL(k_small_conf_order, dim3(1), dim3(CF_ORDER_T), 0, st, a, cb.order);
+  // one wave per 64 rows the call can hold, at most the blocks the context's working set was sized for (the kernel strides)
+  const uint32_t blocks = std::min<uint32_t>(cb.work_blocks, std::max<uint32_t>(1u, (r.row_cap + 63u) / 64u));
+  hipLaunchKernelGGL(k_conf_script, dim3(blocks), dim3(CF_THREADS), 0, st, a);
+  if (r.early) hipLaunchKernelGGL(k_conf_apply_early, dim3((r.row_cap + 255u) / 256u), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_conf_apply_late, dim3((r.nq + 255u) / 256u), dim3(256), 0, st, a, r_count);
   HIP_TRY(hipGetLastError());
   return ANX_OK;
 }

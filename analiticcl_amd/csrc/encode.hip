@@ -62,6 +62,8 @@ struct EncArgs {
   int dbg;                  // ANX_ENC_DBG (debug builds, timing only, results WRONG): 1 no count-vector writes, 2 no code stores, 4 no walk, 8 no record stores
   int zero_cv;              // !bits_ok: every lane clears its own count-vector row first (the small path: no memset launch before the kernel)
   uint32_t stage_off[17];   // k_enc_strings<true> (<= 4096 strings): off[256 b] for every block b and off[n]: the block's byte range without a read of the (host) offsets
+  uint8_t* keep_text;       // k_enc_strings<true>: the staged bytes and the offsets also go to these device buffers (the small call's confusable
+  uint32_t* keep_off;       // weighting reads them there); nullptr: not kept
 };
 
 // Where the codes of string i start: the bytes of string i and its separator are >= symbols + 1, and rounding every start up to a
@@ -124,7 +126,16 @@ __global__ __launch_bounds__(256) void k_enc_strings(EncArgs a) {
   const uint32_t off_i = i < a.n ? a.off[i] : 0u, off_i1 = i < a.n ? a.off[i + 1] : 1u;
   if (STAGE) {
     const uint32_t b0 = a.stage_off[blockIdx.x] & ~15u, b1 = a.stage_off[blockIdx.x + 1u] + 16u;   // (the window of the last string may read 16 bytes past it)
-    for (uint32_t x = threadIdx.x; x < (b1 - b0 + 15u) / 16u; x += 256u) s_stage[x] = reinterpret_cast<const uint4*>(a.blob + b0)[x];
+    for (uint32_t x = threadIdx.x; x < (b1 - b0 + 15u) / 16u; x += 256u) {
+      const uint4 v = reinterpret_cast<const uint4*>(a.blob + b0)[x];
+      s_stage[x] = v;
+      // (neighbouring blocks' ranges overlap by the 16-byte rounding: both write the same bytes)
+      if (a.keep_text) reinterpret_cast<uint4*>(a.keep_text + b0)[x] = v;
+    }
+    if (a.keep_off && i < a.n) {
+      a.keep_off[i] = off_i;
+      if (i + 1u == a.n) a.keep_off[a.n] = off_i1;
+    }
     stage0 = b0;
     __syncthreads();
   }
@@ -636,7 +647,10 @@ int small_encode_launch(const HostModel& m, const DeviceLexicon* dl, const Small
   ea.zero_cv = 1;
   for (uint32_t bk = 0; bk <= 16u; ++bk) ea.stage_off[bk] = host_off ? host_off[std::min<uint32_t>(bk * 256u, n)] : 0u;
   const dim3 gn((n + 255) / 256);
-  if (stage_lds && host_off && n <= 4096u) hipLaunchKernelGGL(k_enc_strings<true>, gn, dim3(256), 0, st, ea);
+  const bool stage = stage_lds && host_off && n <= 4096u;
+  if (e.text && !stage) { err = "small path: the inputs' text is kept by the staging encoder only"; return ANX_EINVAL; }
+  ea.keep_text = e.text; ea.keep_off = e.text ? e.textoff : nullptr;
+  if (stage) hipLaunchKernelGGL(k_enc_strings<true>, gn, dim3(256), 0, st, ea);
   else hipLaunchKernelGGL(k_enc_strings<false>, gn, dim3(256), 0, st, ea);
   GatherArgs ga = gather_args_of(dl);
   ga.nq = n; ga.qw = qw; ga.want_exact = 0;

@@ -60,10 +60,12 @@ int batch_wait(const HostModel& m, const DeviceLexicon* dl, Batch* b, std::strin
 void batch_set_last_stream(Batch* b, void* stream);  // where the fetches / exports of a FINISHED run are enqueued from now on
 int batch_fetch(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_result** rows, size_t** offs,
                 std::string& err);
-// The small call (small_path.hpp): find_variants for at most 4096 inputs of at most 64 bytes in eleven launches and one host wait,
+// The small call (small_path.hpp): find_variants for at most 4096 inputs of at most 64 bytes in nine launches and one host wait,
 // no allocation.  0: done (*rows: a block of the pinned result cache, *offs: malloc'd, as batch_fetch returns them); 1: not taken
-// (too many / too long inputs, StopAtExactMatch, a fixed capacity exceeded): use the batch path; negative: device error.
-// Models with variant lists are taken too (k_compact_expand expands the survivors within the fixed row capacity).
+// (too many / too long inputs, StopAtExactMatch, host-side confusable weighting, a fixed capacity exceeded): use the batch path;
+// negative: device error.  Models with variant lists are taken too (k_compact_expand expands the survivors within the fixed row
+// capacity), and models with confusables: `p` is the caller's own parameter set, late / early weighting follows from the model
+// (four launches more, conf_launch_small; a row the device cannot weight hands the call over like a capacity).
 int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* utf8, size_t n, const anx_params& p, anx_result** rows, size_t** offs, std::string& err);
 void small_stats(uint64_t* out);  // out[0] = calls the small path answered, out[1] = calls it handed to the batch path after a capacity overflow
 size_t batch_n_results(const Batch* b);

@@ -32,6 +32,33 @@ void encoder_stream_release(int device, hipStream_t s);
 struct DeviceConf;
 void conf_free(DeviceConf*);
 int conf_launch(const HostModel& m, const DeviceLexicon* dl, Batch* b, hipStream_t st, bool early, uint32_t row_cap, std::string& err);
+// The same chain for the small call (small_path.hpp): the context's fixed buffers instead of a Batch's, so no allocation, no memset
+// command (ctr is among the words k_small_tiles clears) and no sort library -- k_small_conf_order, one block, stands in for
+// k_conf_key + k_conf_iota + the radix sort.  Four launches: screen, order, script, apply.
+struct SurvRow;
+struct DevRow;
+struct SmallConf {
+  double* weight = nullptr;        // [row_cap] per row slot
+  uint2* need = nullptr;           // [row_cap] (row slot, query) that need an edit script: never more than there are rows
+  uint32_t* key = nullptr;         // [row_cap] shape key per list entry
+  uint32_t* order = nullptr;       // [row_cap] list positions by shape key
+  uint32_t* ctr = nullptr;         // [8]: [0] list length, [1] rows the device could not weight
+  uint32_t* work = nullptr;        // k_conf_script's working set for work_blocks one-wave blocks
+  uint32_t work_blocks = 0;
+};
+struct SmallConfRun {
+  uint32_t nq, row_cap;
+  bool early;
+  const uint32_t *soff, *r_count, *overflow, *q_orig;
+  const uint8_t* text;             // the inputs on the device (SmallEnc::text / textoff)
+  const uint32_t* textoff;
+  SurvRow* c_rows;
+  DevRow* r_rows;
+  double cutoff_threshold;
+  float freq_weight;
+};
+size_t conf_small_work_bytes(uint32_t blocks);
+int conf_launch_small(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, const SmallConf& cb, const SmallConfRun& r, uint32_t* r_count, std::string& err);
 // the signature adjacency lists built on the device (adjacency.hip); host copies of its table and headers for the host encoder
 int adjacency_build_device(DeviceLexicon* d, const LexiconImage& img, int closure, size_t budget_bytes, AdjIndex& stats, std::string& err);
 int adjacency_host_copies(const DeviceLexicon* d, std::string& err);
@@ -52,6 +79,10 @@ struct SmallEnc {
   uint32_t *q_bits = nullptr, *q_cv = nullptr, *q_meta = nullptr, *q_orig = nullptr, *qexact = nullptr, *s_kind = nullptr;
   unsigned long long* s_sig = nullptr;
   Tile* tiles = nullptr;  // [slots * inputs] (8 * SMALL_MAX in all): slot of (query s, part) = part * n + s
+  // confusable models: k_enc_strings<true> leaves the bytes it staged in LDS, and the offsets, on the device (conf.hip reads them: no copy
+  // command, no byte-wise walk of pinned host memory).  Input i = text[textoff[i] .. textoff[i + 1] - 1).  nullptr: not kept
+  uint8_t* text = nullptr;
+  uint32_t* textoff = nullptr;
 };
 struct SmallZero { uint32_t* p[8]; uint32_t n[8]; };  // arrays k_small_tiles clears before the run (unused entries: n = 0)
 // k_enc_strings -> k_enc_gather (identity order) -> k_small_tiles on `st`: no allocation, no host wait.  blob / off may be pinned host

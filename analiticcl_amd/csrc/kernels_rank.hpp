@@ -809,11 +809,12 @@ __global__ __launch_bounds__(SMALL_T) void k_small_offsets(const uint32_t* __res
 }
 // The ranked rows straight into the caller's (pinned, device-visible) result block, in input order: off[n + 1] (u64) and the
 // anx_result rows; behind them the counters the host checks the run's capacities with.  ctl[0] = rows written (0xFFFFFFFF: they
-// did not fit row_cap), ctl[1 ..]: largest pair-list / survivor / slot-list fill, candidate rows, the overflow flag.
-struct SmallCtl { uint32_t rows, maxfill, surv_fill, list_fill, total_surv, overflow, pad0, pad1; };
+// did not fit row_cap), ctl[1 ..]: largest pair-list / survivor / slot-list fill, candidate rows, the overflow flag; with confusables
+// (cf_ctr of conf.hip, else nullptr) the edit scripts run and the rows the device could not weight.
+struct SmallCtl { uint32_t rows, maxfill, surv_fill, list_fill, total_surv, overflow, conf_scripts, conf_unweightable; };
 __global__ __launch_bounds__(SMALL_T) void k_small_fetch(uint32_t n, const uint32_t* __restrict__ soff, const uint32_t* __restrict__ r_count, const DevRow* __restrict__ r_rows,
                                                          const uint32_t* __restrict__ rctr, const uint32_t* __restrict__ sctr, const uint32_t* __restrict__ lctr,
-                                                         const uint32_t* __restrict__ counters, unsigned long long* __restrict__ off, anx_result* __restrict__ out, uint32_t row_cap,
+                                                         const uint32_t* __restrict__ counters, const uint32_t* __restrict__ cf_ctr, unsigned long long* __restrict__ off, anx_result* __restrict__ out, uint32_t row_cap,
                                                          uint32_t crow_cap, SmallCtl* __restrict__ ctl) {
   __shared__ uint32_t s_w[SMALL_T / 64];
   __shared__ uint32_t s_max[3];
@@ -869,7 +870,8 @@ __global__ __launch_bounds__(SMALL_T) void k_small_fetch(uint32_t n, const uint3
     SmallCtl c;
     c.rows = (fits && ranked) ? tot : 0xFFFFFFFFu;
     c.maxfill = s_max[0]; c.surv_fill = s_max[1]; c.list_fill = s_max[2];
-    c.total_surv = soff[n]; c.overflow = counters[CTR_OVERFLOW]; c.pad0 = c.pad1 = 0u;
+    c.total_surv = soff[n]; c.overflow = counters[CTR_OVERFLOW];
+    c.conf_scripts = cf_ctr ? cf_ctr[0] : 0u; c.conf_unweightable = cf_ctr ? cf_ctr[1] : 0u;
     *ctl = c;
   }
 }

@@ -19,6 +19,12 @@
 //     itself unless TRANSPARENT) and k_rank<false>; the launch count and the one host wait stay.  The expanded rows meet the same fixed
 //     capacities: an entry with many references first fills the caller's block of ranked rows (16 n + 64 rows: what survives dedup and crop
 //     of a call of n inputs), and only for the largest calls the context's candidate rows (16 * 4096 + 1024 for the call, before the crop);
+//   * a model with a confusable list (weighted on the device: conf.hip) adds four launches, conf_launch_small -- k_conf_screen,
+//     k_small_conf_order (a single-block LDS counting sort in place of the batch path's key / iota / radix sort), k_conf_script, k_conf_apply_* --
+//     after k_rank (late: k_rank without the cutoff, k_conf_apply_late cuts off) or between the compaction and k_rank (early,
+//     confusables_before_pruning): thirteen launches, still one host wait.  k_enc_strings leaves the bytes it staged on the device for them;
+//     the weights, the list, its order and k_conf_script's working set (SMALL_CF_BLOCKS waves, 60 MB) are the context's, created the first time it
+//     serves such a model.  A row the fixed working memory cannot weight (a string beyond 64 code points) discards the run like an overflow;
 //   * a run whose fills exceeded a fixed capacity (a handful of very short queries can) is discarded and the call takes the batch path.
 // Same kernels, same arithmetic as the batch path: the results are identical (tests/test_gpu_small.py: against the batch path and the oracle).
 #pragma once
@@ -30,6 +36,7 @@ constexpr uint32_t SMALL_LIST_BLOCKS = 2;    // blocks per region of the slot-li
 constexpr uint32_t SMALL_FS_BLK = 512;       // pair-list slots per block of k_filter_score (FS_BLK = 4096 in the batch path)
 constexpr uint32_t SMALL_FETCH_BLOCKS = 8;   // blocks of k_small_fetch: each computes the offsets, copies a share of the rows
 constexpr uint32_t SMALL_ROWS_PER_Q = 16;    // candidate rows per query the row buffers hold on average
+constexpr uint32_t SMALL_CF_BLOCKS = 160;    // one-wave blocks of k_conf_script (it strides): 160 x 371 KB = 60 MB of working set per context, not the 386 MB one wave per 64 row slots would be
 
 struct SmallCtx {
   int device = 0;
@@ -52,6 +59,8 @@ struct SmallCtx {
   int nplanes = 0;             // count-vector dwords the buffers were sized for
   std::vector<void*> blocks;   // device allocations (pool)
   size_t row_cap = 0;
+  SmallConf cf;                // confusable weighting: created by small_ctx_conf the first time the context serves a model with confusables
+  bool cf_ready = false;
 };
 constexpr size_t SMALL_IN_BLOB = (size_t)SMALL_MAX * (SMALL_MAX_BYTES + 1) + 64;
 
@@ -101,6 +110,34 @@ static SmallCtx* small_ctx_create(const DeviceLexicon* dl, std::string& err) {
   if (small_iota(e.perm, SMALL_MAX, c->st) != ANX_OK || hipStreamSynchronize(c->st) != hipSuccess) { err = "small path: set-up kernel"; return nullptr; }
   return c.release();
 }
+// The buffers of the confusable chain, once per context; false: no room (the call takes the batch path, a later call tries again)
+static bool small_ctx_conf(SmallCtx* c) {
+  if (c->cf_ready) return true;
+  const size_t mark = c->blocks.size();
+  bool ok = true;
+  auto dev = [&](auto** p, size_t bytes) {
+    void* q = nullptr;
+    if (!ok || pool_malloc(&q, bytes) != hipSuccess) { ok = false; return; }
+    c->blocks.push_back(q);
+    *p = static_cast<std::remove_reference_t<decltype(*p)>>(q);
+  };
+  SmallConf f;
+  uint8_t* text = nullptr;
+  uint32_t* textoff = nullptr;
+  dev(&f.weight, c->row_cap * sizeof(double)); dev(&f.need, c->row_cap * sizeof(uint2)); dev(&f.key, c->row_cap * sizeof(uint32_t)); dev(&f.order, c->row_cap * sizeof(uint32_t));
+  dev(&f.ctr, 8 * sizeof(uint32_t)); dev(&text, SMALL_IN_BLOB); dev(&textoff, (SMALL_MAX + 1) * sizeof(uint32_t));
+  dev(&f.work, conf_small_work_bytes(SMALL_CF_BLOCKS));
+  if (!ok) {
+    (void)hipGetLastError();
+    for (size_t i = mark; i < c->blocks.size(); ++i) pool_free(c->blocks[i]);
+    c->blocks.resize(mark);
+    return false;
+  }
+  f.work_blocks = SMALL_CF_BLOCKS;
+  c->cf = f; c->enc.text = text; c->enc.textoff = textoff;
+  c->cf_ready = true;
+  return true;
+}
 static SmallCtx* small_ctx_acquire(const DeviceLexicon* dl, std::string& err) {
   DevPool& pl = pool_of(dl->device);
   {
@@ -123,12 +160,23 @@ static void small_ctxs_destroy(int device) {  // (the current device is `device`
 
 static std::atomic<uint64_t> g_small_taken{0}, g_small_overflow{0};
 void small_stats(uint64_t* out) { out[0] = g_small_taken.load(); out[1] = g_small_overflow.load(); }
+static std::atomic<uint64_t> g_small_conf_taken{0}, g_small_conf_scripts{0}, g_small_conf_unweightable{0};
+// include/anx.h: calls answered with device confusables, edit scripts run on them, calls discarded for a row the device cannot weight
+extern "C" int anx_debug_small_conf_stats(uint64_t* out) {
+  if (!out) return ANX_EINVAL;
+  out[0] = g_small_conf_taken.load(); out[1] = g_small_conf_scripts.load(); out[2] = g_small_conf_unweightable.load();
+  return ANX_OK;
+}
 
 // 0: done (*out_rows: a block of the pinned result cache, *out_offs: malloc'd); 1: not taken (the caller uses the batch path);
 // negative: an error of the device
 int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* utf8, size_t n, const anx_params& p, anx_result** out_rows, size_t** out_offs,
                std::string& err) {
   if (!dl || n == 0 || n > SMALL_MAX || !switches().small_path || p.stop_at_exact_match || dl->nplanes > 42) return 1;
+  // confusables: 0 none, 1 late (after the crop, then re-rank + cutoff), 2 early (before the crop) -- Batch::conf_mode.  `p` is the caller's
+  // own parameter set; host-side weighting (ANX_CONFUSABLES=host) belongs to the batch path
+  const int conf_mode = m.confusables.empty() ? 0 : m.confusables_before_pruning ? 2 : 1;
+  if (conf_mode && switches().confusables_host) return 1;
   uint32_t lens[SMALL_MAX];
   uint32_t maxbytes = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -142,6 +190,7 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   if (!c) { (void)hipGetLastError(); return 1; }  // (no context: the batch path still works)
   struct Release { SmallCtx* c; ~Release() { small_ctx_release(c); } } rel{c};
   hipStream_t st = c->st;
+  if (conf_mode && !small_ctx_conf(c)) return 1;  // (no room for the working set: the batch path answers)
   // ---- inputs -> pinned staging -----------------------------------------------------------------------------------------------------
   uint32_t* h_off = reinterpret_cast<uint32_t*>(c->h_in + SMALL_IN_BLOB);
   {
@@ -176,8 +225,8 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   // ---- encode + tiles (+ the counters cleared) ----------------------------------------------------------------------------------------
   SmallZero z{};
   {
-    uint32_t* zp[8] = {c->counters, c->rctr, c->sctr, c->lctr, c->qsurv, c->qmaxfreq, c->qexpand, nullptr};
-    const uint32_t zn[8] = {CTR_N, SCAN_REGIONS * RC_STRIDE, SCAN_REGIONS * RC_STRIDE, 3 * SCAN_REGIONS * RC_STRIDE, n32, n32, n32, 0u};
+    uint32_t* zp[8] = {c->counters, c->rctr, c->sctr, c->lctr, c->qsurv, c->qmaxfreq, c->qexpand, conf_mode ? c->cf.ctr : nullptr};
+    const uint32_t zn[8] = {CTR_N, SCAN_REGIONS * RC_STRIDE, SCAN_REGIONS * RC_STRIDE, 3 * SCAN_REGIONS * RC_STRIDE, n32, n32, n32, conf_mode ? 8u : 0u};
     for (int i = 0; i < 8; ++i) { z.p[i] = zp[i]; z.n[i] = zn[i]; }
   }
   // the encoder kernels read the pinned staging buffer themselves (k_enc_strings<true>: a coalesced burst per block into LDS): a copy
@@ -189,7 +238,9 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   // returns: 1 000 inputs 164 -> 156 us with 8 instead of 32 slots per query)
   const uint32_t slots = n32 <= 128u ? 32u : n32 <= 512u ? 16u : 8u;
   guard.drain = true;
-  int rc = small_encode_launch(m, dl, c->enc, in_blob, in_off, n32, qw, p, z, slots, true, h_off, st, err);
+  SmallEnc enc = c->enc;
+  if (!conf_mode) enc.text = nullptr, enc.textoff = nullptr;  // (a plain model's call on a context that has served confusables: nothing to keep)
+  int rc = small_encode_launch(m, dl, enc, in_blob, in_off, n32, qw, p, z, slots, true, h_off, st, err);
   if (rc) return rc;
   // ---- scan -----------------------------------------------------------------------------------------------------------------------------
   const uint32_t region_cap = 1u << SMALL_SHIFT;
@@ -229,6 +280,7 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
     // k_filter_score's rarely used arguments live in device memory (FsCold): uploaded again only when they change (another model,
     // other weights / thresholds / row width) -- compared field by field (struct padding is not).  any_variants is part of the key: a
     // model with variant lists and one without share the context pool of a device.  (The batch path uploads its pinned copy with every run.)
+    // Nothing of FsCold depends on the confusable mode or the cutoff (both reach k_rank / k_conf_apply_late as launch arguments).
     const double key[12] = {sa.w_ld, sa.w_lcs, sa.w_prefix, sa.w_suffix, sa.w_case, sa.w_sum, sa.score_threshold, (double)sa.have_freq + 2.0 * (double)sa.any_variants, (double)sa.lqp, (double)sa.lcp, (double)sa.stride,
                             (double)sa.qw + 1e3 * (double)(reinterpret_cast<uintptr_t>(sa.quot) & 0xFFFFFFFFu)};
     if (!c->cold_valid || memcmp(key, c->cold_key, sizeof key) != 0) {
@@ -252,7 +304,8 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
     hipLaunchKernelGGL(k_score_pairs, lgrid, dim3(threads), plan.lds_bytes(), st, sl.lg, pa, sa, so);
   }
   // ---- compact + rank + the rows into the caller's block ---------------------------------------------------------------------------------
-  const RankArgs ra = rank_args_of(m, dl, p, p.cutoff_threshold);  // (the caller's cutoff: no device confusables on this path)
+  // late confusables: k_rank crops without the cutoff, k_conf_apply_late re-ranks and cuts off afterwards (Run::compact_rank)
+  const RankArgs ra = rank_args_of(m, dl, p, conf_mode == 1 ? 0.0 : p.cutoff_threshold);
   const uint32_t crow_cap = (uint32_t)c->row_cap;
   hipLaunchKernelGGL(k_small_offsets, dim3(1), dim3(SMALL_T), 0, st, c->qsurv, n32, c->soff, c->qcur);
   if (dl->any_variants)  // variant lists: a survivor expands to a row per VariantOf reference (+ itself), within the same fixed capacity
@@ -261,8 +314,13 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   else
     hipLaunchKernelGGL(k_compact_grouped, dim3(SCAN_REGIONS), dim3(COMPACT_B), 0, st, c->surv, c->sctr, SMALL_SURV_CAP, m.have_freq ? 1 : 0, c->qcur, dl->ent_rec, c->c_rows,
                        c->soff + n32, crow_cap, c->counters + CTR_OVERFLOW);
+  const SmallConfRun cr{n32, crow_cap, conf_mode == 2, c->soff, c->r_count, c->counters + CTR_OVERFLOW, c->enc.q_orig, c->enc.text, c->enc.textoff, c->c_rows, c->r_rows,
+                        p.cutoff_threshold, p.freq_weight};
+  if (conf_mode == 2 && (rc = conf_launch_small(m, dl, st, c->cf, cr, c->r_count, err))) return rc;
   launch_rank(ra, st, n32, c->soff, c->c_rows, c->qmaxfreq, c->qexpand, c->t_key, c->r_rows, c->r_count, crow_cap, c->counters + CTR_OVERFLOW, SegRows{nullptr, 0u, nullptr});
-  hipLaunchKernelGGL(k_small_fetch, dim3(n32 > 256u ? SMALL_FETCH_BLOCKS : 1u), dim3(SMALL_T), 0, st, n32, c->soff, c->r_count, c->r_rows, c->rctr, c->sctr, c->lctr, c->counters, h_off64, rows, (uint32_t)row_cap, crow_cap, h_ctl);
+  if (conf_mode == 1 && (rc = conf_launch_small(m, dl, st, c->cf, cr, c->r_count, err))) return rc;
+  hipLaunchKernelGGL(k_small_fetch, dim3(n32 > 256u ? SMALL_FETCH_BLOCKS : 1u), dim3(SMALL_T), 0, st, n32, c->soff, c->r_count, c->r_rows, c->rctr, c->sctr, c->lctr, c->counters,
+                     conf_mode ? c->cf.ctr : nullptr, h_off64, rows, (uint32_t)row_cap, crow_cap, h_ctl);
   // one check for the whole chain (the batch path: HIP_TRY per call)
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
     err = std::string("small path: ") + hipGetErrorString(hipGetLastError());
@@ -271,8 +329,12 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   guard.drain = false;  // (nothing in flight any more)
   // ---- did the run fit the fixed capacities? -----------------------------------------------------------------------------------------------
   const SmallCtl ctl = *h_ctl;
-  if (ctl.rows > row_cap || ctl.maxfill > fs_cap || ctl.surv_fill > SMALL_SURV_CAP || ctl.list_fill > SMALL_SURV_CAP || ctl.total_surv > crow_cap || ctl.overflow) {
+  // (conf_unweightable: a row beyond conf.hip's fixed working memory -- the batch path repeats such a batch with the host-side weighting;
+  // the list of rows to weight has a slot per candidate row, so conf_scripts > crow_cap cannot happen while total_surv fits)
+  if (ctl.rows > row_cap || ctl.maxfill > fs_cap || ctl.surv_fill > SMALL_SURV_CAP || ctl.list_fill > SMALL_SURV_CAP || ctl.total_surv > crow_cap || ctl.overflow ||
+      ctl.conf_unweightable || ctl.conf_scripts > crow_cap) {
     g_small_overflow.fetch_add(1, std::memory_order_relaxed);
+    if (ctl.conf_unweightable) g_small_conf_unweightable.fetch_add(1, std::memory_order_relaxed);
     return 1;  // the batch path sizes its buffers from what it measures
   }
   size_t* offs = static_cast<size_t*>(malloc((n + 1) * sizeof(size_t)));
@@ -283,5 +345,9 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   *out_rows = rows;
   *out_offs = offs;
   g_small_taken.fetch_add(1, std::memory_order_relaxed);
+  if (conf_mode) {
+    g_small_conf_taken.fetch_add(1, std::memory_order_relaxed);
+    g_small_conf_scripts.fetch_add(ctl.conf_scripts, std::memory_order_relaxed);
+  }
   return ANX_OK;
 }

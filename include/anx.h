@@ -368,12 +368,17 @@ int anx_debug_search_lattice_stats(uint64_t out[4]);
  * (PatternMatch::matches, what the host decoder evaluates), flat = 1: as the flattened element the device decoder evaluates.  *out = 0 / 1.
  * Host code only.  ANX_EINVAL: no such element; ANX_ELIMIT (flat = 1): the model's rule set is not in the flat form. */
 int anx_debug_contextrule_match(const anx_model *model, size_t rule, size_t position, uint64_t vocab_id, uint32_t lexindex, int flat, int *out);
-/* The small call: anx_find_variants_batch answers calls of at most 4096 inputs of at most 64 bytes each (single-device models without
- * variant lists, confusables or StopAtExactMatch) through a path of nine launches and one host wait with preallocated buffers (the
- * reference's own granularity: one string per call, src/lib.rs:972; 1 000 per batch, src/bin/analiticcl.rs:416) instead of the batch
+/* The small call: anx_find_variants_batch answers calls of at most 4096 inputs of at most 64 bytes each (single-device models, with
+ * or without variant lists and confusables -- the latter when they are weighted on the device, i.e. not under ANX_CONFUSABLES=host --
+ * and without StopAtExactMatch) through a path of nine launches (thirteen with confusables) and one host wait with preallocated buffers
+ * (the reference's own granularity: one string per call, src/lib.rs:972; 1 000 per batch, src/bin/analiticcl.rs:416) instead of the batch
  * pipeline; results are identical.  ANX_SMALL=0 switches it off (A/B).  out[0] = calls it answered since the library was loaded,
  * out[1] = calls it handed to the batch pipeline because a fixed capacity did not hold. */
 int anx_debug_small_stats(uint64_t out[2]);
+/* Of those, the calls on models with confusables: out[0] = calls the small path answered with the weighting on the device, out[1] = edit
+ * scripts run for them, out[2] = calls discarded (counted in anx_debug_small_stats out[1] too) because a row was beyond the fixed
+ * working memory of the device weighting (a string of more than 64 code points): the batch pipeline answered with the host weighting. */
+int anx_debug_small_conf_stats(uint64_t out[3]);
 /* The length-partitioned split by itself (no device needed): which of n_shards replicas each of the n inputs
  * would go to (out_shard[i] in 0 .. n_shards - 1; see anx_batch_shard_info).  bench.py and the tests use it to build one GPU's share of
  * a larger job (BASELINE configs[3]) on a one-GPU box.  learn_ms (may be NULL): the device times of THOSE shares, measured by the caller
