@@ -198,6 +198,10 @@ def lib():
         "anx_counts_free": (None, [C.POINTER(C.c_uint32)]),
         "anx_batch_export_topk": (C.c_int, [vp, vp, C.c_uint32, vp]),
         "anx_batch_export_compact": (C.c_int, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "anx_batch_export_compact_via": (C.c_int, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "anx_batch_gather_compact_via": (C.c_int, [vp, C.c_int, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "anx_batch_export_topk_via": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+        "anx_debug_small_replica_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), sz]),
         "anx_batch_get_stats": (C.c_int, [vp, C.POINTER(BatchStats), C.c_size_t]),
         "anx_shutdown": (None, []),
         "anx_pipeline_new": (vp, [vp, C.c_int]),

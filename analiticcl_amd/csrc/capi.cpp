@@ -61,6 +61,12 @@ struct Replica {
   void* stream = nullptr;              // non-blocking stream of the replica (multi-replica batches run on it)
   std::unique_ptr<Worker> worker;      // only with more than one replica
 };
+// The small call's book-keeping of one replica (anx_find_variants_batch): calls in flight there now -- the replica choice reads it --
+// and calls it has answered (anx_debug_small_replica_stats).  A cache line each: concurrent callers on different replicas do not share one.
+struct alignas(64) SmallLoad {
+  std::atomic<uint32_t> inflight{0};
+  std::atomic<uint64_t> answered{0};
+};
 struct Shard {  // the part of a batch one replica holds: inputs [lo, lo + n) of the call, or -- length-partitioned split -- the inputs idx[0 .. n)
   int replica = 0;
   anx::Batch* b = nullptr;
@@ -95,6 +101,8 @@ struct anx_model {
   anx::DeviceLexicon* dev = nullptr;   // == replicas[0].dev
   std::vector<Replica> replicas;
   mutable LengthCost len_cost;
+  std::unique_ptr<SmallLoad[]> small_load;     // one per replica (anx_model_to_devices)
+  mutable std::atomic<uint32_t> small_next{0}; // where the replica choice of the small call starts looking: rotates with every call
   void* learn_vocab = nullptr;                 // learn mode's vocabulary table on replica 0's device (learn.hip via learn_capi.cpp)
   void (*learn_vocab_release)(void*) = nullptr;
 };
@@ -281,6 +289,7 @@ static void drop_replicas(anx_model* m) {
     anx::lexicon_free(r.dev);
   }
   m->replicas.clear();
+  m->small_load.reset();
   m->dev = nullptr;
   if (m->learn_vocab_release) m->learn_vocab_release(m->learn_vocab);
   m->learn_vocab = nullptr;
@@ -369,6 +378,7 @@ int anx_model_to_devices(anx_model* m, const int* devices, int n) {
     m->replicas.push_back(std::move(r));
   }
   m->dev = m->replicas[0].dev;
+  m->small_load.reset(new SmallLoad[m->replicas.size()]);
   return ANX_OK;
 }
 int anx_model_to_device(anx_model* m, int device) { return anx_model_to_devices(m, &device, 1); }
@@ -434,6 +444,12 @@ int anx_debug_set_switch(const char* name, const char* value) {
   return anx::set_switch(name, value) ? ANX_OK : fail(ANX_EINVAL, "unknown switch");
 }
 void anx_debug_kernel_timer(int enable) { anx::kernel_timer_enable(enable != 0); }
+int anx_debug_small_replica_stats(const anx_model* m, uint64_t* out, size_t cap) {
+  if (!m || (!out && cap)) return fail(ANX_EINVAL, "NULL argument");
+  const size_t R = m->replicas.size();
+  for (size_t i = 0; i < R && i < cap; ++i) out[i] = m->small_load[i].answered.load(std::memory_order_relaxed);
+  return (int)R;
+}
 int anx_debug_small_stats(uint64_t* out) { if (!out) return fail(ANX_EINVAL, "NULL argument"); anx::small_stats(out); return ANX_OK; }
 int anx_debug_kernel_time(const char* name, double* total_ms, uint64_t* launches) {
   return anx::kernel_timer_read(name, total_ms, launches) ? ANX_OK : fail(ANX_EINVAL, "no launch of that kernel was timed");
@@ -1603,6 +1619,25 @@ void anx_batch_free(anx_batch* b) {
   delete b;
 }
 
+}  // extern "C"
+// The replica a small call runs on: the one with the fewest small calls in flight, ties broken from a start index that moves on with every
+// call -- consecutive callers walk the replicas, concurrent ones spread.  Two relaxed atomics, no lock; replicas without a device copy (the
+// fake devices of the host test harness) are passed over.  -1: none.
+static int small_replica(const anx_model* m) {
+  const size_t R = m->replicas.size();
+  if (R == 1) return m->replicas[0].dev ? 0 : -1;
+  const size_t start = m->small_next.fetch_add(1, std::memory_order_relaxed) % R;
+  int best = -1;
+  uint32_t least = 0;
+  for (size_t k = 0; k < R; ++k) {
+    const size_t i = start + k < R ? start + k : start + k - R;
+    if (!m->replicas[i].dev) continue;
+    const uint32_t load = m->small_load[i].inflight.load(std::memory_order_relaxed);
+    if (best < 0 || load < least) { best = (int)i; least = load; }
+  }
+  return best;
+}
+extern "C" {
 int anx_find_variants_batch(const anx_model* m, const char* const* utf8, size_t n, const anx_params* p,
                             anx_result** out_rows, size_t** out_offsets) {
   if (!out_rows || !out_offsets) return fail(ANX_EINVAL, "NULL output argument");
@@ -1613,11 +1648,18 @@ int anx_find_variants_batch(const anx_model* m, const char* const* utf8, size_t 
   // (src/lib.rs:972, src/bin/analiticcl.rs:416) -- in nine launches and one host wait instead of the batch pipeline.  A model with
   // confusables is taken when they are weighted on the device (thirteen launches): small_find gets the caller's own parameters then, as
   // anx_batch_encode's dev_conf batches do, and derives late / early from the model; host-side weighting stays with the batch path
-  if (m && utf8 && p && n >= 1 && n <= 4096 && m->host.built && m->replicas.size() == 1 && m->replicas[0].dev && anx::switches().small_path) {
-    if (m->host.confusables.empty() || !anx::switches().confusables_host) {
+  // A multi-device model runs the WHOLE call on one replica (small_replica below): the calls of concurrent and of consecutive callers spread
+  // over the devices, a call is never split
+  if (m && utf8 && p && n >= 1 && n <= 4096 && m->host.built && !m->replicas.empty() && anx::switches().small_path) {
+    const int r = (m->host.confusables.empty() || !anx::switches().confusables_host) ? small_replica(m) : -1;
+    if (r >= 0) {
+      SmallLoad& load = m->small_load[(size_t)r];
+      const bool several = m->replicas.size() > 1;
+      if (several) load.inflight.fetch_add(1, std::memory_order_relaxed);
       std::string err;
-      const int rc = anx::small_find(m->host, m->replicas[0].dev, utf8, n, *p, out_rows, out_offsets, err);
-      if (rc == ANX_OK) return ANX_OK;
+      const int rc = anx::small_find(m->host, m->replicas[(size_t)r].dev, utf8, n, *p, out_rows, out_offsets, err);
+      if (several) load.inflight.fetch_sub(1, std::memory_order_relaxed);
+      if (rc == ANX_OK) { load.answered.fetch_add(1, std::memory_order_relaxed); return ANX_OK; }
       if (rc < 0) return fail(rc, err);
     }
   }
@@ -1926,6 +1968,17 @@ int learn_rebuild(anx_model* m, double* ms_build, double* ms_upload) {
   return rc2;
 }
 }  // namespace
+
+// ---- what export_capi.cpp (the exports with `via`) reaches of a batch: the engine calls themselves are made there --------------------------
+size_t anx_export_num_shards(const anx_batch* b) { return b->shards.size(); }
+// shard g: its replica's lexicon, its device batch (nullptr: never encoded) and the stream its exports run on (the caller's for a one-replica model)
+void anx_export_shard(const anx_batch* b, size_t g, void* caller_stream, const anx::DeviceLexicon** dl, anx::Batch** sb, void** stream) {
+  const Shard& s = b->shards[g];
+  *dl = b->model->replicas[(size_t)s.replica].dev;
+  *sb = s.b;
+  *stream = shard_stream(b, s, caller_stream);
+}
+int anx_export_on_shards(const anx_batch* b, const std::function<int(size_t, std::string&)>& fn) { return on_shards(b, fn); }
 
 // what learn_capi.cpp (strict mode: the device fold) needs of the model and of a batch
 anx::HostModel& anx_learn_host(anx_model* m) { return m->host; }

@@ -89,6 +89,13 @@ int batch_export_compact(const DeviceLexicon* dl, const Batch* b, void* dst, siz
 // devices see each other, staged through the host otherwise); returns when the bytes are at their destination
 size_t batch_compact_bytes(const Batch* b);
 int batch_gather_compact(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err);
+// The exports with `via` (the vocabulary id of the variant a row was reached through, 0xFFFFFFFF = none), for every model: the compact form
+// followed by u32 via[n_results] (batch_compact_via_bytes in all; offsets and records byte-equal to batch_export_compact's), the gather of
+// that section, and the fixed-stride form with a parallel array via[n_input * stride] (0xFFFFFFFF also in every unused slot)
+size_t batch_compact_via_bytes(const Batch* b);
+int batch_export_compact_via(const DeviceLexicon* dl, const Batch* b, void* dst, size_t capacity, void* stream, size_t* used, std::string& err);
+int batch_gather_compact_via(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err);
+int batch_export_topk_via(const DeviceLexicon* dl, const Batch* b, void* dst, void* via, uint32_t stride, void* stream, std::string& err);
 // test hook (adjacency.hip): the adjacency lists of the given signatures as the replica holds them
 int adjacency_debug_lists(const DeviceLexicon* d, const uint64_t* sigs, size_t n, uint32_t* out_cum, uint32_t** out_ids, std::string& err);
 void batch_stats(const Batch* b, anx_batch_stats* s);

@@ -1830,9 +1830,30 @@ int batch_export_topk(const DeviceLexicon* dl, const Batch* b, void* dst, uint32
   b->async_stream = stream; b->async_pending = true;
   const uint64_t total = (uint64_t)b->nq * stride;
   if (total)
-    hipLaunchKernelGGL(k_export_topk, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(k_export_topk<false>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), (uint32_t)b->nq, stride, b->soff, b->r_count,
-                       b->r_rows, b->q_orig, static_cast<anx_topk_record*>(dst));
+                       b->r_rows, b->q_orig, static_cast<anx_topk_record*>(dst), static_cast<uint32_t*>(nullptr));
+  HIP_TRY(hipGetLastError());
+  return ANX_OK;
+}
+// The same with the `via` word of every slot in a parallel array via[n_input * stride] (k_export_topk<true>): 0xFFFFFFFF for rows
+// without one and for unused slots -- also those of inputs the encoder dropped (no query: their RECORD slots stay untouched, as above)
+int batch_export_topk_via(const DeviceLexicon* dl, const Batch* b, void* dst, void* via, uint32_t stride, void* stream, std::string& err) {
+  (void)dl;
+  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
+  if (!dst || !via || stride == 0) { err = "bad export arguments"; return ANX_EINVAL; }
+  if (stride < b->max_rows) {
+    err = "export stride " + std::to_string(stride) + " is smaller than the longest result list (" + std::to_string(b->max_rows) + " rows): use a larger stride or anx_batch_export_compact_via";
+    return ANX_ELIMIT;
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  b->async_stream = stream; b->async_pending = true;
+  if (b->nq < b->n_input) HIP_TRY(hipMemsetAsync(via, 0xFF, b->n_input * (size_t)stride * sizeof(uint32_t), st));
+  const uint64_t total = (uint64_t)b->nq * stride;
+  if (total)
+    hipLaunchKernelGGL(k_export_topk<true>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, (uint32_t)b->nq, stride, b->soff, b->r_count,
+                       b->r_rows, b->q_orig, static_cast<anx_topk_record*>(dst), static_cast<uint32_t*>(via));
   HIP_TRY(hipGetLastError());
   return ANX_OK;
 }
@@ -1864,16 +1885,47 @@ int batch_export_compact(const DeviceLexicon* dl, const Batch* b, void* dst, siz
   return ANX_OK;
 }
 
+// The compact form followed by the `via` words of its rows (EmitRecordVia): [u32 offsets[n + 1] padded to 16 bytes][records][u32 via[n_results]]
+// -- offsets and records are the bytes batch_export_compact writes; a model without variant lists gets 0xFFFFFFFF in every word
+size_t batch_compact_via_bytes(const Batch* b) { return batch_compact_bytes(b) + (b->ran ? (size_t)b->n_results : 0) * sizeof(uint32_t); }
+int batch_export_compact_via(const DeviceLexicon* dl, const Batch* b, void* dst, size_t capacity, void* stream, size_t* used, std::string& err) {
+  (void)dl;
+  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
+  if (!dst || !used) { err = "bad export arguments"; return ANX_EINVAL; }
+  const size_t n = b->n_input;
+  const size_t off_bytes = ((n + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
+  *used = batch_compact_via_bytes(b);
+  if (capacity < *used) { err = "export buffer too small: " + std::to_string(*used) + " bytes needed"; return ANX_ELIMIT; }
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  b->async_stream = stream; b->async_pending = true;
+  uint32_t* d_off = static_cast<uint32_t*>(dst);
+  anx_topk_record* d_rows = reinterpret_cast<anx_topk_record*>(static_cast<char*>(dst) + off_bytes);
+  uint32_t* d_via = reinterpret_cast<uint32_t*>(d_rows + b->n_results);
+  if (n == 0 || b->nq == 0) { HIP_TRY(hipMemsetAsync(d_off, 0, off_bytes, st)); return ANX_OK; }
+  if (!b->x_cnt) {
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_cnt), n * sizeof(uint32_t)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_tmp), scan_tmp_bytes(n)));
+  }
+  if (const int rc = enqueue_rows(b, b->x_cnt, d_off, b->x_tmp, st, EmitRecordVia{d_rows, d_via}, err)) return rc;
+  HIP_TRY(hipGetLastError());
+  return ANX_OK;
+}
+
 size_t batch_compact_bytes(const Batch* b) {
   return (((b->n_input + 1) * sizeof(uint32_t) + 15) & ~(size_t)15) + (b->ran ? (size_t)b->n_results : 0) * sizeof(anx_topk_record);
 }
-int batch_gather_compact(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err) {
+// with_via: the section is batch_export_compact_via's
+static int gather_compact(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, bool with_via, std::string& err) {
   if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  const size_t need = batch_compact_bytes(b);
+  const size_t need = with_via ? batch_compact_via_bytes(b) : batch_compact_bytes(b);
   if (capacity < need) { err = "gather buffer too small: " + std::to_string(need) + " bytes needed for this shard"; return ANX_ELIMIT; }
+  auto export_to = [&](void* to, size_t cap, size_t* used) {
+    return with_via ? batch_export_compact_via(dl, b, to, cap, stream, used, err) : batch_export_compact(dl, b, to, cap, stream, used, err);
+  };
   size_t used = 0;
   if (b->device == dst_device) {  // already where the rows are wanted
-    const int rc = batch_export_compact(dl, b, dst, capacity, stream, &used, err);
+    const int rc = export_to(dst, capacity, &used);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
     return ANX_OK;
@@ -1890,7 +1942,7 @@ int batch_gather_compact(const DeviceLexicon* dl, const Batch* b, int dst_device
   void* tmp = nullptr;
   HIP_TRY(pool_malloc(&tmp, std::max<size_t>(need, 16)));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int rc = batch_export_compact(dl, b, tmp, need, stream, &used, err);
+  int rc = export_to(tmp, need, &used);
   if (rc == ANX_OK) {
     const hipError_t e = hipMemcpyPeerAsync(dst, dst_device, tmp, b->device, used, st);
     if (e != hipSuccess) { err = std::string("hipMemcpyPeerAsync: ") + hipGetErrorString(e); rc = ANX_ENODEVICE; }
@@ -1898,6 +1950,12 @@ int batch_gather_compact(const DeviceLexicon* dl, const Batch* b, int dst_device
   (void)hipStreamSynchronize(st);
   pool_free(tmp);
   return rc;
+}
+int batch_gather_compact(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err) {
+  return gather_compact(dl, b, dst_device, dst, capacity, stream, false, err);
+}
+int batch_gather_compact_via(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err) {
+  return gather_compact(dl, b, dst_device, dst, capacity, stream, true, err);
 }
 
 // Scored pairs per input query, counted by the scan of a PRODUCTION run (pairs that fail the DL's length test are only

@@ -745,11 +745,13 @@ __global__ __launch_bounds__(256) void k_emit_rows(uint32_t nq, const uint32_t* 
   for (uint32_t i = 0; i < n; ++i) emit(dst + i, r_rows[src + i]);
 }
 // fixed-stride export: `stride` records per query in input order, the unused ones marked with vocab_id 0xFFFFFFFF
+// VIA: also one `via` word per slot into the parallel array out_via (0xFFFFFFFF for rows without one and for unused slots)
+template <bool VIA>
 __global__ __launch_bounds__(256) void k_export_topk(uint32_t nq, uint32_t stride, const uint32_t* __restrict__ soff,
                                                      const uint32_t* __restrict__ r_count,
                                                      const DevRow* __restrict__ r_rows,
                                                      const uint32_t* __restrict__ q_orig,
-                                                     anx_topk_record* __restrict__ out) {
+                                                     anx_topk_record* __restrict__ out, uint32_t* __restrict__ out_via) {
   const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= (uint64_t)nq * stride) return;
   const uint32_t q = (uint32_t)(t / stride), i = (uint32_t)(t % stride);
@@ -757,8 +759,14 @@ __global__ __launch_bounds__(256) void k_export_topk(uint32_t nq, uint32_t strid
   r.vocab_id = 0xFFFFFFFFu;
   r.freq_score = 0.0f;
   r.dist_score = 0.0;
-  if (i < r_count[q]) r = topk_record_of(r_rows[soff[q] + i]);
+  uint32_t via = 0xFFFFFFFFu;
+  if (i < r_count[q]) {
+    const DevRow d = r_rows[soff[q] + i];
+    r = topk_record_of(d);
+    if constexpr (VIA) via = d.via;
+  }
   out[(size_t)q_orig[q] * stride + i] = r;
+  if constexpr (VIA) out_via[(size_t)q_orig[q] * stride + i] = via;
 }
 
 // ------------------------------------------------------------------------------------------------

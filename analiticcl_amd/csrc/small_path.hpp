@@ -54,7 +54,7 @@ struct SmallCtx {
   double* t_key = nullptr;
   FsCold* d_cold = nullptr;
   FsCold h_cold_last;          // what d_cold holds (uploaded again only when it changes: cold_key)
-  double cold_key[12] = {};
+  double cold_key[13] = {};
   bool cold_valid = false;
   int nplanes = 0;             // count-vector dwords the buffers were sized for
   std::vector<void*> blocks;   // device allocations (pool)
@@ -281,8 +281,11 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
     // other weights / thresholds / row width) -- compared field by field (struct padding is not).  any_variants is part of the key: a
     // model with variant lists and one without share the context pool of a device.  (The batch path uploads its pinned copy with every run.)
     // Nothing of FsCold depends on the confusable mode or the cutoff (both reach k_rank / k_conf_apply_late as launch arguments).
-    const double key[12] = {sa.w_ld, sa.w_lcs, sa.w_prefix, sa.w_suffix, sa.w_case, sa.w_sum, sa.score_threshold, (double)sa.have_freq + 2.0 * (double)sa.any_variants, (double)sa.lqp, (double)sa.lcp, (double)sa.stride,
-                            (double)sa.qw + 1e3 * (double)(reinterpret_cast<uintptr_t>(sa.quot) & 0xFFFFFFFFu)};
+    // sa.quot is the one lexicon-side pointer in FsCold, so the WHOLE pointer is in the key (low and high half: each exact in a double): the
+    // replicas of a multi-device model that live on one device share this pool, their tables can lie a multiple of 4 GB apart, and a context
+    // that last served one replica must not hand the other a pointer into a lexicon its owner may free
+    const double key[13] = {sa.w_ld, sa.w_lcs, sa.w_prefix, sa.w_suffix, sa.w_case, sa.w_sum, sa.score_threshold, (double)sa.have_freq + 2.0 * (double)sa.any_variants, (double)sa.lqp, (double)sa.lcp, (double)sa.stride,
+                            (double)sa.qw + 1e3 * (double)(reinterpret_cast<uintptr_t>(sa.quot) & 0xFFFFFFFFu), (double)((uint64_t)reinterpret_cast<uintptr_t>(sa.quot) >> 32)};
     if (!c->cold_valid || memcmp(key, c->cold_key, sizeof key) != 0) {
       memcpy(c->cold_key, key, sizeof key);
       c->h_cold_last = FsCold{sa, so, sl.l8, sl.lg, sl.lw};

@@ -329,23 +329,32 @@ class Batch:
         finally:
             L.lib().anx_counts_free(out)
 
-    def export_topk(self, device_ptr: int, stride: int, stream: int = 0):
-        L.check(L.lib().anx_batch_export_topk(self.h, C.c_void_p(device_ptr), stride, C.c_void_p(stream)))
+    def export_topk(self, device_ptr: int, stride: int, stream: int = 0, via_ptr: Optional[int] = None):
+        """`stride` records per input into a device buffer of n * stride * 16 bytes.  via_ptr: a second device buffer of n * stride
+        uint32 that receives the `via` of every slot (anx_batch_export_topk_via; 0xFFFFFFFF = none / unused slot), for every model."""
+        if via_ptr is None:
+            L.check(L.lib().anx_batch_export_topk(self.h, C.c_void_p(device_ptr), stride, C.c_void_p(stream)))
+        else:
+            L.check(L.lib().anx_batch_export_topk_via(self.h, C.c_void_p(device_ptr), C.c_void_p(via_ptr), stride, C.c_void_p(stream)))
 
-    def export_compact(self, device_ptr: int, capacity: int, stream: int = 0) -> int:
-        """offsets[n+1] (u32, padded to 16 bytes) + unpadded records into a device buffer; returns the bytes used."""
+    def export_compact(self, device_ptr: int, capacity: int, stream: int = 0, with_via: bool = False) -> int:
+        """offsets[n+1] (u32, padded to 16 bytes) + unpadded records into a device buffer; returns the bytes used.
+        with_via: followed by one uint32 `via` per record (anx_batch_export_compact_via: every model, variant lists included)."""
         used = C.c_size_t(0)
-        L.check(L.lib().anx_batch_export_compact(self.h, C.c_void_p(device_ptr), capacity, C.c_void_p(stream), C.byref(used)))
+        fn = L.lib().anx_batch_export_compact_via if with_via else L.lib().anx_batch_export_compact
+        L.check(fn(self.h, C.c_void_p(device_ptr), capacity, C.c_void_p(stream), C.byref(used)))
         return used.value
 
-    def gather_compact(self, dst_device: int, device_ptr: int, capacity: int):
+    def gather_compact(self, dst_device: int, device_ptr: int, capacity: int, with_via: bool = False):
         """anx_batch_gather_compact: every shard's compact export in one buffer on device dst_device (the shards' own devices copy
-        their sections over) -> (section offsets [shards + 1], bytes used)."""
+        their sections over) -> (section offsets [shards + 1], bytes used).  with_via: every section in export_compact(with_via=True)'s
+        layout (anx_batch_gather_compact_via)."""
         import numpy as np
         ns = L.lib().anx_batch_num_shards(self.h)
         offs = (C.c_size_t * (ns + 1))()
         used = C.c_size_t(0)
-        L.check(L.lib().anx_batch_gather_compact(self.h, dst_device, C.c_void_p(device_ptr), capacity, offs, C.byref(used)))
+        fn = L.lib().anx_batch_gather_compact_via if with_via else L.lib().anx_batch_gather_compact
+        L.check(fn(self.h, dst_device, C.c_void_p(device_ptr), capacity, offs, C.byref(used)))
         return np.array(list(offs), dtype=np.int64), used.value
 
     def free(self):
@@ -516,6 +525,16 @@ class VariantModel:
     @property
     def num_replicas(self) -> int:
         return L.lib().anx_model_num_replicas(self.h)
+
+    def small_replica_stats(self) -> List[int]:
+        """Per replica: the small calls (find_variants of at most 4096 short inputs) it has answered since the model went to its
+        devices (anx_debug_small_replica_stats) -- a multi-device model spreads such calls over its replicas, each call on one."""
+        n = L.lib().anx_model_num_replicas(self.h)
+        out = (C.c_uint64 * max(n, 1))()
+        got = L.lib().anx_debug_small_replica_stats(self.h, out, n)
+        if got < 0:
+            L.check(got)
+        return [int(out[i]) for i in range(min(n, got))]
 
     # -- introspection ------------------------------------------------------------------------------
     def __contains__(self, text: str) -> bool:

@@ -45,12 +45,24 @@ def gather_topk(local, n_total: int, stride: int, rank: int, world: int, dst: in
     return torch.cat(parts)
 
 
-def decode_topk(buf, n: int, stride: int) -> List[List[Tuple[int, float, float]]]:
-    """uint8 tensor / bytes -> per query [(vocab_id, dist_score, freq_score)] (empty slots dropped)."""
-    raw = bytes(buf.cpu().numpy().tobytes()) if hasattr(buf, "cpu") else bytes(buf)
-    a = np.frombuffer(raw, dtype=TOPK_DTYPE).reshape(n, stride)
-    return [[(int(r["vocab_id"]), float(r["dist_score"]), float(r["freq_score"])) for r in row if r["vocab_id"] != EMPTY]
-            for row in a]
+def _raw(buf) -> bytes:
+    return bytes(buf.cpu().numpy().tobytes()) if hasattr(buf, "cpu") else bytes(buf)
+
+
+def _via_or_none(v) -> Optional[int]:
+    return None if int(v) == EMPTY else int(v)
+
+
+def decode_topk(buf, n: int, stride: int, via=None):
+    """uint8 tensor / bytes -> per query [(vocab_id, dist_score, freq_score)] (empty slots dropped).
+    via: the parallel array of anx_batch_export_topk_via (n * stride uint32, tensor / bytes) -> 4-tuples (..., via or None)."""
+    a = np.frombuffer(_raw(buf), dtype=TOPK_DTYPE).reshape(n, stride)
+    if via is None:
+        return [[(int(r["vocab_id"]), float(r["dist_score"]), float(r["freq_score"])) for r in row if r["vocab_id"] != EMPTY]
+                for row in a]
+    v = np.frombuffer(_raw(via), dtype="<u4", count=n * stride).reshape(n, stride)
+    return [[(int(r["vocab_id"]), float(r["dist_score"]), float(r["freq_score"]), _via_or_none(w)) for r, w in zip(row, vrow) if r["vocab_id"] != EMPTY]
+            for row, vrow in zip(a, v)]
 
 
 # -- the gather of compact exports (anx_batch_export_compact): variable size, pipelined ---------------------------
@@ -58,17 +70,25 @@ def compact_offsets_bytes(n: int) -> int:
     return ((n + 1) * 4 + 15) & ~15
 
 
-def compact_capacity(n: int, stride: int) -> int:
-    """bytes that always suffice for n inputs with at most `stride` records each"""
-    return compact_offsets_bytes(n) + n * stride * TOPK_DTYPE.itemsize
+def compact_capacity(n: int, stride: int, with_via: bool = False) -> int:
+    """bytes that always suffice for n inputs with at most `stride` records each (with_via: anx_batch_export_compact_via's layout,
+    one uint32 more per record)"""
+    return compact_offsets_bytes(n) + n * stride * (TOPK_DTYPE.itemsize + (4 if with_via else 0))
 
 
-def decode_compact(buf, n: int) -> List[List[Tuple[int, float, float]]]:
-    """compact export (uint8 tensor / bytes) -> per input [(vocab_id, dist_score, freq_score)]"""
-    raw = bytes(buf.cpu().numpy().tobytes()) if hasattr(buf, "cpu") else bytes(buf)
+def decode_compact(buf, n: int, with_via: bool = False):
+    """compact export (uint8 tensor / bytes) -> per input [(vocab_id, dist_score, freq_score)]
+    with_via: the export of anx_batch_export_compact_via / a section of anx_batch_gather_compact_via, whose records are followed by
+    one uint32 per record -> 4-tuples (vocab_id, dist_score, freq_score, via or None)"""
+    raw = _raw(buf)
     off = np.frombuffer(raw, dtype="<u4", count=n + 1)
-    rows = np.frombuffer(raw, dtype=TOPK_DTYPE, count=int(off[n]), offset=compact_offsets_bytes(n))
-    return [[(int(r["vocab_id"]), float(r["dist_score"]), float(r["freq_score"])) for r in rows[off[i]:off[i + 1]]]
+    total = int(off[n])
+    rows = np.frombuffer(raw, dtype=TOPK_DTYPE, count=total, offset=compact_offsets_bytes(n))
+    if not with_via:
+        return [[(int(r["vocab_id"]), float(r["dist_score"]), float(r["freq_score"])) for r in rows[off[i]:off[i + 1]]]
+                for i in range(n)]
+    via = np.frombuffer(raw, dtype="<u4", count=total, offset=compact_offsets_bytes(n) + total * TOPK_DTYPE.itemsize)
+    return [[(int(r["vocab_id"]), float(r["dist_score"]), float(r["freq_score"]), _via_or_none(w)) for r, w in zip(rows[off[i]:off[i + 1]], via[off[i]:off[i + 1]])]
             for i in range(n)]
 
 

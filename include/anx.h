@@ -34,7 +34,9 @@ extern "C" {
  *    ANX_LEARN_HASH_BITS; compact records with `via` for models with variant lists (anx_batch_fetch_compact_via,
  *    anx_compact_to_results_via, anx_pipeline_next_via: additive, anx_topk_record and every existing call unchanged);
  *    anx_debug_search_lattice_stats and the test hook anx_debug_contextrule_match (models with context rules are decoded on the
- *    device: additive, results unchanged). */
+ *    device: additive, results unchanged); the device-side exports with `via` (anx_batch_export_compact_via,
+ *    anx_batch_gather_compact_via, anx_batch_export_topk_via: additive, the via-less exports unchanged) and the small call on
+ *    multi-device models (anx_debug_small_replica_stats; results unchanged). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -294,6 +296,19 @@ int anx_batch_export_compact(const anx_batch *, void *device_dst, size_t capacit
  * when all sections are in place; *used = bytes needed (also when ANX_ELIMIT says capacity is too small).  The reference's
  * counterpart is the collect() of its rayon fan-out (src/bin/analiticcl.rs:445-448). */
 int anx_batch_gather_compact(const anx_batch *, int dst_device, void *device_dst, size_t capacity, size_t *shard_offsets, size_t *used);
+/* The three exports with `via`, for EVERY model (the 16-byte anx_topk_record has no room for it, so the via-less exports above lose the
+ * `via` of every row of a model with variant lists): one uint32 per row beside the records, the vocabulary id of the variant the row
+ * was reached through (anx_result::via), UINT32_MAX = none -- every word of a model without variant lists.  Arguments are checked as by
+ * the via-less calls (batch not run / rows rescored on the host: ANX_EINVAL; several shards on export_*: ANX_EINVAL; capacity or stride
+ * too small: ANX_ELIMIT), and the offsets and records are byte-equal to what those write for the same batch.
+ * anx_batch_export_compact_via: as anx_batch_export_compact, followed by uint32 via[n_rows]:
+ *   [u32 offsets[n + 1] padded to 16 bytes][anx_topk_record rows[n_rows]][u32 via[n_rows]], n_rows = offsets[n]; *used counts all three.
+ * anx_batch_gather_compact_via: as anx_batch_gather_compact, every 256-byte-aligned shard section in that layout.
+ * anx_batch_export_topk_via: as anx_batch_export_topk, plus device_via[n * stride] words: slot (i, k) holds the `via` of record (i, k),
+ *   UINT32_MAX for rows without one and for every unused slot (also those of inputs that have no record written at all). */
+int anx_batch_export_compact_via(const anx_batch *, void *device_dst, size_t capacity, void *stream, size_t *used);
+int anx_batch_gather_compact_via(const anx_batch *, int dst_device, void *device_dst, size_t capacity, size_t *shard_offsets, size_t *used);
+int anx_batch_export_topk_via(const anx_batch *, void *device_dst, void *device_via, uint32_t stride, void *stream);
 typedef struct anx_batch_stats {
   uint64_t n_queries;
   uint64_t n_pairs;          /* scored (query,candidate) pairs = DL invocations of the reference */
@@ -368,8 +383,9 @@ int anx_debug_search_lattice_stats(uint64_t out[4]);
  * (PatternMatch::matches, what the host decoder evaluates), flat = 1: as the flattened element the device decoder evaluates.  *out = 0 / 1.
  * Host code only.  ANX_EINVAL: no such element; ANX_ELIMIT (flat = 1): the model's rule set is not in the flat form. */
 int anx_debug_contextrule_match(const anx_model *model, size_t rule, size_t position, uint64_t vocab_id, uint32_t lexindex, int flat, int *out);
-/* The small call: anx_find_variants_batch answers calls of at most 4096 inputs of at most 64 bytes each (single-device models, with
- * or without variant lists and confusables -- the latter when they are weighted on the device, i.e. not under ANX_CONFUSABLES=host --
+/* The small call: anx_find_variants_batch answers calls of at most 4096 inputs of at most 64 bytes each (models on one or several
+ * devices -- a multi-device model runs the whole call on ONE replica, the one with the fewest small calls in flight, so concurrent and
+ * consecutive callers spread over the devices; anx_debug_small_replica_stats --, with or without variant lists and confusables -- the latter when they are weighted on the device, i.e. not under ANX_CONFUSABLES=host --
  * and without StopAtExactMatch) through a path of nine launches (thirteen with confusables) and one host wait with preallocated buffers
  * (the reference's own granularity: one string per call, src/lib.rs:972; 1 000 per batch, src/bin/analiticcl.rs:416) instead of the batch
  * pipeline; results are identical.  ANX_SMALL=0 switches it off (A/B).  out[0] = calls it answered since the library was loaded,
@@ -379,6 +395,9 @@ int anx_debug_small_stats(uint64_t out[2]);
  * scripts run for them, out[2] = calls discarded (counted in anx_debug_small_stats out[1] too) because a row was beyond the fixed
  * working memory of the device weighting (a string of more than 64 code points): the batch pipeline answered with the host weighting. */
 int anx_debug_small_conf_stats(uint64_t out[3]);
+/* Per replica of the model (anx_model_to_devices order): the calls the small path answered THERE since the model went to its devices.
+ * Writes min(cap, replicas) words and returns the number of replicas (negative: error). */
+int anx_debug_small_replica_stats(const anx_model *model, uint64_t *out, size_t cap);
 /* The length-partitioned split by itself (no device needed): which of n_shards replicas each of the n inputs
  * would go to (out_shard[i] in 0 .. n_shards - 1; see anx_batch_shard_info).  bench.py and the tests use it to build one GPU's share of
  * a larger job (BASELINE configs[3]) on a one-GPU box.  learn_ms (may be NULL): the device times of THOSE shares, measured by the caller
