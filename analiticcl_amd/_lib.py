@@ -69,6 +69,12 @@ class Pair(C.Structure):
                 ("score", C.c_double)]
 
 
+class PairScore(C.Structure):  # anx_pair_score, 24 bytes
+    _fields_ = [("score", C.c_double), ("ld", C.c_uint16), ("lcs", C.c_uint16), ("prefixlen", C.c_uint16),
+                ("suffixlen", C.c_uint16), ("len_a", C.c_uint8), ("len_b", C.c_uint8), ("samecase", C.c_uint8),
+                ("status", C.c_int8), ("_pad", C.c_uint32)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("n_queries", C.c_uint64), ("n_pairs", C.c_uint64), ("n_class_tests", C.c_uint64),
                 ("n_results", C.c_uint64), ("n_scan_blocks", C.c_uint64), ("n_tests_kind", C.c_uint64 * 5),
@@ -194,6 +200,8 @@ def lib():
         "anx_compact_to_results_via": (None, [C.c_void_p, C.POINTER(C.c_uint32), sz, C.POINTER(Result)]),
         "anx_batch_fetch_pairs": (C.c_int, [vp, C.POINTER(C.POINTER(Pair)), C.POINTER(sz)]),
         "anx_pairs_free": (None, [C.POINTER(Pair)]),
+        "anx_score_pairs": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(PairScore)]),
+        "anx_score_pairs_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(PairScore)]),
         "anx_batch_pair_counts": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_uint32))]),
         "anx_counts_free": (None, [C.POINTER(C.c_uint32)]),
         "anx_batch_export_topk": (C.c_int, [vp, vp, C.c_uint32, vp]),

@@ -1,4 +1,4 @@
-"""`python -m analiticcl_amd query|search|learn ...` -- the `analiticcl query` / `search` / `learn` command line
+"""`python -m analiticcl_amd query|search|learn|score ...` -- the `analiticcl query` / `search` / `learn` command line
 (/root/reference/src/bin/analiticcl.rs) on top of the MI355X engine.
 
 Same option names and defaults (note the CLI's own weight defaults 0.5/0.125/0.125/0.125/0.125, bin:760-800, and
@@ -7,7 +7,9 @@ k=3 d=2 n=10, bin:800-817), same TSV / JSON output (bin:21-187).  `query` reads 
 into texts like bin:561-636 and decodes them with find_all_matches.  `learn` (bin:484-553) reads the whole input, runs
 `--iterations` rounds of learn_variants over it (`--strict`: one string per line, find_variants; otherwise one text per line,
 find_all_matches) and writes the weighted variant list (bin:186-365; `-O`: one file per lexicon, with the reference's selection
-and field quirks).  Not mirrored: index mode,
+and field quirks).  `score` has no counterpart in the reference's binary: it reads `a<TAB>b` lines and writes the model's measures
+for each pair (score_pairs: the reference's public distance functions, src/distance.rs:101-231, and the score of src/lib.rs:1433-1452).
+Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
 (the flag is looked up under the wrong name, bin:1175), has no effect; `--allow-overlap`, `--lm-order` and `--weight-context` are
@@ -88,7 +90,7 @@ def json_item(inp: str, variants: Optional[List[dict]], seqnr: int, offset=None,
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m analiticcl_amd", description=__doc__.split("\n\n")[0])
-    p.add_argument("mode", choices=["query", "search", "learn"])
+    p.add_argument("mode", choices=["query", "search", "learn", "score"])
     p.add_argument("files", nargs="*", help="input files (default: standard input)")
     p.add_argument("--lexicon", "-l", action="append", default=[])
     p.add_argument("--variants", "-V", action="append", default=[])
@@ -380,6 +382,51 @@ def run_learn(model, params, a, out) -> None:
     out.flush()
 
 
+def score_tsv_line(a: str, b: str, r: dict) -> str:
+    """a, b, score, ld, lcs, prefix, suffix, samecase; a pair with a status (an empty side, more than 255 symbols) keeps its two
+    strings and gets empty measure columns."""
+    if r["status"]:
+        return f"{a}\t{b}\t\t\t\t\t\t"
+    return "\t".join([a, b, rust_f64(r["score"]), str(r["ld"]), str(r["lcs"]), str(r["prefixlen"]), str(r["suffixlen"]),
+                      "1" if r["samecase"] else "0"])
+
+
+def score_json_item(a: str, b: str, r: dict, seqnr: int) -> str:
+    head = "    ," if seqnr > 1 else "    "
+    if r["status"]:
+        return '%s{ "a": "%s", "b": "%s", "status": %d }\n' % (head, _esc(a), _esc(b), r["status"])
+    return '%s{ "a": "%s", "b": "%s", "score": %s, "ld": %d, "lcs": %d, "prefix": %d, "suffix": %d, "samecase": %s }\n' % (
+        head, _esc(a), _esc(b), rust_f64(r["score"]), r["ld"], r["lcs"], r["prefixlen"], r["suffixlen"], "true" if r["samecase"] else "false")
+
+
+def run_score(model, a, out) -> None:
+    """`score`: every input line is `a<TAB>b` (a line without a tab: b is empty); the pairs of --batch-size lines are one
+    score_pairs call.  The model's lexicons play no part in the numbers: only its alphabet and weights do."""
+    seqnr = 0
+    pa: List[str] = []
+    pb: List[str] = []
+
+    def flush():
+        nonlocal seqnr
+        if not pa:
+            return
+        for x, y, r in zip(pa, pb, model.score_pairs(pa, pb)):
+            seqnr += 1
+            out.write(score_json_item(x, y, r, seqnr) if a.json else score_tsv_line(x, y, r) + "\n")
+        out.flush()
+        pa.clear()
+        pb.clear()
+
+    limit = 1 if a.interactive else max(1, a.batch_size)
+    for line in _lines(a.files):
+        x, _, y = (line[:-1] if line.endswith("\r") else line).partition("\t")
+        pa.append(x)
+        pb.append(y.split("\t", 1)[0])
+        if len(pa) >= limit:
+            flush()
+    flush()
+
+
 def main(argv=None) -> int:
     a = build_parser().parse_intermixed_args(argv)
     if a.mode == "learn" and not 0 <= a.iterations <= 255:
@@ -393,7 +440,10 @@ def main(argv=None) -> int:
         return 0
     if a.json:
         out.write("[\n")
-    (run_query if a.mode == "query" else run_search)(model, params, a, out)
+    if a.mode == "score":
+        run_score(model, a, out)
+    else:
+        (run_query if a.mode == "query" else run_search)(model, params, a, out)
     if a.json:
         out.write("]\n")
     return 0

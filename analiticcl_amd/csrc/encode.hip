@@ -66,10 +66,7 @@ struct EncArgs {
   uint32_t* keep_off;       // weighting reads them there); nullptr: not kept
 };
 
-// Where the codes of string i start: the bytes of string i and its separator are >= symbols + 1, and rounding every start up to a
-// dword plus one dword per string keeps the regions disjoint (start(i+1) - start(i) is a multiple of 4 that is >= symbols + 2).
-// The buffer holds blob bytes + 4 n + 16.
-__device__ inline uint32_t code_off(uint32_t off_i, uint32_t i) { return ((off_i + 3u) & ~3u) + 4u * i; }
+// (code_off, where the codes of string i start: engine_internal.h -- pairs.hip reads them there too)
 // 16 bytes of the blob from any byte position: aligned dwords + v_alignbyte; only dwords that hold one of the `left` bytes are read
 __device__ inline void load_window(const uint8_t* __restrict__ blob, uint32_t pos, uint32_t left, uint32_t (&r)[4]) {
   const uint32_t sh = pos & 3u;
@@ -661,6 +658,20 @@ int small_encode_launch(const HostModel& m, const DeviceLexicon* dl, const Small
   ta.tq = 1; ta.nq = n; ta.q_meta = e.q_meta; ta.s_kind = e.s_kind; ta.s_sig = e.s_sig; ta.ctr = nullptr;
   ta.head = nullptr; ta.tcount = nullptr; ta.tiles = e.tiles; ta.tkey = nullptr;
   hipLaunchKernelGGL(k_small_tiles, gn, dim3(256), 0, st, ga, ta, z, slots, dl->adj_hdr);
+  HIP_TRY(hipGetLastError());
+  return ANX_OK;
+}
+// The normaliser alone, for anx_score_pairs (pairs.hip): k_enc_strings over n strings that are already on the device.  Of what it
+// writes the pair kernels read the codes (at code_off) and meta (symbols in bits 0-7, first character lowercase in bit 24; 0 = empty
+// or more than 255 symbols); the thresholds behind meta's k / d bits are nobody's, so they are Absolute(0).
+int pairs_encode_launch(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n, hipStream_t st,
+                        std::string& err) {
+  anx_params p{};
+  EncArgs ea = enc_args_of(m, dl, p);
+  ea.blob = blob; ea.off = off; ea.n = n;
+  ea.codes = e.codes; ea.meta = e.meta; ea.bits = e.bits; ea.sig = e.sig; ea.kind = e.kind; ea.cv = e.cv; ea.key = e.key; ea.blk = e.blk;
+  ea.zero_cv = 1;  // (no memset launch ahead of the kernel)
+  hipLaunchKernelGGL(k_enc_strings<false>, dim3((n + 255) / 256), dim3(256), 0, st, ea);
   HIP_TRY(hipGetLastError());
   return ANX_OK;
 }

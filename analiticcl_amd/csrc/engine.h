@@ -144,6 +144,16 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& i
                    uint32_t* out_n, uint32_t* out_syms, std::string& err);
 void batch_free(Batch*);
 
+// ---- caller-chosen string pairs (pairs.hip): anx_score_pairs ------------------------------------------------------------------------
+// One chunk of at most PAIRS_CHUNK pairs: pair i = (a[i], b[i]), byte spans without their terminators.  out[i] receives the measures
+// of pair i (unrestricted Damerau-Levenshtein, longest common substring, common prefix / suffix, case flag) and the distance score
+// under the model's weights.  One upload, the encoder, at most one launch per tier (both sides <= PAIRS_SHORT_BYTES bytes: a pair per
+// lane; everything else: a pair per wave), one download.
+constexpr size_t PAIRS_CHUNK = (size_t)1 << 20;
+constexpr uint32_t PAIRS_SHORT_BYTES = 16;
+struct PairSpan { const char* p; size_t len; };
+int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, anx_pair_score* out, std::string& err);
+
 // ---- learn mode's fold on the device (learn.hip) ------------------------------------------------------------------------------------
 struct LearnVocab;  // vocabulary hash table of one device (text hash -> id): built on first use, rebuilt when the vocabulary size or ANX_LEARN_HASH_BITS changes
 void learn_vocab_free(LearnVocab*);

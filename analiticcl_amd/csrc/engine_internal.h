@@ -90,5 +90,14 @@ struct SmallZero { uint32_t* p[8]; uint32_t n[8]; };  // arrays k_small_tiles cl
 int small_encode_launch(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n, uint32_t qw,
                         const anx_params& p, const SmallZero& z, uint32_t slots, bool stage_lds, const uint32_t* host_off, hipStream_t st, std::string& err);  // host_off: the offsets as the HOST reads them (stage_lds: the blocks' byte ranges go into the kernel arguments)  // slots: tile slots per query (>= 8)
 int small_iota(uint32_t* perm, uint32_t n, hipStream_t st);
+// Where the encoder puts the codes of string i: the bytes of string i and its separator are >= symbols + 1, and rounding every start up
+// to a dword plus one dword per string keeps the regions disjoint (start(i+1) - start(i) is a multiple of 4 that is >= symbols + 2).
+// The buffer holds blob bytes + 4 n + 16.
+__host__ __device__ inline uint32_t code_off(uint32_t off_i, uint32_t i) { return ((off_i + 3u) & ~3u) + 4u * i; }
+
+// ---- anx_score_pairs (pairs.hip): caller-chosen pairs, scored by the model's measures ---------------------------------------------------
+// the normaliser alone over n strings on the device (encode.hip): of `e` the fields codes, meta, bits, sig, kind, cv, key, blk are used
+int pairs_encode_launch(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n, hipStream_t st,
+                        std::string& err);
 
 }  // namespace anx

@@ -612,6 +612,42 @@ class VariantModel:
         finally:
             L.lib().anx_results_free(rows, offs)
 
+    # -- caller-chosen pairs ----------------------------------------------------------------------------
+    PAIR_KEYS = ("score", "ld", "lcs", "prefixlen", "suffixlen", "samecase", "len_a", "len_b", "status")
+
+    def score_pairs_arrays(self, a: Sequence[str], b: Sequence[str], packed: bool = True) -> dict:
+        """anx_score_pairs: the model's measures for the pairs (a[i], b[i]) as numpy columns -- score (f64; the dist_score
+        find_variants would give the pair, input = a[i]), ld (unrestricted Damerau-Levenshtein, no distance bound), lcs, prefixlen,
+        suffixlen (u16), len_a, len_b (symbols), samecase (u8) and status (i8: 0, ANX_EEMPTY for an empty side, ANX_ELIMIT beyond 255
+        symbols; score, ld, lcs, prefixlen, suffixlen and samecase of such a pair are 0, len_a / len_b hold the symbols of a side that
+        could be normalised and 0 otherwise).  packed = False: the pointer form of the call instead of the packed one."""
+        import numpy as np
+        n = len(a)
+        if len(b) != n:
+            raise ValueError("score_pairs: a and b differ in length")
+        dt = np.dtype([("score", "<f8"), ("ld", "<u2"), ("lcs", "<u2"), ("prefixlen", "<u2"), ("suffixlen", "<u2"),
+                       ("len_a", "u1"), ("len_b", "u1"), ("samecase", "u1"), ("status", "i1"), ("_pad", "<u4")])
+        assert dt.itemsize == C.sizeof(L.PairScore)
+        out = np.zeros(max(n, 1), dtype=dt)
+        optr = out.ctypes.data_as(C.POINTER(L.PairScore))
+        if packed:
+            ba, bb = _pack(a), _pack(b)
+            L.check(L.lib().anx_score_pairs_packed(self.h, ba, len(ba), bb, len(bb), n, optr))
+        else:
+            aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in a])
+            ab = (C.c_char_p * max(n, 1))(*[_b(t) for t in b])
+            L.check(L.lib().anx_score_pairs(self.h, aa, ab, n, optr))
+        out = out[:n]
+        return {k: out[k].copy() for k in self.PAIR_KEYS}
+
+    def score_pairs(self, a: Sequence[str], b: Sequence[str]) -> List[dict]:
+        """score_pairs_arrays as one dict per pair (keys: score, ld, lcs, prefixlen, suffixlen, samecase, len_a, len_b, status;
+        samecase is a bool)."""
+        cols = self.score_pairs_arrays(a, b)
+        lists = {k: cols[k].tolist() for k in self.PAIR_KEYS}
+        lists["samecase"] = [bool(x) for x in lists["samecase"]]
+        return [{k: lists[k][i] for k in self.PAIR_KEYS} for i in range(len(a))]
+
     def query_output(self, inputs: Sequence[str], params: SearchParameters, json: bool = False,
                      output_lexmatch: bool = False, first_seqnr: int = 1) -> str:
         """One device batch + the text `analiticcl query` prints for it (anx_format_query_output: the TSV lines or JSON

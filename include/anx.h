@@ -36,7 +36,8 @@ extern "C" {
  *    anx_debug_search_lattice_stats and the test hook anx_debug_contextrule_match (models with context rules are decoded on the
  *    device: additive, results unchanged); the device-side exports with `via` (anx_batch_export_compact_via,
  *    anx_batch_gather_compact_via, anx_batch_export_topk_via: additive, the via-less exports unchanged) and the small call on
- *    multi-device models (anx_debug_small_replica_stats; results unchanged). */
+ *    multi-device models (anx_debug_small_replica_stats; results unchanged); anx_score_pairs / anx_score_pairs_packed and the
+ *    struct anx_pair_score: the measures and the score of caller-chosen string pairs (additive, nothing else changed). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -270,6 +271,33 @@ void anx_pipeline_free(anx_pipeline *);
 /* every scored pair of the batch (order unspecified within a query) */
 int anx_batch_fetch_pairs(const anx_batch *, anx_pair **out_pairs, size_t *out_n);
 void anx_pairs_free(anx_pair *);
+/* The model's measures for caller-chosen string pairs, computed on the device: for pair i the two strings go through
+ * normalize_to_alphabet (src/anahash.rs:50-80) and out[i] receives what the reference's public distance functions return for the
+ * two code sequences -- damerau_levenshtein(a, b, 255) (src/distance.rs:101-179: unrestricted, no distance bound),
+ * longest_common_substring_length (:181-205), common_prefix_length (:207-218), common_suffix_length (:220-231) -- the
+ * equality of char::is_lowercase of the two first characters (src/lib.rs:1367-1377) and the distance score of
+ * src/lib.rs:1433-1452 under the model's weights with input_length = the symbols of a.  Every measure is computed whatever its
+ * weight (the reference skips those of weight 0, src/lib.rs:1352-1377; their terms are 0 either way), so for a pair that
+ * find_variants ranks, `score` is bit for bit the dist_score of that row.  No lexicon entry is involved: the strings need not be in
+ * the vocabulary, and nothing limits their anagram or edit distance.
+ * out[i] belongs to pair i.  Per-pair status: ANX_EEMPTY when a side is empty, ANX_ELIMIT when a side has more than 255 symbols;
+ * the measures and the score of such a pair are 0.  The call itself returns ANX_OK then.
+ * Returns ANX_OK for n == 0; ANX_EINVAL for a NULL argument (or a NULL string); ANX_ENOTBUILT before anx_model_build;
+ * ANX_ENODEVICE for a model that is not resident on a device; ANX_ELIMIT for more than 4 GB of text (a packed blob, or a chunk
+ * of 2^20 pairs).  Calls of any size: the work is done in chunks of at most 2^20 pairs.  Thread-safe like the query entry points;
+ * a multi-device model runs the call on its first replica.
+ * _packed: a = the first n NUL-terminated spans of blob_a[0, len_a), b likewise; a blob holding fewer strings than n: ANX_EINVAL. */
+typedef struct anx_pair_score {
+  double score;                          /* src/lib.rs:1443-1452, input_length = symbols of a; 0 when status != ANX_OK */
+  uint16_t ld, lcs, prefixlen, suffixlen;
+  uint8_t len_a, len_b;                  /* symbols after normalize_to_alphabet */
+  uint8_t samecase;
+  int8_t status;                         /* ANX_OK, ANX_EEMPTY or ANX_ELIMIT */
+  uint32_t _pad;
+} anx_pair_score;                        /* 24 bytes */
+int anx_score_pairs(const anx_model *, const char *const *a, const char *const *b, size_t n, anx_pair_score *out);
+int anx_score_pairs_packed(const anx_model *, const char *blob_a, size_t len_a, const char *blob_b, size_t len_b, size_t n,
+                           anx_pair_score *out);
 /* Scored pairs per input (counts[n], malloc'd, release with anx_counts_free): the number of damerau_levenshtein calls the
  * reference's gather_instances makes for that input (src/lib.rs:1311-1402, one per instance of every anagram class
  * find_nearest_anahashes returned; StopAtExactMatch: of the exact class only when it exists, src/lib.rs:1164-1173).
