@@ -202,6 +202,10 @@ def lib():
         "anx_pairs_free": (None, [C.POINTER(Pair)]),
         "anx_score_pairs": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(PairScore)]),
         "anx_score_pairs_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(PairScore)]),
+        "anx_score_pairs_weighted": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(PairScore), C.POINTER(C.c_double)]),
+        "anx_score_pairs_weighted_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(PairScore), C.POINTER(C.c_double)]),
+        "anx_model_confusable_weight_text": (C.c_int, [vp, cp, cp, C.POINTER(C.c_double)]),
+        "anx_debug_pairs_conf_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
         "anx_batch_pair_counts": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_uint32))]),
         "anx_counts_free": (None, [C.POINTER(C.c_uint32)]),
         "anx_batch_export_topk": (C.c_int, [vp, vp, C.c_uint32, vp]),

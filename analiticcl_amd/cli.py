@@ -8,7 +8,8 @@ into texts like bin:561-636 and decodes them with find_all_matches.  `learn` (bi
 `--iterations` rounds of learn_variants over it (`--strict`: one string per line, find_variants; otherwise one text per line,
 find_all_matches) and writes the weighted variant list (bin:186-365; `-O`: one file per lexicon, with the reference's selection
 and field quirks).  `score` has no counterpart in the reference's binary: it reads `a<TAB>b` lines and writes the model's measures
-for each pair (score_pairs: the reference's public distance functions, src/distance.rs:101-231, and the score of src/lib.rs:1433-1452).
+for each pair (score_pairs: the reference's public distance functions, src/distance.rs:101-231, and the score of src/lib.rs:1433-1452); `--weighted` adds the pair's confusable weight under `--confusables`
+(src/lib.rs:1733-1756) and score * weight, the dist_score a ranked row carries on such a model.
 Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
@@ -123,6 +124,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight-variant-model", type=float, default=3.0)
     p.add_argument("--weight-contextrules", type=float, default=1.0)
     p.add_argument("--batch-size", type=int, default=100000, help="query mode: lines per device batch")
+    p.add_argument("--weighted", action="store_true", help="score mode: two more columns / keys, weight (the confusable weight of the pair under --confusables) and weighted_score = score * weight")
     p.add_argument("--index-cache", default=None, help="image of the built model: loaded if the file exists (lexicons are then not read), written after build() otherwise")
     p.add_argument("--device", type=int, default=None)
     p.add_argument("--single-thread", "-1", action="store_true", help="accepted for compatibility, no effect")
@@ -384,19 +386,24 @@ def run_learn(model, params, a, out) -> None:
 
 def score_tsv_line(a: str, b: str, r: dict) -> str:
     """a, b, score, ld, lcs, prefix, suffix, samecase; a pair with a status (an empty side, more than 255 symbols) keeps its two
-    strings and gets empty measure columns."""
+    strings and gets empty measure columns.  A weighted record (--weighted) has two more columns: weight, weighted_score."""
+    weighted = "weight" in r
     if r["status"]:
-        return f"{a}\t{b}\t\t\t\t\t\t"
-    return "\t".join([a, b, rust_f64(r["score"]), str(r["ld"]), str(r["lcs"]), str(r["prefixlen"]), str(r["suffixlen"]),
-                      "1" if r["samecase"] else "0"])
+        return f"{a}\t{b}\t\t\t\t\t\t" + ("\t\t" if weighted else "")
+    cols = [a, b, rust_f64(r["score"]), str(r["ld"]), str(r["lcs"]), str(r["prefixlen"]), str(r["suffixlen"]),
+            "1" if r["samecase"] else "0"]
+    if weighted:
+        cols += [rust_f64(r["weight"]), rust_f64(r["weighted_score"])]
+    return "\t".join(cols)
 
 
 def score_json_item(a: str, b: str, r: dict, seqnr: int) -> str:
     head = "    ," if seqnr > 1 else "    "
     if r["status"]:
         return '%s{ "a": "%s", "b": "%s", "status": %d }\n' % (head, _esc(a), _esc(b), r["status"])
-    return '%s{ "a": "%s", "b": "%s", "score": %s, "ld": %d, "lcs": %d, "prefix": %d, "suffix": %d, "samecase": %s }\n' % (
-        head, _esc(a), _esc(b), rust_f64(r["score"]), r["ld"], r["lcs"], r["prefixlen"], r["suffixlen"], "true" if r["samecase"] else "false")
+    tail = ', "weight": %s, "weighted_score": %s' % (rust_f64(r["weight"]), rust_f64(r["weighted_score"])) if "weight" in r else ""
+    return '%s{ "a": "%s", "b": "%s", "score": %s, "ld": %d, "lcs": %d, "prefix": %d, "suffix": %d, "samecase": %s%s }\n' % (
+        head, _esc(a), _esc(b), rust_f64(r["score"]), r["ld"], r["lcs"], r["prefixlen"], r["suffixlen"], "true" if r["samecase"] else "false", tail)
 
 
 def run_score(model, a, out) -> None:
@@ -410,7 +417,7 @@ def run_score(model, a, out) -> None:
         nonlocal seqnr
         if not pa:
             return
-        for x, y, r in zip(pa, pb, model.score_pairs(pa, pb)):
+        for x, y, r in zip(pa, pb, model.score_pairs(pa, pb, weighted=True) if a.weighted else model.score_pairs(pa, pb)):
             seqnr += 1
             out.write(score_json_item(x, y, r, seqnr) if a.json else score_tsv_line(x, y, r) + "\n")
         out.flush()

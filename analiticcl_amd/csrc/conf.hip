@@ -12,6 +12,9 @@
 //   k_conf_script  : one lane per listed row: decode the input, edit script, found_in over the patterns -> weight
 //   k_conf_apply   : early: multiply the candidate rows' scores;  late: multiply, stable re-sort (rank_cmp, src/types.rs:344-365),
 //                    cutoff, new row count
+//   k_pairs_conf_screen / k_pairs_conf_script : the same two steps for anx_score_pairs_weighted (pairs.hip): BOTH sides come from the
+//                    caller's text (the chunk's uploaded blob), no vocabulary item is involved; a pair the lane memory cannot hold gets
+//                    a NaN marker and the host weights that pair alone
 // A row the fixed-size context cannot hold (strings beyond 64 code points, arena / diff overflow) raises a flag and the host
 // repeats the batch with the host-side weighting (capi.cpp): rare, and it keeps the device path free of "approximately" results.
 #include <hip/hip_runtime.h>
@@ -392,6 +395,216 @@ __global__ __launch_bounds__(256) void k_conf_apply_late(ConfArgs a, uint32_t* _
   r_count[s] = len;
 }
 
+
+// ---- caller-chosen pairs (anx_score_pairs_weighted) -----------------------------------------------------------------------------------
+// Both sides of pair p are strings of the chunk's blob (pairs.hip): a = string p, b = string n + p, string s = blob[off[s] .. off[s + 1] - 1).
+struct PairConfArgs {
+  uint32_t n;
+  const uint8_t* blob;
+  const uint32_t* off;             // [2 n + 1]
+  const anx_pair_score* rec;       // [n] the pair kernels' records (same stream, earlier): a pair with a status is not weighted
+  double* weight;                  // [n]
+  uint32_t* need;                  // [n] the pairs that need an edit script
+  uint32_t* ctr;                   // [0] list length, [1] pairs left to the host
+  cdiff::Patterns P;
+  const uint32_t (*alpha)[2]; uint32_t nalpha;
+  uint32_t* work;                  // [blocks][CF_WORDS][64]
+  uint32_t* key;                   // [n] shape key per list entry (conf_shape_key's idea), preset to all ones behind the list
+};
+
+// The ASCII presence bits of one side from its bytes, and whether the bytes are anything but well-formed UTF-8 (a stray continuation
+// byte, a lead byte without its continuation bytes, an overlong form, 0xF8..).  The decoder of k_pairs_conf_script and of the host
+// takes the length from the lead byte alone: on such bytes it may swallow an ASCII byte into a character, or produce an ASCII
+// character from non-ASCII bytes, so bits and byte-wise prefix / suffix say nothing about the decoded string.
+__device__ inline bool pairs_side_bits(const uint8_t* __restrict__ blob, uint32_t t0, uint32_t t1, cdiff::CharSet& cs) {
+  cs.w[0] = cs.w[1] = 0;
+  cs.other = 0;
+  bool bad = false;
+  uint32_t pend = 0, lo = 0x80u;
+  for (uint32_t x = t0; x < t1; ++x) {
+    const uint32_t ch = blob[x];
+    if (ch < 64u) cs.w[0] |= 1ull << ch; else if (ch < 128u) cs.w[1] |= 1ull << (ch - 64u); else cs.other = 1;
+    if (pend) {
+      if ((ch & 0xC0u) != 0x80u || ch < lo) bad = true;
+      --pend;
+      lo = 0x80u;
+    } else if (ch >= 0x80u) {
+      if (ch >= 0xC2u && ch < 0xE0u) pend = 1;
+      else if (ch >= 0xE0u && ch < 0xF0u) { pend = 2; lo = ch == 0xE0u ? 0xA0u : 0x80u; }
+      else if (ch >= 0xF0u && ch < 0xF8u) { pend = 3; lo = ch == 0xF0u ? 0x90u : 0x80u; }
+      else bad = true;
+    }
+  }
+  return bad || pend != 0;
+}
+
+// An instruction with a multi-character or non-ASCII option, on presence bits: one of its options must have every ASCII character in
+// the set (s0, s1) and, if it has a character beyond ASCII, the string(s) must have one too (`other`).  Necessary like the bits of a
+// `simple` instruction: the option is a substring of the text it is matched against.
+__device__ inline bool pairs_opt_may(const cdiff::Patterns& P, const cdiff::FlatOp& o, uint64_t s0, uint64_t s1, bool other) {
+  for (uint32_t k = 0; k < o.nopt; ++k) {
+    const cdiff::FlatOpt opt = P.opts[o.opt_begin + k];
+    bool all = true;
+    for (uint32_t i = 0; i < opt.len && all; ++i) {
+      const uint32_t cp = P.pool[opt.off + i];
+      all = cp < 64u ? (s0 >> cp) & 1ull : cp < 128u ? (s1 >> (cp - 64u)) & 1ull : other;
+    }
+    if (all) return true;
+  }
+  return false;
+}
+
+// One lane per pair: k_conf_screen's two looks with both sides taken from bytes -- the presence bits of the whole strings against the
+// patterns' `simple` instructions, then the bits of the middles (what is left between the common ASCII prefix and suffix).  The list
+// positions of a wave are reserved with one atomic.
+__global__ __launch_bounds__(256) void k_pairs_conf_screen(PairConfArgs a) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  bool need = false;
+  uint32_t key = 0x1B7Fu;  // (the largest shape key: where a pair of malformed bytes is put)
+  if (p < a.n && a.rec[p].status == 0) {
+    const uint32_t a0 = a.off[p], a1 = a.off[p + 1u] - 1u, b0 = a.off[a.n + p], b1 = a.off[a.n + p + 1u] - 1u;
+    cdiff::CharSet ins, cs;
+    const bool bad_a = pairs_side_bits(a.blob, a0, a1, ins), bad_b = pairs_side_bits(a.blob, b0, b1, cs);
+    const bool forced = bad_a || bad_b;  // malformed bytes: the script kernel decides
+    need = forced;
+    for (uint32_t j = 0; j < a.P.nconf && !need; ++j) {
+      const cdiff::FlatConf& cf = a.P.conf[j];
+      bool may = true;
+      for (uint32_t o_ = 0; o_ < cf.nops && may; ++o_) {
+        const cdiff::FlatOp& o = a.P.ops[cf.op_begin + o_];
+        const bool tail = cf.strictend && o_ == cf.nops - 1 && o.op != '=';
+        if (o.simple && !tail) {
+          uint64_t h0 = o.bits[0], h1 = o.bits[1];
+          if (o.op != '+') { h0 &= ins.w[0]; h1 &= ins.w[1]; }
+          if (o.op != '-') { h0 &= cs.w[0]; h1 &= cs.w[1]; }
+          if (!(h0 | h1)) may = false;
+        } else if (!o.simple) {
+          uint64_t s0 = ~0ull, s1 = ~0ull;
+          bool other = true;
+          if (o.op != '+') { s0 &= ins.w[0]; s1 &= ins.w[1]; other = other && ins.other; }
+          if (o.op != '-') { s0 &= cs.w[0]; s1 &= cs.w[1]; other = other && cs.other; }
+          may = pairs_opt_may(a.P, o, s0, s1, other);
+        }
+      }
+      need = may;
+    }
+    if (need && !forced) {  // the middles (see k_conf_screen): prefix and suffix on bytes, stopping at the first non-ASCII byte
+      const uint32_t na = a1 - a0, nb = b1 - b0, nmin = na < nb ? na : nb;
+      uint32_t pre = 0;
+      while (pre < nmin) {
+        const uint32_t x = a.blob[a0 + pre];
+        if (x >= 128u || x != a.blob[b0 + pre]) break;
+        ++pre;
+      }
+      uint32_t sfx = 0;
+      while (sfx < nmin - pre) {
+        const uint32_t x = a.blob[a1 - 1u - sfx];
+        if (x >= 128u || x != a.blob[b1 - 1u - sfx]) break;
+        ++sfx;
+      }
+      {  // the shape of the script as k_conf_key sees it: middle lengths, prefix / suffix flags, then the length
+        const uint32_t ma = na - pre - sfx, mb = nb - pre - sfx;
+        key = ((ma < 6u ? ma : 6u) << 5) | ((mb < 6u ? mb : 6u) << 2) | (pre ? 2u : 0u) | (sfx ? 1u : 0u);
+        key = key << 5 | (na < 31u ? na : 31u);
+      }
+      uint64_t im0 = 0, im1 = 0, cm0 = 0, cm1 = 0;
+      bool imo = false, cmo = false;  // (prefix and suffix stop at the first non-ASCII byte: those are all in the middles)
+      for (uint32_t x = pre; x < na - sfx; ++x) {
+        const uint32_t ch = a.blob[a0 + x];
+        if (ch < 64u) im0 |= 1ull << ch; else if (ch < 128u) im1 |= 1ull << (ch - 64u); else imo = true;
+      }
+      for (uint32_t x = pre; x < nb - sfx; ++x) {
+        const uint32_t ch = a.blob[b0 + x];
+        if (ch < 64u) cm0 |= 1ull << ch; else if (ch < 128u) cm1 |= 1ull << (ch - 64u); else cmo = true;
+      }
+      need = false;
+      for (uint32_t j = 0; j < a.P.nconf && !need; ++j) {
+        const cdiff::FlatConf& cf = a.P.conf[j];
+        bool may = true;
+        for (uint32_t o_ = 0; o_ < cf.nops && may; ++o_) {
+          const cdiff::FlatOp& o = a.P.ops[cf.op_begin + o_];
+          if (!o.simple) {
+            may = o.op == '-' ? pairs_opt_may(a.P, o, im0, im1, imo) : o.op == '+' ? pairs_opt_may(a.P, o, cm0, cm1, cmo)
+                              : pairs_opt_may(a.P, o, ins.w[0] & cs.w[0], ins.w[1] & cs.w[1], ins.other && cs.other);
+            continue;
+          }
+          uint64_t h0 = o.bits[0], h1 = o.bits[1];
+          if (o.op == '-') { h0 &= im0; h1 &= im1; }
+          else if (o.op == '+') { h0 &= cm0; h1 &= cm1; }
+          else { h0 &= ins.w[0] & cs.w[0]; h1 &= ins.w[1] & cs.w[1]; }
+          if (!(h0 | h1)) may = false;
+        }
+        need = may;
+      }
+    }
+  }
+  if (p < a.n) a.weight[p] = 1.0;
+  // every lane is still here: one reservation per wave
+  const unsigned long long bal = __ballot(need);
+  if (!bal) return;  // (wave-uniform)
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t first = 0;
+  if (lane == 0u) first = atomicAdd(&a.ctr[0], (uint32_t)__popcll(bal));
+  first = (uint32_t)__shfl((int)first, 0);
+  if (need) {
+    const uint32_t pos = first + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    a.need[pos] = p;
+    a.key[pos] = key;
+  }
+}
+
+// UTF-8 -> scalar values into the lane memory at word `dst`, exactly as the host's utf8_decode_at (host_model.cpp): the length comes
+// from the lead byte alone (a sequence the string is too short for, a stray continuation byte and 0xF8.. are one byte that decodes
+// to itself) -- the host function is this kernel's fallback, so the two must read any bytes alike.  false: more than CF_MAXCP code points
+__device__ inline bool pairs_conf_decode(const cdiff::Ctx& c, const uint8_t* __restrict__ text, uint32_t t0, uint32_t t1, uint32_t dst, uint32_t* n_out) {
+  uint32_t n = 0;
+  for (uint32_t p = t0; p < t1;) {
+    const uint32_t b0 = text[p];
+    uint32_t len = b0 < 0x80u ? 1u : (b0 >> 5) == 0x6u ? 2u : (b0 >> 4) == 0xEu ? 3u : (b0 >> 3) == 0x1Eu ? 4u : 1u;
+    if (len > t1 - p) len = 1u;
+    uint32_t cp = b0;
+    if (len == 2u) cp = ((b0 & 0x1Fu) << 6) | (text[p + 1] & 0x3Fu);
+    else if (len == 3u) cp = ((b0 & 0x0Fu) << 12) | ((text[p + 1] & 0x3Fu) << 6) | (text[p + 2] & 0x3Fu);
+    else if (len == 4u) cp = ((b0 & 0x07u) << 18) | ((text[p + 1] & 0x3Fu) << 12) | ((text[p + 2] & 0x3Fu) << 6) | (text[p + 3] & 0x3Fu);
+    if (n >= CF_MAXCP) return false;
+    DC::W(c, dst + n++) = cp;
+    p += len;
+  }
+  *n_out = n;
+  return true;
+}
+
+// One lane per listed pair, a fixed grid that strides over the list (the working set is the grid's, not the list's): both sides into
+// the lane memory, then confusables_core.hpp's confusable_weight with both presence sets.  What the lane memory cannot hold (a side
+// above CF_MAXCP code points; arena, diff, diagonal or frame overflow) gets a NaN: the host weights that pair alone.
+__global__ __launch_bounds__(CF_THREADS) void k_pairs_conf_script(PairConfArgs a) {
+  const uint32_t n = min(a.ctr[0], a.n);
+  cdiff::Ctx c;
+  c.mem = a.work + (size_t)blockIdx.x * CF_WORDS * 64u + threadIdx.x * CF_G;
+  c.arena_off = CF_ARENA_OFF; c.arena_cap = CF_ARENA; c.arena_used = 0;
+  c.d_off = CF_D_OFF; c.d_cap = CF_DIFFS; c.nd = 0;
+  c.v_off = CF_V_OFF; c.v_cap = CF_V;
+  c.f_off = CF_F_OFF; c.frame_cap = CF_FRAMES;
+  c.alpha = a.alpha; c.nalpha = a.nalpha;
+  c.overflow = false;
+  for (uint32_t k = blockIdx.x * CF_THREADS + threadIdx.x; k < n; k += gridDim.x * CF_THREADS) {
+    const uint32_t p = a.need[k];
+    uint32_t na = 0, nb = 0;
+    double w = 1.0;
+    bool ok = pairs_conf_decode(c, a.blob, a.off[p], a.off[p + 1u] - 1u, CF_IN_OFF, &na) &&
+              pairs_conf_decode(c, a.blob, a.off[a.n + p], a.off[a.n + p + 1u] - 1u, CF_CAND_OFF, &nb);
+    if (ok) {
+      const cdiff::View in = cdiff::mk(CF_IN_OFF, na), cand = cdiff::mk(CF_CAND_OFF, nb);
+      ok = DC::confusable_weight(c, a.P, in, DC::charset_of(c, in), cand, DC::charset_of(c, cand), &w);
+    }
+    if (!ok) {
+      atomicAdd(&a.ctr[1], 1u);
+      w = __longlong_as_double(0x7FF8000000000000ll);
+    }
+    a.weight[p] = w;
+  }
+}
+
 // ---- host driver ----------------------------------------------------------------------------------------------------------
 namespace {
 std::mutex g_conf_mu;
@@ -413,8 +626,9 @@ void conf_free(DeviceConf* dc) {
 }
 
 // The replica's copy of the pattern tables and of the vocabulary (code points + presence bits): built on first use, rebuilt when
-// patterns or vocabulary items were added since.
-static int conf_ensure(const HostModel& m, const DeviceLexicon* dl, std::string& err) {
+// patterns or vocabulary items were added since.  vocab = false (caller-chosen pairs: both sides are the caller's text): the
+// vocabulary copy is left as it is.
+static int conf_ensure(const HostModel& m, const DeviceLexicon* dl, std::string& err, bool vocab = true) {
   std::lock_guard<std::mutex> g(g_conf_mu);
   DeviceConf*& dc = dl->dconf;
   if (!dc) { dc = new DeviceConf(); dc->device = dl->device; }
@@ -427,7 +641,7 @@ static int conf_ensure(const HostModel& m, const DeviceLexicon* dl, std::string&
     dc->nconf = (uint32_t)t.conf.size();
     dc->built_patterns = m.confusables.size();
   }
-  if (dc->built_vocab != m.decoder.size() || !dc->v_cs) {
+  if (vocab && (dc->built_vocab != m.decoder.size() || !dc->v_cs)) {
     const uint32_t *pool, *off;
     const void* cs;
     size_t npool, n;
@@ -547,6 +761,51 @@ int conf_launch_small(const HostModel& m, const DeviceLexicon* dl, hipStream_t s
   hipLaunchKernelGGL(k_conf_script, dim3(blocks), dim3(CF_THREADS), 0, st, a);
   if (r.early) hipLaunchKernelGGL(k_conf_apply_early, dim3((r.row_cap + 255u) / 256u), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_conf_apply_late, dim3((r.nq + 255u) / 256u), dim3(256), 0, st, a, r_count);
+  HIP_TRY(hipGetLastError());
+  return ANX_OK;
+}
+
+// ---- caller-chosen pairs ------------------------------------------------------------------------------------------------------------
+size_t conf_pairs_sort_tmp_bytes(uint32_t n) {
+  size_t bytes = 0;
+  uint32_t* nil = nullptr;
+  (void)rocprim::radix_sort_pairs(nullptr, bytes, nil, nil, nil, nil, (size_t)n, 0u, 13u, (hipStream_t)0);
+  return bytes;
+}
+// Enqueues the weighting of a chunk's pairs on `st`, behind the pair kernels that wrote r.rec: r.weight[p] = 1.0, the product of the
+// matching patterns' weights, or NaN (the host weights that pair).  r.ctr (16 bytes) is cleared here.
+int conf_launch_pairs(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, const PairConfRun& r, std::string& err) {
+  const int rc = conf_ensure(m, dl, err, false);
+  if (rc) return rc;
+  const DeviceConf* dc = dl->dconf;
+  PairConfArgs a;
+  a.n = r.n; a.blob = r.blob; a.off = r.off; a.rec = r.rec; a.weight = r.weight; a.need = r.need; a.ctr = r.ctr;
+  a.P.conf = dc->conf; a.P.nconf = dc->nconf; a.P.ops = dc->ops; a.P.opts = dc->opts; a.P.pool = dc->pool;
+  a.alpha = dc->alpha; a.nalpha = dc->nalpha; a.work = r.work;
+  // r.sort = [keys n | sorted keys n | sorted list n]; the keys behind the list are all ones and sort last (the list length stays on the device)
+  a.key = r.sort;
+  HIP_TRY(hipMemsetAsync(r.ctr, 0, 16, st));
+  HIP_TRY(hipMemsetAsync(r.sort, 0xFF, (size_t)r.n * sizeof(uint32_t), st));
+  const int kt = ktimer_begin("k_pairs_conf_screen", st);
+  hipLaunchKernelGGL(k_pairs_conf_screen, dim3((r.n + 255u) / 256u), dim3(256), 0, st, a);
+  ktimer_end(kt, st);
+  // the listed pairs in the order of their scripts' shapes, as the batch path sorts its rows: pairs of one route side by side in the
+  // waves of k_pairs_conf_script (measured, HISTORY.md: script + sort 0.78 ms against 0.95-0.99 ms in the screen's order)
+  bool in_order = true;
+#ifdef ANX_DEBUG_SWITCHES
+  static const bool identity = [] { const char* e = getenv("ANX_PAIRS_CONF_ORDER"); return e && strcmp(e, "identity") == 0; }();  // timing A/B, tools/score_pairs_conf_bench.py
+  in_order = !identity;
+#endif
+  if (in_order) {
+    size_t bytes = r.sort_tmp_bytes;
+    const int kto = ktimer_begin("k_pairs_conf_order", st);
+    HIP_TRY(rocprim::radix_sort_pairs(r.sort_tmp, bytes, r.sort, r.sort + r.n, r.need, r.sort + 2 * (size_t)r.n, (size_t)r.n, 0u, 13u, st));
+    ktimer_end(kto, st);
+    a.need = r.sort + 2 * (size_t)r.n;
+  }
+  const int kt2 = ktimer_begin("k_pairs_conf_script", st);
+  hipLaunchKernelGGL(k_pairs_conf_script, dim3(r.work_blocks), dim3(CF_THREADS), 0, st, a);
+  ktimer_end(kt2, st);
   HIP_TRY(hipGetLastError());
   return ANX_OK;
 }

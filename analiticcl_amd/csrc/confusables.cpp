@@ -255,6 +255,25 @@ void HostModel::confusable_weights(const char* input, size_t len, const uint64_t
   }
 }
 
+// confusable_weights with the candidate taken from text instead of the vocabulary cache: both strings decoded as they come
+// (utf8_decode_at), nothing normalised.  The fallback of the device's pair weighting (conf.hip) and what the CPU tests pin.
+double HostModel::confusable_weight_text(const char* a, size_t la, const char* b, size_t lb) const {
+  if (confusables.empty()) return 1.0;
+  const U in = to_u32(a, la), cand = to_u32(b, lb);
+  const cdiff::cp_t* inp = reinterpret_cast<const cdiff::cp_t*>(in.data());
+  const cdiff::cp_t* candp = reinterpret_cast<const cdiff::cp_t*>(cand.data());
+  const cdiff::CharSet ins = cdiff::charset_of_array(inp, (uint32_t)in.size()), cs = cdiff::charset_of_array(candp, (uint32_t)cand.size());
+  const cdiff::Patterns P = conf_patterns();
+  HostCtx& h = host_ctx();
+  double weight = 1.0;
+  for (unsigned scale = 1;; scale *= 2) {
+    h.size_for(in.size(), cand.size(), scale);
+    h.load(inp, candp);
+    if (HC::confusable_weight(h.c, P, h.in, ins, h.cand, cs, &weight)) break;
+  }
+  return weight;
+}
+
 const std::vector<uint32_t>& HostModel::vocab_gather_order() const {
   const uint64_t gen = index_generation.load(std::memory_order_acquire);
   const VocabOrder* cur = vocab_order.load(std::memory_order_acquire);

@@ -152,7 +152,14 @@ void batch_free(Batch*);
 constexpr size_t PAIRS_CHUNK = (size_t)1 << 20;
 constexpr uint32_t PAIRS_SHORT_BYTES = 16;
 struct PairSpan { const char* p; size_t len; };
-int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, anx_pair_score* out, std::string& err);
+// weight != nullptr (anx_score_pairs_weighted): weight[i] = the product of the weights of the model's confusables found in the edit
+// script of (a[i] -> b[i]) (src/lib.rs:1733-1756), 1.0 for a pair with a status or a model without confusables; `out` is what the
+// unweighted call writes.  Screen and edit script run on the device behind the pair kernels (conf.hip); a pair beyond the device's
+// fixed capacities, and every pair under ANX_CONFUSABLES=host, is weighted by HostModel::confusable_weight_text.
+int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, anx_pair_score* out, std::string& err,
+                      double* weight = nullptr);
+// running totals of the weighted calls: pairs seen, pairs the screen gave 1.0 without a script, scripts run on the device, pairs weighted on the host
+void pairs_conf_stats(uint64_t out[4]);
 
 // ---- learn mode's fold on the device (learn.hip) ------------------------------------------------------------------------------------
 struct LearnVocab;  // vocabulary hash table of one device (text hash -> id): built on first use, rebuilt when the vocabulary size or ANX_LEARN_HASH_BITS changes

@@ -99,5 +99,25 @@ __host__ __device__ inline uint32_t code_off(uint32_t off_i, uint32_t i) { retur
 // the normaliser alone over n strings on the device (encode.hip): of `e` the fields codes, meta, bits, sig, kind, cv, key, blk are used
 int pairs_encode_launch(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n, hipStream_t st,
                         std::string& err);
+// anx_score_pairs_weighted: the confusable weights of a chunk's pairs (conf.hip k_pairs_conf_screen + k_pairs_conf_script), enqueued on
+// `st` behind the pair kernels.  Both sides are read from the chunk's uploaded blob (string p and string n + p); the pattern tables are
+// the replica's (uploaded on first use, without the vocabulary copy the batch path keeps).  work: conf_small_work_bytes(work_blocks).
+constexpr uint32_t PAIRS_CF_BLOCKS = 2048;  // one-wave blocks of k_pairs_conf_script at most (it strides): 2048 x 371 KB = 760 MB for a full chunk
+struct PairConfRun {
+  uint32_t n;
+  const uint8_t* blob;
+  const uint32_t* off;             // [2 n + 1]
+  const anx_pair_score* rec;       // [n] the records the pair kernels wrote
+  double* weight;                  // [n]: 1.0, the weight, or NaN = left to the host
+  uint32_t* need;                  // [n]
+  uint32_t* ctr;                   // [4]: [0] pairs listed for a script, [1] pairs left to the host
+  uint32_t* work;
+  uint32_t work_blocks;
+  uint32_t* sort;                  // [3 n]: shape keys | sorted keys | the list in shape-key order
+  void* sort_tmp;                  // conf_pairs_sort_tmp_bytes(n)
+  size_t sort_tmp_bytes;
+};
+size_t conf_pairs_sort_tmp_bytes(uint32_t n);
+int conf_launch_pairs(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, const PairConfRun& r, std::string& err);
 
 }  // namespace anx

@@ -261,6 +261,7 @@ class HostModel {
   int add_to_confusables(const std::string& script, double weight, std::string& err);
   int read_confusablelist(const std::string& path, std::string& err);
   double confusable_weight(const std::string& input, uint64_t candidate) const;
+  double confusable_weight_text(const char* a, size_t la, const char* b, size_t lb) const;  // the candidate from text: any two strings
   // the same for the n ranked rows of one input (ids[k] -> out[k]): the input is decoded once, the vocabulary texts come from a
   // decoded copy built on first use
   void confusable_weights(const char* input, size_t len, const uint64_t* ids, size_t n, double* out) const;

@@ -22,13 +22,19 @@
 // LCS is the longest run of equal symbols along a diagonal; prefix / suffix the first mismatch from either end.  The score restates
 // score_finish (kernels_score.hpp) term by term: same association, x / L from DeviceLexicon::quot where score_finish takes it there,
 // no FMA contraction (-ffp-contract=off).
+// anx_score_pairs_weighted adds the confusable weight of every pair (src/lib.rs:1733-1756): the kernels are conf.hip's
+// (conf_launch_pairs), enqueued here behind the pair kernels on the chunk's uploaded blob; this file owns their buffers, the second
+// download, and the host's share (pairs the device marks NaN; every pair under ANX_CONFUSABLES=host).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "engine_internal.h"
@@ -318,9 +324,39 @@ struct PairScratch {  // pool blocks and pinned host blocks released together, a
     encoder_stream_release(device, st);
   }
 };
+std::atomic<uint64_t> g_cf_seen{0}, g_cf_screened{0}, g_cf_scripts{0}, g_cf_host{0};
+
+// weight[i] on the host for the pairs `pick` selects: HostModel::confusable_weight_text, on up to 16 threads when there are many
+template <typename Pick>
+uint64_t weight_on_host(const HostModel& m, const PairSpan* a, const PairSpan* b, size_t n, double* weight, Pick pick) {
+  std::vector<uint32_t> todo;
+  for (size_t i = 0; i < n; ++i)
+    if (pick(i)) todo.push_back((uint32_t)i);
+  auto work = [&](size_t lo, size_t hi) {
+    for (size_t k = lo; k < hi; ++k) {
+      const uint32_t i = todo[k];
+      weight[i] = m.confusable_weight_text(a[i].p, a[i].len, b[i].p, b[i].len);
+    }
+  };
+  const size_t nt = todo.size() < 4096 ? 1 : std::min<size_t>(16, std::max(1u, usable_hw_threads()));
+  if (nt <= 1) work(0, todo.size());
+  else {
+    std::vector<std::thread> th;
+    const size_t per = (todo.size() + nt - 1) / nt;
+    for (size_t t = 0; t < nt; ++t) th.emplace_back(work, std::min(todo.size(), t * per), std::min(todo.size(), (t + 1) * per));
+    for (std::thread& t : th) t.join();
+  }
+  return todo.size();
+}
 }  // namespace
 
-int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, anx_pair_score* out, std::string& err) {
+void pairs_conf_stats(uint64_t out[4]) {
+  out[0] = g_cf_seen.load(std::memory_order_relaxed); out[1] = g_cf_screened.load(std::memory_order_relaxed);
+  out[2] = g_cf_scripts.load(std::memory_order_relaxed); out[3] = g_cf_host.load(std::memory_order_relaxed);
+}
+
+int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, anx_pair_score* out, std::string& err,
+                      double* weight) {
   if (n == 0) return ANX_OK;
   if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
   if (n > PAIRS_CHUNK) { err = "score_pairs_chunk: more than 2^20 pairs"; return ANX_EINVAL; }
@@ -372,6 +408,31 @@ int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpa
     return rc;
   anx_pair_score* h_out = static_cast<anx_pair_score*>(sc.pinned(n * sizeof(anx_pair_score)));
   if (!h_out) { err = "out of host memory"; return ANX_EINVAL; }
+  // ---- confusable weights: on the device unless the model has no list, the switch says host, or the working set finds no room ----
+  const bool weigh = weight && !m.confusables.empty();
+  bool on_device = weigh && !switches().confusables_host;
+  PairConfRun cr{};
+  double* h_w = nullptr;  // [n] weights | 16 bytes of counters
+  if (on_device) {
+    cr.work_blocks = std::min<uint32_t>(PAIRS_CF_BLOCKS, (uint32_t)((n + 63) / 64));
+    void* wk = nullptr;
+    if (pool_malloc(&wk, conf_small_work_bytes(cr.work_blocks)) != hipSuccess) {
+      (void)hipGetLastError();
+      on_device = false;  // (same weights from the host)
+    } else {
+      sc.blocks.push_back(wk);
+      cr.work = static_cast<uint32_t*>(wk);
+      char* tmp = nullptr;
+      cr.sort_tmp_bytes = conf_pairs_sort_tmp_bytes((uint32_t)n);
+      if ((rc = sc.get(&cr.weight, n + 2, err)) || (rc = sc.get(&cr.need, n, err)) || (rc = sc.get(&cr.sort, 3 * n, err)) ||
+          (rc = sc.get(&tmp, cr.sort_tmp_bytes, err)))
+        return rc;
+      cr.sort_tmp = tmp;
+      cr.ctr = reinterpret_cast<uint32_t*>(cr.weight + n);
+      h_w = static_cast<double*>(sc.pinned((n + 2) * sizeof(double)));
+      if (!h_w) { err = "out of host memory"; return ANX_EINVAL; }
+    }
+  }
   HIP_TRY(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, st));
   const uint32_t* d_off = reinterpret_cast<const uint32_t*>(d_in);
   const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_in + o_idx);
@@ -394,9 +455,31 @@ int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpa
     ktimer_end(kt, st);
   }
   HIP_TRY(hipGetLastError());
+  if (on_device) {
+    cr.n = (uint32_t)n; cr.blob = reinterpret_cast<const uint8_t*>(d_in + o_blob); cr.off = d_off; cr.rec = d_out;
+    if ((rc = conf_launch_pairs(m, dl, st, cr, err))) return rc;
+  }
   HIP_TRY(hipMemcpyAsync(h_out, d_out, n * sizeof(anx_pair_score), hipMemcpyDeviceToHost, st));
+  if (on_device) HIP_TRY(hipMemcpyAsync(h_w, cr.weight, (n + 2) * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   memcpy(out, h_out, n * sizeof(anx_pair_score));
+  if (!weight) return ANX_OK;
+  g_cf_seen.fetch_add(n, std::memory_order_relaxed);
+  if (!weigh) {
+    std::fill(weight, weight + n, 1.0);
+  } else if (on_device) {
+    memcpy(weight, h_w, n * sizeof(double));
+    uint32_t ctr[4];
+    memcpy(ctr, h_w + n, sizeof(ctr));
+    const uint64_t listed = std::min<uint64_t>(ctr[0], n);
+    const uint64_t fell = ctr[1] ? weight_on_host(m, a, b, n, weight, [&](size_t i) { return std::isnan(weight[i]); }) : 0;
+    g_cf_screened.fetch_add(n - listed, std::memory_order_relaxed);
+    g_cf_scripts.fetch_add(listed - std::min(listed, fell), std::memory_order_relaxed);
+    g_cf_host.fetch_add(fell, std::memory_order_relaxed);
+  } else {
+    std::fill(weight, weight + n, 1.0);
+    g_cf_host.fetch_add(weight_on_host(m, a, b, n, weight, [&](size_t i) { return out[i].status == 0; }), std::memory_order_relaxed);
+  }
   return ANX_OK;
 }
 

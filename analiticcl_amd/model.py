@@ -615,12 +615,15 @@ class VariantModel:
     # -- caller-chosen pairs ----------------------------------------------------------------------------
     PAIR_KEYS = ("score", "ld", "lcs", "prefixlen", "suffixlen", "samecase", "len_a", "len_b", "status")
 
-    def score_pairs_arrays(self, a: Sequence[str], b: Sequence[str], packed: bool = True) -> dict:
+    def score_pairs_arrays(self, a: Sequence[str], b: Sequence[str], packed: bool = True, weighted: bool = False) -> dict:
         """anx_score_pairs: the model's measures for the pairs (a[i], b[i]) as numpy columns -- score (f64; the dist_score
         find_variants would give the pair, input = a[i]), ld (unrestricted Damerau-Levenshtein, no distance bound), lcs, prefixlen,
         suffixlen (u16), len_a, len_b (symbols), samecase (u8) and status (i8: 0, ANX_EEMPTY for an empty side, ANX_ELIMIT beyond 255
         symbols; score, ld, lcs, prefixlen, suffixlen and samecase of such a pair are 0, len_a / len_b hold the symbols of a side that
-        could be normalised and 0 otherwise).  packed = False: the pointer form of the call instead of the packed one."""
+        could be normalised and 0 otherwise).  packed = False: the pointer form of the call instead of the packed one.
+        weighted = True (anx_score_pairs_weighted): one more column, weight (f64) -- compute_confusable_weight(a[i], b[i]) under the
+        model's confusable list, 1.0 without one and for a pair with a status; score * weight is the dist_score of the row
+        find_variants ranks on such a model.  The other columns do not change."""
         import numpy as np
         n = len(a)
         if len(b) != n:
@@ -630,23 +633,54 @@ class VariantModel:
         assert dt.itemsize == C.sizeof(L.PairScore)
         out = np.zeros(max(n, 1), dtype=dt)
         optr = out.ctypes.data_as(C.POINTER(L.PairScore))
+        weight = np.ones(max(n, 1), dtype=np.float64) if weighted else None
+        wptr = weight.ctypes.data_as(C.POINTER(C.c_double)) if weighted else None
         if packed:
             ba, bb = _pack(a), _pack(b)
-            L.check(L.lib().anx_score_pairs_packed(self.h, ba, len(ba), bb, len(bb), n, optr))
+            if weighted:
+                L.check(L.lib().anx_score_pairs_weighted_packed(self.h, ba, len(ba), bb, len(bb), n, optr, wptr))
+            else:
+                L.check(L.lib().anx_score_pairs_packed(self.h, ba, len(ba), bb, len(bb), n, optr))
         else:
             aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in a])
             ab = (C.c_char_p * max(n, 1))(*[_b(t) for t in b])
-            L.check(L.lib().anx_score_pairs(self.h, aa, ab, n, optr))
+            if weighted:
+                L.check(L.lib().anx_score_pairs_weighted(self.h, aa, ab, n, optr, wptr))
+            else:
+                L.check(L.lib().anx_score_pairs(self.h, aa, ab, n, optr))
         out = out[:n]
-        return {k: out[k].copy() for k in self.PAIR_KEYS}
+        cols = {k: out[k].copy() for k in self.PAIR_KEYS}
+        if weighted:
+            cols["weight"] = weight[:n]
+        return cols
 
-    def score_pairs(self, a: Sequence[str], b: Sequence[str]) -> List[dict]:
+    def score_pairs(self, a: Sequence[str], b: Sequence[str], weighted: bool = False) -> List[dict]:
         """score_pairs_arrays as one dict per pair (keys: score, ld, lcs, prefixlen, suffixlen, samecase, len_a, len_b, status;
-        samecase is a bool)."""
-        cols = self.score_pairs_arrays(a, b)
+        samecase is a bool).  weighted = True adds weight and weighted_score = score * weight (one f64 multiply: the dist_score
+        of the ranked row on a model with confusables)."""
+        cols = self.score_pairs_arrays(a, b, weighted=weighted)
         lists = {k: cols[k].tolist() for k in self.PAIR_KEYS}
         lists["samecase"] = [bool(x) for x in lists["samecase"]]
-        return [{k: lists[k][i] for k in self.PAIR_KEYS} for i in range(len(a))]
+        keys = self.PAIR_KEYS
+        if weighted:
+            lists["weight"] = cols["weight"].tolist()
+            lists["weighted_score"] = (cols["score"] * cols["weight"]).tolist()
+            keys = keys + ("weight", "weighted_score")
+        return [{k: lists[k][i] for k in keys} for i in range(len(a))]
+
+    def confusable_weight_text(self, a: str, b: str) -> float:
+        """anx_model_confusable_weight_text: compute_confusable_weight (src/lib.rs:1733-1756) of two strings on the host -- the
+        product of the weights of the confusable patterns found in the edit script a -> b.  Needs no device and no build()."""
+        w = C.c_double(1.0)
+        L.check(L.lib().anx_model_confusable_weight_text(self.h, _b(a), _b(b), C.byref(w)))
+        return w.value
+
+    @staticmethod
+    def pairs_conf_stats() -> dict:
+        """anx_debug_pairs_conf_stats: running totals of the weighted pair calls."""
+        out = (C.c_uint64 * 4)()
+        L.check(L.lib().anx_debug_pairs_conf_stats(out))
+        return {"pairs": int(out[0]), "screened": int(out[1]), "device_scripts": int(out[2]), "host_pairs": int(out[3])}
 
     def query_output(self, inputs: Sequence[str], params: SearchParameters, json: bool = False,
                      output_lexmatch: bool = False, first_seqnr: int = 1) -> str:

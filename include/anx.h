@@ -37,7 +37,9 @@ extern "C" {
  *    device: additive, results unchanged); the device-side exports with `via` (anx_batch_export_compact_via,
  *    anx_batch_gather_compact_via, anx_batch_export_topk_via: additive, the via-less exports unchanged) and the small call on
  *    multi-device models (anx_debug_small_replica_stats; results unchanged); anx_score_pairs / anx_score_pairs_packed and the
- *    struct anx_pair_score: the measures and the score of caller-chosen string pairs (additive, nothing else changed). */
+ *    struct anx_pair_score: the measures and the score of caller-chosen string pairs (additive, nothing else changed);
+ *    anx_score_pairs_weighted / _packed, anx_model_confusable_weight_text and anx_debug_pairs_conf_stats: the confusable weight of
+ *    such pairs (additive). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -298,6 +300,31 @@ typedef struct anx_pair_score {
 int anx_score_pairs(const anx_model *, const char *const *a, const char *const *b, size_t n, anx_pair_score *out);
 int anx_score_pairs_packed(const anx_model *, const char *blob_a, size_t len_a, const char *blob_b, size_t len_b, size_t n,
                            anx_pair_score *out);
+/* The same call with the confusable weight of every pair.  On a model with a confusable list the reference multiplies every ranked
+ * row's dist_score by compute_confusable_weight(input, candidate) (src/lib.rs:1656-1663, 1733-1756; early mode :1505-1508, late
+ * :1591-1595), so `score` alone is NOT the dist_score of a ranked row there: score * weight[i] (one double multiply) is, in late
+ * and in early mode.  weight[i] = the product, in list order, of the weights of the model's confusables that are found_in
+ * (src/confusables.rs:47-127) shortest_edit_script(a_i, b_i); both RAW strings are decoded as Unicode scalar values (a byte that
+ * starts no complete sequence decodes to itself), nothing is normalised to the alphabet.  It is 1.0 on a model without confusables
+ * and for a pair whose record has a status.  out[] is byte for byte what anx_score_pairs writes for the same pairs: `score` stays
+ * unweighted.  Screen and edit script run on the device behind the pair kernels, on the text the call uploaded anyway; a pair the
+ * device's fixed capacities cannot hold (a side above 64 code points, a very long script) is weighted on the host, that pair alone.
+ * Device memory of a weighted call on a model with a list, per caller and chunk, on top of anx_score_pairs': 24 bytes per pair and
+ * the script kernel's working set of 371 KB per 64 pairs of the chunk, at most 760 MB (a chunk of 2^17 pairs or more).  A call
+ * that finds no room for the working set weights its chunk on the host (same weights; anx_debug_pairs_conf_stats out[3] counts them).
+ * Argument checks, chunking, statuses, thread-safety and the choice of replica are those of anx_score_pairs; weight == NULL:
+ * ANX_EINVAL. */
+int anx_score_pairs_weighted(const anx_model *, const char *const *a, const char *const *b, size_t n, anx_pair_score *out,
+                             double *weight);
+int anx_score_pairs_weighted_packed(const anx_model *, const char *blob_a, size_t len_a, const char *blob_b, size_t len_b, size_t n,
+                                    anx_pair_score *out, double *weight);
+/* compute_confusable_weight (src/lib.rs:1733-1756) of two strings on the host: anx_model_confusable_weight with the candidate taken
+ * from text instead of the vocabulary.  Needs no device and no anx_model_build.  1.0 on a model without confusables. */
+int anx_model_confusable_weight_text(const anx_model *, const char *a_utf8, const char *b_utf8, double *out_weight);
+/* Running totals of the weighted calls: out[0] = pairs seen, out[1] = pairs the device screen gave weight 1 without an edit script,
+ * out[2] = edit scripts run on the device, out[3] = pairs weighted on the host (beyond the device's capacities, or every scorable
+ * pair under ANX_CONFUSABLES=host). */
+int anx_debug_pairs_conf_stats(uint64_t out[4]);
 /* Scored pairs per input (counts[n], malloc'd, release with anx_counts_free): the number of damerau_levenshtein calls the
  * reference's gather_instances makes for that input (src/lib.rs:1311-1402, one per instance of every anagram class
  * find_nearest_anahashes returned; StopAtExactMatch: of the exact class only when it exists, src/lib.rs:1164-1173).
