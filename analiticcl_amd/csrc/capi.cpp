@@ -810,15 +810,7 @@ size_t count_nul(const char* p, size_t len) {
   return c;
 }
 
-// body(lo, hi, t) over [0, n) on up to 16 host threads (one for small n)
-void parallel_ranges(size_t n, const std::function<void(size_t, size_t, unsigned)>& body, unsigned* used = nullptr) {
-  unsigned T = n < (1u << 16) ? 1u : std::max(1u, std::min(16u, anx::usable_hw_threads()));
-  if (used) *used = T;
-  if (T == 1) { body(0, n, 0); return; }
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < T; ++t) th.emplace_back(body, n * t / T, n * (t + 1) / T, t);
-  for (auto& x : th) x.join();
-}
+using anx::parallel_ranges;
 // offsets of the first n NUL-terminated spans of blob (n + 1 values), found by several threads: every thread takes a byte range that
 // starts at a string start, counts its strings, then writes their offsets behind the strings of the ranges before it
 bool packed_offsets_mt(const char* blob, size_t len, size_t n, std::vector<uint32_t>& off) {

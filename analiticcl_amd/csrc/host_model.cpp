@@ -3,6 +3,9 @@
 #include "adjacency.h"
 
 #include <sched.h>
+#if defined(__SSE2__)
+#include <emmintrin.h>
+#endif
 
 #include <thread>
 
@@ -11,6 +14,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <numeric>
 #include <sstream>
 
@@ -546,6 +550,7 @@ const SwitchDef kSwitches[] = {
     {"ANX_HINTS", [](Switches& s, const char* v) { s.hints = flag01(v, 1); }},
     {"ANX_ADJ_MB", [](Switches& s, const char* v) { const long x = v ? atol(v) : 0; s.adj_budget_mb = x > 0 ? x : 16384; }},
     {"ANX_SIG_GROUPS", [](Switches& s, const char* v) { const int x = v ? atoi(v) : 0; s.sig_groups = x >= 1 && x <= 8 ? x : 0; }},
+    {"ANX_SIG_SEARCH", [](Switches& s, const char* v) { s.sig_search = flag01(v, 1); }},
     {"ANX_PREFILTER", [](Switches& s, const char* v) { s.prefilter = flag01(v, 1); }},
     {"ANX_SCORE_FAST", [](Switches& s, const char* v) { s.score_fast = flag01(v, 1); }},
     {"ANX_FS_SPLIT", [](Switches& s, const char* v) { s.fs_split = flag01(v, 1); }},
@@ -622,6 +627,259 @@ uint64_t signature_of(const uint8_t* cv, size_t n, const std::vector<uint8_t>& s
   return s;
 }
 
+// body(lo, hi, t) over [0, n) on up to 16 host threads (one below min_n)
+void parallel_ranges(size_t n, const std::function<void(size_t, size_t, unsigned)>& body, unsigned* used, size_t min_n) {
+  unsigned T = n < min_n ? 1u : (unsigned)std::min<size_t>(std::max<size_t>(n, 1), std::max(1u, std::min(16u, usable_hw_threads())));
+  if (used) *used = T;
+  if (T == 1) { body(0, n, 0); return; }
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < T; ++t) th.emplace_back(body, n * t / T, n * (t + 1) / T, t);
+  for (auto& x : th) x.join();
+}
+
+// ---- search for the signature's symbol groups ------------------------------------------------------
+// Any partition of the count-vector slots into groups is exact (summing is a contraction of L1); the partition only decides how
+// many lexicon records fall inside a query's signature ball, which is what the scan's class tests, the adjacency lists and their
+// chunks scale with.  Starting from the frequency-balanced greedy partition, three sweeps of "move one slot to another group"
+// minimise
+//     sum over proxies p, sampled classes c with |len(c) - len(p)| <= 3 and L1(sig(p), sig(c)) <= 3 of entries(c)
+// where the proxies are a fixed-stride sample of the lexicon's own classes (no queries exist at build time; proxies with the 0-2
+// edits of synth.make_queries carried over to held-out queries no better) and the classes another fixed-stride
+// sample.  A sweep estimates every candidate at once from the pairs within L1 <= 5 (exact for count differences of one; further
+// pairs cannot enter the ball by such a step); the best candidates are then evaluated exactly and only a strict improvement of the
+// exact objective is accepted.  Everything is integer arithmetic over fixed samples: the same lexicon gives the same groups on any
+// number of threads.
+namespace {
+constexpr int kSearchBall = 3;         // the flagship's anagram distance and length window
+constexpr int kSearchNear = 5;         // pairs a sweep looks at: a count difference of one changes the distance by at most 2
+constexpr size_t kSearchProxies = 128;
+constexpr size_t kSearchClasses = 2048;
+constexpr int kSearchMaxSweeps = 3;
+constexpr int kSearchTries = 3;        // candidates of a sweep that get an exact evaluation
+constexpr uint64_t kSearchStepPpm = 5000;  // smallest relative improvement that is accepted
+
+struct SigClassView { const uint8_t* cv; int len; uint32_t weight; };
+
+inline int sad8(uint64_t a, uint64_t b) {
+#if defined(__SSE2__)
+  return _mm_cvtsi128_si32(_mm_sad_epu8(_mm_cvtsi64_si128((long long)a), _mm_cvtsi64_si128((long long)b)));
+#else
+  int s = 0;
+  for (int i = 0; i < 8; ++i) s += std::abs((int)((a >> (8 * i)) & 0xFF) - (int)((b >> (8 * i)) & 0xFF));
+  return s;
+#endif
+}
+void on_threads(unsigned T, const std::function<void(unsigned)>& body) {  // body(t) for t < T, a thread each
+  parallel_ranges(T, [&](size_t lo, size_t, unsigned) { body((unsigned)lo); }, nullptr, 2);
+}
+struct GroupSearch {
+  struct Near { uint32_t c; uint16_t p; uint8_t l1; };
+  struct Cand { int64_t delta; int s, g; };  // move slot s to group g
+  int A = 0, G = 0;
+  unsigned T = 1;
+  size_t n = 0, P = 0;
+  std::vector<uint8_t> cv, pcv;  // [n][A], [P][A] counts of the active slots
+  std::vector<uint32_t> w;
+  std::vector<int> plen;
+  uint32_t len_begin[258];       // first sampled class of at least this length (the sample is sorted by length)
+  std::vector<uint64_t> sig, psig;
+
+  void sign(const std::vector<uint8_t>& grp) {
+    auto one = [&](const uint8_t* v) {
+      uint8_t g[8] = {};
+      for (int i = 0; i < A; ++i) g[grp[(size_t)i]] = (uint8_t)(g[grp[(size_t)i]] + v[i]);
+      uint64_t s = 0;
+      for (int i = 0; i < 8; ++i) s |= (uint64_t)g[i] << (8 * i);
+      return s;
+    };
+    on_threads(T, [&](unsigned t) {
+      for (size_t c = n * t / T; c < n * (t + 1) / T; ++c) sig[c] = one(&cv[c * (size_t)A]);
+    });
+    for (size_t p = 0; p < P; ++p) psig[p] = one(&pcv[p * (size_t)A]);
+  }
+  // the objective; near[t] = the pairs within `reach` of thread t's proxies
+  uint64_t evaluate(const std::vector<uint8_t>& grp, std::vector<std::vector<Near>>& near, int reach) {
+    sign(grp);
+    std::vector<uint64_t> part(T, 0);
+    near.resize(T);
+    on_threads(T, [&](unsigned t) {
+      uint64_t sum = 0;
+      std::vector<Near>& nr = near[t];
+      nr.clear();
+      for (size_t p = t; p < P; p += T) {
+        const uint64_t ps = psig[p];
+        const uint32_t lo = len_begin[std::max(0, plen[p] - kSearchBall)], hi = len_begin[std::min(256, plen[p] + kSearchBall) + 1];
+        for (uint32_t c = lo; c < hi; ++c) {
+          const int l1 = sad8(ps, sig[c]);
+          if (l1 <= reach) {
+            if (l1 <= kSearchBall) sum += w[c];
+            nr.push_back({c, (uint16_t)p, (uint8_t)l1});
+          }
+        }
+      }
+      part[t] = sum;
+    });
+    return std::accumulate(part.begin(), part.end(), (uint64_t)0);
+  }
+  // estimated change of the objective for every move, best first; sig / psig / near are those of grp
+  std::vector<Cand> sweep(const std::vector<uint8_t>& grp, const std::vector<std::vector<Near>>& near) {
+    const size_t ncand = (size_t)A * (size_t)G;
+    std::vector<std::vector<int64_t>> acc(T, std::vector<int64_t>(ncand, 0));
+    std::vector<Near> all;  // the threads' lists differ in size by far (short proxies have many neighbours): even slices of all of them
+    for (const std::vector<Near>& v : near) all.insert(all.end(), v.begin(), v.end());
+    on_threads(T, [&](unsigned th) {
+      int64_t* out = acc[th].data();
+      std::vector<int> d((size_t)A), nz;
+      for (size_t k = all.size() * th / T; k < all.size() * (th + 1) / T; ++k) {
+        const Near& e = all[k];
+        const uint8_t* a = &pcv[(size_t)e.p * (size_t)A];
+        const uint8_t* b = &cv[(size_t)e.c * (size_t)A];
+        nz.clear();
+        for (int i = 0; i < A; ++i) {
+          d[(size_t)i] = (int)a[i] - (int)b[i];
+          if (d[(size_t)i]) nz.push_back(i);
+        }
+        if (nz.empty()) continue;
+        int D[8], aD[8];
+        for (int g = 0; g < 8; ++g) aD[g] = std::abs(D[g] = (int)((psig[e.p] >> (8 * g)) & 0xFF) - (int)((sig[e.c] >> (8 * g)) & 0xFF));
+        const int l1 = e.l1;
+        const bool in0 = l1 <= kSearchBall;
+        const int64_t wt = in0 ? -(int64_t)w[e.c] : (int64_t)w[e.c];
+        unsigned posm = 0, negm = 0;
+        for (int g = 0; g < G; ++g) { posm |= (unsigned)(D[g] > 0) << g; negm |= (unsigned)(D[g] < 0) << g; }
+        // the groups gb for which y leaving group ga for gb changes whether the pair is in the ball
+        auto flips = [&](int ga, int y) {
+          const int base = l1 - aD[ga] + std::abs(D[ga] - y);
+          unsigned m = 0;
+          if (y == 1 || y == -1) {  // the distance goes down by one where y shrinks the group's difference, else up
+            const unsigned red = y > 0 ? negm : posm;
+            m = in0 ? (base >= kSearchBall ? ~red : 0u) | (base >= kSearchBall + 2 ? red : 0u)
+                    : (base <= kSearchBall + 1 ? red : 0u) | (base <= kSearchBall - 1 ? ~red : 0u);
+          } else {
+            for (int gb = 0; gb < G; ++gb) m |= (unsigned)((base - aD[gb] + std::abs(D[gb] + y) <= kSearchBall) != in0) << gb;
+          }
+          return m & ((1u << G) - 1u) & ~(1u << ga);
+        };
+        for (int s : nz) {
+          const int ga = grp[(size_t)s], ds = d[(size_t)s];
+          for (unsigned r = flips(ga, ds); r; r &= r - 1) out[(size_t)s * (size_t)G + (size_t)__builtin_ctz(r)] += wt;
+        }
+      }
+    });
+    std::vector<Cand> out;
+    for (size_t i = 0; i < ncand; ++i) {
+      int64_t v = 0;
+      for (unsigned t = 0; t < T; ++t) v += acc[t][i];
+      if (v >= 0) continue;
+      out.push_back({v, (int)(i / (size_t)G), (int)(i % (size_t)G)});
+    }
+    std::stable_sort(out.begin(), out.end(), [](const Cand& x, const Cand& y) { return x.delta < y.delta; });
+    return out;
+  }
+};
+
+// sym_group: the greedy partition on entry, the searched one on return
+void search_sig_groups(const std::vector<SigClassView>& cls, const std::vector<uint64_t>& slot_freq, int ngroups, std::vector<uint8_t>& sym_group) {
+  std::vector<uint32_t> active;
+  for (size_t sl = 0; sl < slot_freq.size(); ++sl)
+    if (slot_freq[sl]) active.push_back((uint32_t)sl);
+  if (active.size() < 2 || ngroups < 2 || cls.size() < 2) return;
+  GroupSearch s;
+  s.A = (int)active.size();
+  s.G = ngroups;
+  s.T = std::max(1u, std::min(16u, usable_hw_threads()));
+  if (cls.size() < 4096) s.T = 1;
+  const size_t A = active.size();
+  {  // the class sample, by length
+    const size_t n = std::min(cls.size(), kSearchClasses);
+    std::vector<uint32_t> pick(n);
+    for (size_t i = 0; i < n; ++i) pick[i] = (uint32_t)(i * cls.size() / n);
+    std::stable_sort(pick.begin(), pick.end(), [&](uint32_t a, uint32_t b) { return cls[a].len < cls[b].len; });
+    s.n = n;
+    s.cv.resize(n * A);
+    s.w.resize(n);
+    s.sig.resize(n);
+    for (uint32_t& x : s.len_begin) x = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const SigClassView& c = cls[pick[i]];
+      for (size_t k = 0; k < A; ++k) s.cv[i * A + k] = c.cv[active[k]];
+      s.w[i] = c.weight;
+      s.len_begin[std::min(c.len, 256) + 1]++;
+    }
+    for (int l = 0; l < 257; ++l) s.len_begin[l + 1] += s.len_begin[l];
+  }
+  {  // the proxies
+    const size_t P = std::min(cls.size(), kSearchProxies);
+    s.P = P;
+    s.pcv.resize(P * A);
+    s.plen.resize(P);
+    s.psig.resize(P);
+    for (size_t j = 0; j < P; ++j) {
+      const SigClassView& c = cls[(j * cls.size() + cls.size() / 2) / P];
+      uint8_t* v = &s.pcv[j * A];
+      int len = 0;
+      for (size_t k = 0; k < A; ++k) len += v[k] = c.cv[active[k]];
+      s.plen[j] = len;
+    }
+  }
+  std::vector<uint8_t> grp(A);
+  for (size_t k = 0; k < A; ++k) grp[k] = sym_group[active[k]];
+  // Group sums of EVERY class (the byte-wise ball arithmetic of the kernels holds up to 120): a step may not push any of them
+  // beyond the largest one of the greedy partition.
+  const size_t N = cls.size();
+  std::vector<uint8_t> allcv(N * A), gsum(N * 8, 0);
+  on_threads(s.T, [&](unsigned t) {
+    for (size_t c = N * t / s.T; c < N * (t + 1) / s.T; ++c)
+      for (size_t k = 0; k < A; ++k) gsum[c * 8 + grp[k]] = (uint8_t)(gsum[c * 8 + grp[k]] + (allcv[c * A + k] = cls[c].cv[active[k]]));
+  });
+  const int max_sum = *std::max_element(gsum.begin(), gsum.end());
+  auto fits = [&](const GroupSearch::Cand& m) {
+    for (size_t c = 0; c < N; ++c)
+      if ((int)gsum[c * 8 + (size_t)m.g] + (int)allcv[c * A + (size_t)m.s] > max_sum) return false;
+    return true;
+  };
+  // A sweep may accept several moves as long as they touch different groups (a move's estimate only depends on its own two
+  // groups and the distance); each is accepted on its exact value against the running objective.
+  std::vector<std::vector<GroupSearch::Near>> near, near2;
+  uint64_t cur = s.evaluate(grp, near, kSearchNear);
+  for (int sweeps = 0; sweeps < kSearchMaxSweeps && cur > 0; ++sweeps) {
+    const std::vector<GroupSearch::Cand> cands = s.sweep(grp, near);
+    unsigned touched = 0;
+    int tries = 0;
+    bool stale = false;
+    const uint64_t before = cur;
+    for (const GroupSearch::Cand& c : cands) {
+      if (tries >= kSearchTries) break;
+      const int ga = grp[(size_t)c.s];
+      const unsigned mask = 1u << ga | 1u << c.g;
+      if (touched & mask) continue;
+      if ((uint64_t)-c.delta * 1000000ull <= cur * kSearchStepPpm) break;  // the estimates are close: the rest is below the step
+      if (std::count(grp.begin(), grp.end(), (uint8_t)ga) < 2 || !fits(c)) continue;  // every group in use stays in use
+      std::vector<uint8_t> g2 = grp;
+      g2[(size_t)c.s] = (uint8_t)c.g;
+      ++tries;
+      const uint64_t v = s.evaluate(g2, near2, kSearchNear);
+      stale = true;
+      if (v < cur && (cur - v) * 1000000ull > cur * kSearchStepPpm) {
+        for (size_t k = 0; k < N; ++k) {
+          const uint8_t y = allcv[k * A + (size_t)c.s];
+          gsum[k * 8 + (size_t)ga] = (uint8_t)(gsum[k * 8 + (size_t)ga] - y);
+          gsum[k * 8 + (size_t)c.g] = (uint8_t)(gsum[k * 8 + (size_t)c.g] + y);
+        }
+        grp.swap(g2);
+        near.swap(near2);
+        cur = v;
+        touched |= mask;
+        stale = false;
+      }
+    }
+    if (cur == before) break;
+    if (stale) cur = s.evaluate(grp, near, kSearchNear);  // the signatures and pairs of grp again
+  }
+  for (size_t k = 0; k < A; ++k) sym_group[active[k]] = grp[k];
+}
+}  // namespace
+
 int HostModel::build_index(std::string& err) {
   const int A = alphabet.size();
   lex = LexiconImage();
@@ -658,7 +916,7 @@ int HostModel::build_index(std::string& err) {
     }
     tmp[it->second].ids.push_back((uint32_t)id);  // ascending id order (src/lib.rs:215-219)
   }
-  {  // symbol groups of the signature: slots by decreasing total count, each to the currently lightest group
+  {  // symbol groups of the signature: slots by decreasing total count, each to the currently lightest group; then the search
     std::vector<uint64_t> slot_freq(cvbytes, 0);
     for (const Tmp& t : tmp)
       for (size_t sl = 0; sl < cvbytes; ++sl) slot_freq[sl] += (uint8_t)t.cv[sl];
@@ -674,6 +932,11 @@ int HostModel::build_index(std::string& err) {
         if (weight[i] < weight[g]) g = i;
       lex.sym_group[sl] = (uint8_t)g;
       weight[g] += slot_freq[sl];
+    }
+    if (switches().sig_search) {
+      std::vector<SigClassView> view(tmp.size());
+      for (size_t i = 0; i < tmp.size(); ++i) view[i] = {reinterpret_cast<const uint8_t*>(tmp[i].cv.data()), tmp[i].charcount, (uint32_t)tmp[i].ids.size()};
+      search_sig_groups(view, slot_freq, ngroups, lex.sym_group);
     }
   }
   std::vector<uint64_t> sig(tmp.size());

@@ -2,6 +2,7 @@
 // SoA lexicon image that is uploaded to HBM.  Mirrors the reference's VariantModel for the query path
 // (/root/reference/src/lib.rs:50-245, 369-407, 519-568, 900-967; src/anahash.rs:16-80; src/vocab.rs).
 #pragma once
+#include <functional>
 #include <cstdint>
 #include <atomic>
 #include <memory>
@@ -62,6 +63,8 @@ std::string trim_whitespace(const std::string& s);  // str::trim()
 // Host threads worth starting: hardware threads, limited by the affinity mask and the cgroup CPU quota (the GPU boxes
 // show 256 hardware threads and grant 16 CPUs).
 unsigned usable_hw_threads();
+// body(lo, hi, t) over [0, n) on up to 16 host threads, t = the range's thread (one thread, and one call, below min_n); used: how many
+void parallel_ranges(size_t n, const std::function<void(size_t, size_t, unsigned)>& body, unsigned* used = nullptr, size_t min_n = 1u << 16);
 
 // A/B, test and tuning switches.  Read ONCE from the environment (variable names in the comments) when the library is first
 // used -- a variable set later has no effect -- and changed at run time only through anx_debug_set_switch (tests, tools).  None of
@@ -76,6 +79,7 @@ struct Switches {
   int adj_closure = 2;       // ANX_ADJ_CLOSURE=0..2: lists for the signatures within this distance of a lexicon signature (models put on a device afterwards)
   long adj_budget_mb = 16384; // ANX_ADJ_MB: most HBM the lists may take per replica (16 GB of 288: every list of the closure of a 1 M-entry lexicon, 12.8 GB)
   int sig_groups = 0;        // ANX_SIG_GROUPS=1..8: signature groups of a model built afterwards (0 = default)
+  int sig_search = 1;        // ANX_SIG_SEARCH=0: the frequency-balanced greedy symbol groups as they are, no search (A/B reference; models built afterwards)
   int prefilter = 1;         // ANX_PREFILTER=0: no SWAR bound, every length-compatible pair goes through the DL
   int score_fast = 1;        // ANX_SCORE_FAST=0: general k_score_pairs for every pair
   int fs_planes = 1;         // ANX_FS_PLANES=0: byte rows instead of symbol planes in k_filter_score (A/B; alphabets beyond 61 classes always take the rows)
@@ -167,8 +171,9 @@ struct LexiconImage {
                                         // then vocab id (src/lib.rs:1327-1332); last key of the ranking order
   std::vector<uint8_t> rows;            // token rows padded to 16-byte multiples with 0xFF
   std::vector<BigVal> cls_value;        // anagram value per class (host only)
-  // Signature pruning of the window scan: the count-vector slots are partitioned into kSigGroups groups of about
-  // equal total frequency; sig(c) = per-group symbol counts (one byte each).  L1(sig(q), sig(c)) <= L1(cv_q, cv_c),
+  // Signature pruning of the window scan: the count-vector slots are partitioned into kSigGroups groups -- of about equal total
+  // frequency first, then moved and swapped by build_index's search for the partition that leaves the fewest lexicon records in a
+  // query's ball (ANX_SIG_SEARCH=0: no search); sig(c) = per-group symbol counts (one byte each).  L1(sig(q), sig(c)) <= L1(cv_q, cv_c),
   // so a class whose signature is further than k from the query's cannot be within anagram distance k.  Classes are
   // stored in (charcount, signature, anagram value) order: all classes of one signature are one contiguous run.
   std::vector<uint8_t> sym_group;       // [nplanes*4] group of each count-vector slot
