@@ -49,7 +49,7 @@ namespace anx {
 // ------------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------------
-// layout of the pinned block a run reads back into (Batch::h_read), in uint32 words
+// layout of a run's control block on the device (Batch::ctl) and of the pinned block it is read back into (Batch::h_read), in uint32 words
 enum { HR_RCTR = 0, HR_SCTR = SCAN_REGIONS * RC_STRIDE, HR_LCTR = 2 * SCAN_REGIONS * RC_STRIDE, HR_CTR = 5 * SCAN_REGIONS * RC_STRIDE,
        HR_TOTAL_SURV = HR_CTR + CTR_N, HR_TOTAL_RESULTS = HR_TOTAL_SURV + 1, HR_CONF = HR_TOTAL_RESULTS + 1 /* 2 words */, HR_N = HR_CONF + 2 };
 constexpr size_t HR_COLD_OFF = (HR_N * sizeof(uint32_t) + 63) & ~(size_t)63;  // byte offset of the FsCold staging copy in Batch::h_read
@@ -999,10 +999,12 @@ static int encode_tail(Batch* b, std::string& err) {
   const size_t nq = b->nq;
   int rc;
   const size_t nblk = (nq + SCAN_TILE - 1) / SCAN_TILE + 2;
-  if ((rc = dalloc(&b->counters, CTR_N, err)) || (rc = dalloc(&b->rctr, SCAN_REGIONS * RC_STRIDE, err)) || (rc = dalloc(&b->sctr, SCAN_REGIONS * RC_STRIDE, err)) || (rc = dalloc(&b->lctr, 3 * SCAN_REGIONS * RC_STRIDE, err)) || (rc = dalloc(&b->qexpand, nq, err)) || (rc = dalloc(&b->qsurv, nq, err)) ||
-      (rc = dalloc(&b->soff, nq + 1, err)) || (rc = dalloc(&b->qcur, nq, err)) || (rc = dalloc(&b->qmaxfreq, nq, err)) ||
-      (rc = dalloc(&b->scan_tmp, nblk, err)) || (rc = dalloc(&b->r_count, nq, err)) || (rc = dalloc(&b->r_off, nq + 1, err)))
+  if ((rc = dalloc(&b->ctl, HR_N, err)) || (rc = dalloc(&b->qsurv, 3 * nq, err)) ||
+      (rc = dalloc(&b->soff, nq + 1, err)) || (rc = dalloc(&b->qcur, nq, err)) ||
+      (rc = dalloc(&b->scan_tmp, nblk, err)) || (rc = dalloc(&b->r_count, nq, err)))
     return rc;
+  b->rctr = b->ctl + HR_RCTR; b->sctr = b->ctl + HR_SCTR; b->lctr = b->ctl + HR_LCTR; b->counters = b->ctl + HR_CTR;
+  b->qmaxfreq = b->qsurv + nq; b->qexpand = b->qsurv + 2 * nq;  // (qexpand last: only models with variant lists clear and use it)
   return shell_acquire(b, err);
 }
 
@@ -1088,12 +1090,14 @@ Batch* batch_encode(const HostModel& m, const DeviceLexicon* dl, const char* con
   return batch_encode_spans(m, dl, blob.data(), blob.size(), off.data(), n, p, err, code, keep_text);
 }
 
-static int exclusive_scan(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* tmp, hipStream_t st, uint32_t* maxout = nullptr, uint32_t* copy = nullptr) {
+// tmp: nb + 2 words.  Up to SCAN_FUSED_BLOCKS blocks (2 M elements) k_scan_add adds up the block totals in front of it itself: two launches
+static int exclusive_scan(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* tmp, hipStream_t st, uint32_t* copy = nullptr) {
   const uint32_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
   if (nb == 0) return hipMemsetAsync(out, 0, sizeof(uint32_t), st) == hipSuccess ? 0 : -1;
-  hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(SCAN_THREADS), 0, st, in, n, out, tmp, maxout);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, tmp, nb);
-  hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(SCAN_THREADS), 0, st, out, n, tmp, nb, copy);
+  const int fused = nb <= SCAN_FUSED_BLOCKS ? 1 : 0;
+  hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(SCAN_THREADS), 0, st, in, n, out, tmp);
+  if (!fused) hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, tmp, nb);
+  hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(SCAN_THREADS), 0, st, out, n, tmp, nb, copy, fused);
   return 0;
 }
 
@@ -1360,8 +1364,8 @@ int Run::setup() {
 
 int Run::scan() {
   int rc;
-  HIP_TRY(hipMemsetAsync(b->counters, 0, CTR_N * sizeof(uint32_t), st));
-  HIP_TRY(hipMemsetAsync(b->rctr, 0, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), st));
+  // the whole control block: the scan's counters, and already those of the later stages (nothing touches them before Run::score)
+  HIP_TRY(hipMemsetAsync(b->ctl, 0, HR_N * sizeof(uint32_t), st));
   if (b->ntiles == 0) { HIP_TRY(hipEventRecord(b->ev_scan0, st)); HIP_TRY(hipEventRecord(b->ev[5], st)); }
   if (b->ntiles) {
     ScanArgs A = scan_args_of(dl);
@@ -1390,7 +1394,6 @@ int Run::scan() {
     const uint32_t nsad = b->n_sad_tiles, nbits = A.ntiles - nsad, nadj = std::min(b->n_adj_tiles, nbits);
     with_nplanes(dl->nplanes, [&](auto np) { launch_scan<decltype(np)::value>(A, nadj, nbits, nsad, st, b->ev_scan0, b->ev[5]); });
   }
-  HIP_TRY(hipMemcpyAsync(b->h_read + HR_RCTR, b->rctr, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipEventRecord(b->ev[1], st));
   b->n_raw = (uint32_t)(SCAN_REGIONS << b->region_shift);  // slot space (regions are sparse)
   return ANX_OK;
@@ -1398,9 +1401,7 @@ int Run::scan() {
 
 int Run::score() {
   int rc;
-  HIP_TRY(hipMemsetAsync(b->qsurv, 0, nq * sizeof(uint32_t), st));
-  HIP_TRY(hipMemsetAsync(b->qmaxfreq, 0, nq * sizeof(uint32_t), st));
-  if (dl->any_variants) HIP_TRY(hipMemsetAsync(b->qexpand, 0, nq * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(b->qsurv, 0, (dl->any_variants ? 3 : 2) * (size_t)nq * sizeof(uint32_t), st));  // qsurv, qmaxfreq (, qexpand)
   ScorePlan plan = score_plan_of(m, dl, b->params.score_threshold, b->qw, b->dmax);
   ScoreArgs& sa = plan.sa;
 #ifdef ANX_DEBUG_SWITCHES
@@ -1422,8 +1423,6 @@ int Run::score() {
   // without the inline DL (d > 3) every length-compatible pair goes to the general list; else the prefilter passes ~1/3
   if (need_lists && (rc = ensure_slot_lists(b, b->prev_list_fill ? (size_t)b->prev_list_fill + (b->prev_list_fill >> 3) + 256 : (fastD ? (size_t)fill_cap / 2 : (size_t)fill_cap) / cap_div() + 256, err)))
     return rc;
-  HIP_TRY(hipMemsetAsync(b->sctr, 0, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), st));
-  HIP_TRY(hipMemsetAsync(b->lctr, 0, 3 * SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), st));
   const SlotLists sl = slot_lists_of(b->list8, b->listg, b->listw, b->lctr, (uint32_t)b->list_cap);
   const PairArgs pa = pair_args_of(dl, b->raw, b->q_meta, b->q_rows, b->q_rec, b->p_score, b->p_meta, b->qmaxfreq, b->qsurv, b->qexpand);
   FilterArgs fa;
@@ -1461,7 +1460,7 @@ int Run::compact_rank() {
   // confusables weighted on the device, late mode: k_rank crops without the cutoff, conf.hip re-ranks and cuts off afterwards
   // (the small call takes no confusables: always the caller's cutoff)
   const RankArgs ra = rank_args_of(m, dl, b->params, b->conf_mode == 1 ? 0.0 : b->params.cutoff_threshold);
-  exclusive_scan(b->qsurv, nq, b->soff, b->scan_tmp, st, nullptr, b->qcur);  // + qcur = soff: the cursors of the compaction
+  exclusive_scan(b->qsurv, nq, b->soff, b->scan_tmp, st, b->qcur);  // + qcur = soff: the cursors of the compaction
   if (dl->any_variants) {
     // variant lists: a survivor expands to several rows; the row buffer and the grid of k_compact come from the survivor
     // counts, so this (rare) configuration keeps one host round trip in the middle of the run
@@ -1497,20 +1496,18 @@ int Run::compact_rank() {
   launch_rank(ra, st, nq, b->soff, b->c_rows, b->qmaxfreq, b->qexpand, b->t_key, b->r_rows, b->r_count, dl->any_variants ? 0xFFFFFFFFu : row_cap, b->counters + CTR_OVERFLOW,
               dl->any_variants ? SegRows{nullptr, 0u, nullptr} : SegRows{so.seg, so.seg_cap, dl->ent_rec});
   if (b->conf_mode == 1 && (rc = conf_launch(m, dl, b, st, false, row_cap, err))) return rc;
-  exclusive_scan(b->r_count, nq, b->r_off, b->scan_tmp, st, b->counters + CTR_MAXROWS);
+  // what batch_finish wants of the ranked lists (their total and the longest), and the words of other buffers the read-back takes along
+  // (after an overflow k_rank has returned early and r_count is stale: batch_finish repeats the run and uses none of this)
+  hipLaunchKernelGGL(k_run_summary, dim3((nq + SCAN_THREADS * SUMMARY_ITEMS - 1) / (SCAN_THREADS * SUMMARY_ITEMS)), dim3(SCAN_THREADS), 0, st, b->r_count, nq, b->ctl,
+                     (uint32_t)HR_TOTAL_RESULTS, (uint32_t)(HR_CTR + CTR_MAXROWS), b->soff + nq, (uint32_t)HR_TOTAL_SURV,
+                     (b->conf_mode && b->cf_ctr) ? b->cf_ctr : nullptr, (uint32_t)HR_CONF);
   HIP_TRY(hipEventRecord(b->ev[4], st));
   return ANX_OK;
 }
 
 // the fills and totals batch_finish reads, behind everything else of the run
 int Run::readback() {
-  HIP_TRY(hipMemcpyAsync(b->h_read + HR_SCTR, b->sctr, SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(b->h_read + HR_LCTR, b->lctr, 3 * SCAN_REGIONS * RC_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(b->h_read + HR_CTR, b->counters, CTR_N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(b->h_read + HR_TOTAL_SURV, b->soff + nq, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(b->h_read + HR_TOTAL_RESULTS, b->r_off + nq, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  b->h_read[HR_CONF] = b->h_read[HR_CONF + 1] = 0;
-  if (b->conf_mode && b->cf_ctr) HIP_TRY(hipMemcpyAsync(b->h_read + HR_CONF, b->cf_ctr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(b->h_read, b->ctl, HR_N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));  // (HR_CONF: zero unless k_run_summary copied cf_ctr)
   HIP_TRY(hipEventRecord(b->ev_done, st));
   HIP_TRY(hipGetLastError());
   return ANX_OK;
@@ -2011,10 +2008,10 @@ void batch_free(Batch* b) {
   // before the blocks go back to the pool, where another batch / thread / stream may take them at once
   if (b->async_pending) (void)hipStreamSynchronize(reinterpret_cast<hipStream_t>(b->async_stream));
   if (b->launched) (void)hipEventSynchronize(b->ev_done);  // a run enqueued with batch_run_async and never waited for
-  for (void* p : {(void*)b->q_cv, (void*)b->q_bits, (void*)b->q_rows, (void*)b->q_rec, (void*)b->q_meta, (void*)b->q_orig, (void*)b->d_tiles, (void*)b->rctr, (void*)b->sctr, (void*)b->surv,
-                  (void*)b->counters, (void*)b->qexact, (void*)b->qsurv, (void*)b->soff, (void*)b->qcur,
-                  (void*)b->qmaxfreq, (void*)b->d_cold, (void*)b->qpairs, (void*)b->x_cnt, (void*)b->x_tmp, (void*)b->scan_tmp, (void*)b->raw, (void*)b->p_score, (void*)b->p_meta, (void*)b->list8, (void*)b->listg, (void*)b->listw, (void*)b->lctr,
-                  (void*)b->c_rows, (void*)b->sseg, (void*)b->qexpand, (void*)b->r_rows, (void*)b->t_key, (void*)b->r_count, (void*)b->r_off,
+  for (void* p : {(void*)b->q_cv, (void*)b->q_bits, (void*)b->q_rows, (void*)b->q_rec, (void*)b->q_meta, (void*)b->q_orig, (void*)b->d_tiles, (void*)b->ctl, (void*)b->surv,
+                  (void*)b->qexact, (void*)b->qsurv, (void*)b->soff, (void*)b->qcur,
+                  (void*)b->d_cold, (void*)b->qpairs, (void*)b->x_cnt, (void*)b->x_tmp, (void*)b->scan_tmp, (void*)b->raw, (void*)b->p_score, (void*)b->p_meta, (void*)b->list8, (void*)b->listg, (void*)b->listw,
+                  (void*)b->c_rows, (void*)b->sseg, (void*)b->r_rows, (void*)b->t_key, (void*)b->r_count,
                   (void*)b->d_text, (void*)b->d_textoff, (void*)b->cf_weight, (void*)b->cf_need, (void*)b->cf_ctr, b->cf_work, (void*)b->cf_sort, b->cf_sort_tmp})
     if (p) pool_free(p);
   shell_release(b);  // events + pinned read-back block: to the device's pool (hipHostFree / hipEventDestroy here would wait for the device)
@@ -2080,6 +2077,28 @@ int debug_band_bound(int device, const uint8_t* q_rows, const uint8_t* c_rows, c
   if ((e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(out, dout, n, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e);
   cleanup();
   return rc;
+}
+
+// ---- test hook: the run's prefix sum alone (anx_debug_exclusive_scan; tests/test_gpu_prefix_sum.py) -----------------------------------
+// out[0 .. n] = the exclusive prefix sum of in[0 .. n) as exclusive_scan computes it on the device (out[n] = the total), copy (may be
+// nullptr) = out[0 .. n) through the kernel's second output.
+int debug_exclusive_scan(int device, const uint32_t* in, size_t n, uint32_t* out, uint32_t* copy, std::string& err) {
+  if (n >= ((size_t)1 << 31)) { err = "prefix sum: more than 2^31 elements"; return ANX_EINVAL; }
+  HIP_TRY(hipSetDevice(device));
+  uint32_t *din = nullptr, *dout = nullptr, *dcopy = nullptr, *dtmp = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)din, (void*)dout, (void*)dcopy, (void*)dtmp}) if (p) (void)hipFree(p); };
+  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
+  hipError_t e;
+  if ((e = hipMalloc(reinterpret_cast<void**>(&din), (n + 1) * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&dout), (n + 1) * 4)) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&dcopy), (n + 1) * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&dtmp), scan_tmp_bytes(n))) != hipSuccess)
+    return fail_hip(e);
+  if (n && (e = hipMemcpy(din, in, n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e);
+  if (exclusive_scan(din, (uint32_t)n, dout, dtmp, 0, copy ? dcopy : nullptr)) return fail_hip(hipGetLastError());
+  if ((e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(out, dout, (n + 1) * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (copy && n && (e = hipMemcpy(copy, dcopy, n * 4, hipMemcpyDeviceToHost)) != hipSuccess))
+    return fail_hip(e);
+  cleanup();
+  return ANX_OK;
 }
 
 }  // namespace anx

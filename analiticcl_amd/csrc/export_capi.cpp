@@ -37,6 +37,12 @@ int check_export(const anx_batch* b) {
 }  // namespace
 
 extern "C" {
+int anx_debug_exclusive_scan(int device, const uint32_t* in, size_t n, uint32_t* out, uint32_t* copy) {
+  if (!out || (!in && n)) return anx_fail(ANX_EINVAL, "NULL argument");
+  std::string err;
+  const int rc = anx::debug_exclusive_scan(device, in, n, out, copy, err);
+  return rc ? anx_fail(rc, err) : ANX_OK;
+}
 int anx_batch_export_topk_via(const anx_batch* b, void* dst, void* via, uint32_t stride, void* stream) {
   if (int rc = check_export(b)) return rc;
   const ShardRef s = shard_of(b, 0, stream);

@@ -186,12 +186,13 @@ struct Batch {
   uint32_t* q_orig = nullptr;      // original index
   Tile* d_tiles = nullptr;
   // device: pipeline
-  uint32_t* counters = nullptr;
+  uint32_t* ctl = nullptr;         // the run's control block (engine.hip HR_*): cleared by one fill at the start of a run, read back by one copy at its end
+  uint32_t* counters = nullptr;    // (into ctl, like rctr / sctr / lctr)
   uint32_t* rctr = nullptr;        // [SCAN_REGIONS][RC_STRIDE] per-region reservation / statistics counters
   uint32_t region_shift = 0;       // log2(slots per region); raw_cap = SCAN_REGIONS << region_shift
   uint32_t region_fill[SCAN_REGIONS] = {};  // host copy of rctr[r][RC_RAW] after the last run
   uint32_t* qexact = nullptr;      // per query: its exact-anagram class, 0xFFFFFFFF = none (StopAtExactMatch; host lookup)
-  uint32_t* qsurv = nullptr;       // per query: pairs with score >= threshold
+  uint32_t* qsurv = nullptr;       // per query: pairs with score >= threshold ([3][nq] with qmaxfreq and qexpand behind it: one fill)
   uint32_t* soff = nullptr;        // nq+1, exclusive scan of qsurv
   uint32_t* qcur = nullptr;
   uint32_t* qmaxfreq = nullptr;
@@ -236,7 +237,6 @@ struct Batch {
   double* t_key = nullptr;
   size_t surv_cap = 0;
   uint32_t* r_count = nullptr;
-  uint32_t* r_off = nullptr;       // nq+1
   uint32_t n_raw = 0;
   uint64_t n_sel = 0;
   uint64_t n_pairs = 0, n_surv = 0, n_results = 0;

@@ -1,4 +1,4 @@
-// kernels_rank.hpp -- K3b+K4: survivor compaction, ranking with crop / cutoff, result packing (k_compact, k_rank, k_pack_rows), and the
+// kernels_rank.hpp -- K3b+K4: survivor compaction, ranking with crop / cutoff, result rows (k_compact, k_rank), and the
 // way off the device: k_fetch_counts + k_emit_rows<Emit> (one row kernel for the download, the compact fetch with or without `via` and the
 // compact export), k_export_topk (fixed stride)
 // Part of the single translation unit engine.hip (included inside namespace anx); gfx950 only.
@@ -683,16 +683,6 @@ __global__ __launch_bounds__(256) void k_rank(uint32_t nq, const uint32_t* __res
   }
 }
 
-// dense result rows (device) for download / gather
-__global__ __launch_bounds__(256) void k_pack_rows(uint32_t nq, const uint32_t* __restrict__ soff,
-                                                   const uint32_t* __restrict__ r_off,
-                                                   const uint32_t* __restrict__ r_count,
-                                                   const DevRow* __restrict__ r_rows, DevRow* __restrict__ out) {
-  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= nq) return;
-  const uint32_t n = r_count[q], src = soff[q], dst = r_off[q];
-  for (uint32_t i = 0; i < n; ++i) out[dst + i] = r_rows[src + i];
-}
 // download / export path: result rows in the CALLER's input order -- the counts scattered to the input indices (k_fetch_counts), an
 // exclusive scan over them, then the rows through an emitter (k_emit_rows)
 __global__ __launch_bounds__(256) void k_fetch_counts(uint32_t nq, const uint32_t* __restrict__ r_count,

@@ -482,6 +482,10 @@ int anx_debug_adjacency_device(const anx_model *, const uint64_t *sigs, size_t n
  * against the oracle's DL.  Runs on HIP device `device`. */
 int anx_debug_band_bound(int device, const uint8_t *q_rows, const uint8_t *c_rows, const uint8_t *lq, const uint8_t *lc, size_t n,
                          int d, int form, uint8_t *out_reject);
+/* Test hook: the exclusive prefix sum (u32) the run and the fetch / export paths use, on HIP device `device`: out[0 .. n] = the prefix
+ * sums of in[0 .. n) (out[n] = the total), copy (may be NULL) receives out[0 .. n) through the kernel's second output.
+ * tests/test_gpu_prefix_sum.py compares it with numpy.cumsum on both sides of the point where the two-kernel form ends. */
+int anx_debug_exclusive_scan(int device, const uint32_t *in, size_t n, uint32_t *out, uint32_t *copy);
 
 /* ---- output of `analiticcl query` --------------------------------------------------
  * The TSV lines / JSON items of output_matches_as_tsv / output_matches_as_json (src/bin/analiticcl.rs:21-187) for n
