@@ -24,6 +24,22 @@ int debug_band_bound(int device, const uint8_t* q_rows, const uint8_t* c_rows, c
                      uint8_t* out, std::string& err);
 // test hook: the run's exclusive prefix sum (engine.hip exclusive_scan) on n host values: out[0 .. n], copy[0 .. n) (may be nullptr)
 int debug_exclusive_scan(int device, const uint32_t* in, size_t n, uint32_t* out, uint32_t* copy, std::string& err);
+// test hook: k_rank alone (engine.hip debug_rank_rows) on the caller's candidate rows, no model: nq queries of counts[q] rows, back to back
+// in the physical order the caller chose.  via may be nullptr (no row has one).  seg_cap = C > 0: rows i < C of a query as SurvSeg
+// records + hook-made ent_rec, the surplus in c_rows (only any_variants == 0, position 0, no via).  out_count[nq] and out_rows (the whole
+// r_rows buffer: one 24-byte DevRow per candidate row, query q's ranked rows from the exclusive sum of counts) start as 0xFF bytes.
+struct DebugRankIn {
+  size_t nq;
+  const uint32_t *counts, *maxfreq, *qexpand;
+  const double* score;
+  const uint32_t *order, *position, *vocab, *freq, *via;
+  double cutoff_threshold;
+  uint64_t max_matches;
+  float freq_weight;
+  int have_freq, any_variants;
+  uint32_t seg_cap, row_cap, overflow;
+};
+int debug_rank_rows(int device, const DebugRankIn& in, uint32_t* out_count, void* out_rows, std::string& err);
 void kernel_timer_enable(bool on);  // also clears the totals
 bool kernel_timer_read(const char* name, double* total_ms, uint64_t* launches);  // waits for the recorded launches
 void device_pool_trim(int device);  // hands the cached scratch blocks of the device (and the pinned result buffers) back to the driver

@@ -2101,4 +2101,73 @@ int debug_exclusive_scan(int device, const uint32_t* in, size_t n, uint32_t* out
   return ANX_OK;
 }
 
+// ---- test hook: k_rank alone on hand-made candidate rows (anx_debug_rank_rows; tests/test_gpu_rank_rows.py) ---------------------------
+// soff = the exclusive sum of counts; the rows as a run lays them out (c_rows, or segments of seg_cap records + ent_rec + surplus in
+// c_rows); t_key / r_rows / r_count sized by the total whatever row_cap says, r_rows and r_count filled with 0xFF bytes; launch_rank.
+int debug_rank_rows(int device, const DebugRankIn& in, uint32_t* out_count, void* out_rows, std::string& err) {
+  const size_t nq = in.nq;
+  if (nq == 0) return ANX_OK;
+  if (nq >= ((size_t)1 << 28)) { err = "rank rows: too many queries"; return ANX_EINVAL; }
+  std::vector<uint32_t> soff(nq + 1, 0u);
+  uint64_t total64 = 0;
+  for (size_t q = 0; q < nq; ++q) { soff[q] = (uint32_t)total64; total64 += in.counts[q]; if (total64 >= (1ull << 31)) { err = "rank rows: more than 2^31 rows"; return ANX_EINVAL; } }
+  soff[nq] = (uint32_t)total64;
+  const size_t total = (size_t)total64, C = in.seg_cap;
+  for (size_t r = 0; r < total; ++r) {
+    if (in.position[r] >= (1u << 20)) { err = "rank rows: expansion position beyond 2^20"; return ANX_EINVAL; }
+    if (C && (in.position[r] != 0 || (in.via && in.via[r] != 0xFFFFFFFFu))) { err = "rank rows: segments hold rows without expansion position and via only"; return ANX_EINVAL; }
+  }
+  if (C && in.any_variants) { err = "rank rows: no segments with variant lists"; return ANX_EINVAL; }
+  if (C && nq * C >= ((size_t)1 << 31)) { err = "rank rows: segments too large"; return ANX_EINVAL; }
+  std::vector<SurvRow> rows(total ? total : 1, SurvRow{0.0, 0ull, 0u, 0u, 0xFFFFFFFFu, 0u});
+  std::vector<SurvSeg> seg(nq * C + 1, SurvSeg{0.0, 0u, 0u});  // (one spare record behind the last segment)
+  std::vector<EntRec> ent(C && total ? total : 1, EntRec{0u, 0u, 0u, 0u});
+  for (size_t q = 0; q < nq; ++q)
+    for (size_t i = 0; i < in.counts[q]; ++i) {
+      const size_t e = soff[q] + i;
+      if (i < C) {
+        seg[q * C + i] = SurvSeg{in.score[e], (uint32_t)e, 0u};
+        ent[e] = EntRec{in.vocab[e], in.freq[e], in.order[e], 0u};
+      } else {
+        rows[e - C] = SurvRow{in.score[e], (unsigned long long)in.order[e] << 20 | in.position[e], in.vocab[e], in.freq[e], in.via ? in.via[e] : 0xFFFFFFFFu, 0u};
+      }
+    }
+  HIP_TRY(hipSetDevice(device));
+  uint32_t *d_soff = nullptr, *d_maxf = nullptr, *d_qex = nullptr, *d_count = nullptr, *d_ovf = nullptr;
+  SurvRow* d_rows = nullptr;
+  SurvSeg* d_seg = nullptr;
+  EntRec* d_ent = nullptr;
+  double* d_tkey = nullptr;
+  DevRow* d_out = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)d_soff, (void*)d_maxf, (void*)d_qex, (void*)d_count, (void*)d_ovf, (void*)d_rows, (void*)d_seg, (void*)d_ent, (void*)d_tkey, (void*)d_out}) if (p) (void)hipFree(p); };
+  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
+  const size_t out_bytes = (total ? total : 1) * sizeof(DevRow);
+  hipError_t e;
+  if ((e = hipMalloc(reinterpret_cast<void**>(&d_soff), (nq + 1) * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_maxf), nq * 4)) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_qex), nq * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_count), nq * 4)) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_ovf), 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_rows), rows.size() * sizeof(SurvRow))) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_seg), seg.size() * sizeof(SurvSeg))) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_ent), ent.size() * sizeof(EntRec))) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_tkey), (total ? total : 1) * 8)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes)) != hipSuccess)
+    return fail_hip(e);
+  if ((e = hipMemcpy(d_soff, soff.data(), (nq + 1) * 4, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_maxf, in.maxfreq, nq * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d_qex, in.qexpand, nq * 4, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_ovf, &in.overflow, 4, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d_rows, rows.data(), rows.size() * sizeof(SurvRow), hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d_seg, seg.data(), seg.size() * sizeof(SurvSeg), hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d_ent, ent.data(), ent.size() * sizeof(EntRec), hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemset(d_tkey, 0, (total ? total : 1) * 8)) != hipSuccess || (e = hipMemset(d_count, 0xFF, nq * 4)) != hipSuccess || (e = hipMemset(d_out, 0xFF, out_bytes)) != hipSuccess)
+    return fail_hip(e);
+  RankArgs ra{};
+  ra.cutoff_threshold = in.cutoff_threshold;
+  ra.max_matches = in.max_matches;
+  ra.freq_weight = in.freq_weight;
+  ra.have_freq = in.have_freq;
+  ra.any_variants = in.any_variants;
+  launch_rank(ra, 0, (uint32_t)nq, d_soff, d_rows, d_maxf, d_qex, d_tkey, d_out, d_count, in.row_cap, d_ovf, C ? SegRows{d_seg, (uint32_t)C, d_ent} : SegRows{nullptr, 0u, nullptr});
+  if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(out_count, d_count, nq * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (total && (e = hipMemcpy(out_rows, d_out, total * sizeof(DevRow), hipMemcpyDeviceToHost)) != hipSuccess))
+    return fail_hip(e);
+  cleanup();
+  return ANX_OK;
+}
+
 }  // namespace anx

@@ -43,6 +43,20 @@ int anx_debug_exclusive_scan(int device, const uint32_t* in, size_t n, uint32_t*
   const int rc = anx::debug_exclusive_scan(device, in, n, out, copy, err);
   return rc ? anx_fail(rc, err) : ANX_OK;
 }
+int anx_debug_rank_rows(int device, size_t nq, const uint32_t* counts, const uint32_t* maxfreq, const uint32_t* qexpand, const double* score,
+                        const uint32_t* order, const uint32_t* position, const uint32_t* vocab, const uint32_t* freq, const uint32_t* via,
+                        double cutoff_threshold, uint64_t max_matches, float freq_weight, int have_freq, int any_variants, uint32_t seg_cap,
+                        uint32_t row_cap, uint32_t overflow, uint32_t* out_count, void* out_rows) {
+  if (nq && (!counts || !maxfreq || !qexpand || !out_count)) return anx_fail(ANX_EINVAL, "NULL argument");
+  size_t total = 0;
+  for (size_t q = 0; q < nq; ++q) total += counts[q];
+  if (total && (!score || !order || !position || !vocab || !freq || !out_rows)) return anx_fail(ANX_EINVAL, "NULL argument");
+  const anx::DebugRankIn in{nq, counts, maxfreq, qexpand, score, order, position, vocab, freq, via, cutoff_threshold, max_matches, freq_weight,
+                            have_freq ? 1 : 0, any_variants ? 1 : 0, seg_cap, row_cap, overflow};
+  std::string err;
+  const int rc = anx::debug_rank_rows(device, in, out_count, out_rows, err);
+  return rc ? anx_fail(rc, err) : ANX_OK;
+}
 int anx_batch_export_topk_via(const anx_batch* b, void* dst, void* via, uint32_t stride, void* stream) {
   if (int rc = check_export(b)) return rc;
   const ShardRef s = shard_of(b, 0, stream);

@@ -348,10 +348,12 @@ __device__ inline void rank_query_all(uint32_t q, bool valid, int gl, int gshift
 // (:1536-1589) only ever looks at rows before that point or yields a length beyond it (then the cutoff wins).
 // On config 2 the survivors per query are heavy-tailed (mean 10, 2 % above 64 carry half of sum n^2) and most of a
 // long list is below half the best score.  nloop: wave-uniform upper bound of n (ballot count must match).
-template <int G, int LCAP>
+// SrcT: the type of a kept row's source index in LDS -- 16 bits where a group only ever sees <= 32 rows, 32 bits in the 64-lane path,
+// whose lists have no bound (quickselect keeps <= LCAP rows of a list of any length, and they are fetched back by that index).
+template <int G, int LCAP, typename SrcT>
 __device__ inline void rank_query(uint32_t q, bool valid, int gl, int gshift, uint32_t nloop, double* __restrict__ s_key,
                                   unsigned long long* __restrict__ s_ord, uint32_t* __restrict__ s_freq,
-                                  uint16_t* __restrict__ s_src, double* __restrict__ s_sdist, double* __restrict__ s_sfreq,
+                                  SrcT* __restrict__ s_src, double* __restrict__ s_sdist, double* __restrict__ s_sfreq,
                                   uint32_t seg0, uint32_t n, uint32_t maxf, uint32_t qex,
                                   const SurvRow* __restrict__ c_rows, const SegRows& sr, const RankArgs& a, double* __restrict__ t_key,
                                   DevRow* __restrict__ r_rows, uint32_t* __restrict__ r_count) {
@@ -440,7 +442,7 @@ __device__ inline void rank_query(uint32_t q, bool valid, int gl, int gshift, ui
     if (keep && pos < (uint32_t)LCAP) {
       if (packed) { s_key64[pos] = rank_key1(key); s_ord[pos] = rank_key2(r.freq, r.ord); }
       else { s_key[pos] = key; s_ord[pos] = r.ord; }
-      s_freq[pos] = r.freq; s_src[pos] = (uint16_t)i;
+      s_freq[pos] = r.freq; s_src[pos] = (SrcT)i;
     }
     kept += (uint32_t)__popcll(m);
   }
@@ -600,7 +602,7 @@ __device__ inline void rank_query(uint32_t q, bool valid, int gl, int gshift, ui
 // query on config 2) the four are ranked side by side by 16 lanes each; otherwise one after the other by the whole
 // wave (lists up to RANK_LCAP rows in LDS, longer ones through t_key).  1M one-query waves were latency-bound.
 constexpr int RANK_QPW = 4;                                    // queries per wave
-constexpr int RANK_WAVE_BYTES = RANK_LCAP * 22 + 64 * 16;      // LDS per wave: keys, order keys, freqs, source rows + ranked heads
+constexpr int RANK_WAVE_BYTES = RANK_LCAP * 24 + 64 * 16;      // LDS per wave: keys, order keys, freqs, source rows (32 bits) + ranked heads
 // SIMPLE: no variant lists and freq_weight == 0 (the common model): the expansion / dedup and the weighted-score branches fold away
 template <bool SIMPLE>
 __global__ __launch_bounds__(256) void k_rank(uint32_t nq, const uint32_t* __restrict__ soff,
@@ -636,7 +638,7 @@ __global__ __launch_bounds__(256) void k_rank(uint32_t nq, const uint32_t* __res
     // per group: 16 keys (8 B), 16 order keys (8 B), 16 freqs (4 B), 16 source rows (2 B), 16 + 16 ranked heads (8 B) = 608 B
     uint8_t* gb = wl + grp * 608;
     const uint32_t ng = (uint32_t)__shfl((int)my_n, grp);
-    rank_query<16, 16>(qbase + grp, qbase + grp < nq && ng <= 16u, gl, grp * 16, 16u, reinterpret_cast<double*>(gb),
+    rank_query<16, 16, uint16_t>(qbase + grp, qbase + grp < nq && ng <= 16u, gl, grp * 16, 16u, reinterpret_cast<double*>(gb),
                        reinterpret_cast<unsigned long long*>(gb + 128), reinterpret_cast<uint32_t*>(gb + 256),
                        reinterpret_cast<uint16_t*>(gb + 320), reinterpret_cast<double*>(gb + 352), reinterpret_cast<double*>(gb + 480),
                        (uint32_t)__shfl((int)my_seg0, grp), ng, (uint32_t)__shfl((int)my_maxf, grp),
@@ -660,7 +662,7 @@ __global__ __launch_bounds__(256) void k_rank(uint32_t nq, const uint32_t* __res
       const int src = valid ? kk : 0;
       // per half: 32 keys, order keys (8 B each), freqs (4 B), source rows (2 B), 32 + 32 ranked heads (8 B) = 1216 B
       uint8_t* gb = wl + half * 1216;
-      rank_query<32, 32>(qbase + (uint32_t)src, valid, gl, half * 32, 32u, reinterpret_cast<double*>(gb),
+      rank_query<32, 32, uint16_t>(qbase + (uint32_t)src, valid, gl, half * 32, 32u, reinterpret_cast<double*>(gb),
                          reinterpret_cast<unsigned long long*>(gb + 256), reinterpret_cast<uint32_t*>(gb + 512),
                          reinterpret_cast<uint16_t*>(gb + 640), reinterpret_cast<double*>(gb + 704), reinterpret_cast<double*>(gb + 960),
                          (uint32_t)__shfl((int)my_seg0, src), (uint32_t)__shfl((int)my_n, src), (uint32_t)__shfl((int)my_maxf, src),
@@ -672,10 +674,10 @@ __global__ __launch_bounds__(256) void k_rank(uint32_t nq, const uint32_t* __res
       if (qbase + k >= nq) break;  // wave-uniform
       const uint32_t nk = (uint32_t)__builtin_amdgcn_readlane((int)my_n, k);
       if (nk <= 32u) continue;     // wave-uniform: done above
-      rank_query<64, RANK_LCAP>(qbase + k, true, lane, 0, nk, reinterpret_cast<double*>(wl),
+      rank_query<64, RANK_LCAP, uint32_t>(qbase + k, true, lane, 0, nk, reinterpret_cast<double*>(wl),
                                 reinterpret_cast<unsigned long long*>(wl + RANK_LCAP * 8),
-                                reinterpret_cast<uint32_t*>(wl + RANK_LCAP * 16), reinterpret_cast<uint16_t*>(wl + RANK_LCAP * 20),
-                                reinterpret_cast<double*>(wl + RANK_LCAP * 22), reinterpret_cast<double*>(wl + RANK_LCAP * 22 + 512),
+                                reinterpret_cast<uint32_t*>(wl + RANK_LCAP * 16), reinterpret_cast<uint32_t*>(wl + RANK_LCAP * 20),
+                                reinterpret_cast<double*>(wl + RANK_LCAP * 24), reinterpret_cast<double*>(wl + RANK_LCAP * 24 + 512),
                                 (uint32_t)__shfl((int)my_seg0, k), nk, (uint32_t)__shfl((int)my_maxf, k), (uint32_t)__shfl((int)my_qex, k),
                                 c_rows, sr, a, t_key, r_rows, r_count);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");

@@ -39,7 +39,7 @@ extern "C" {
  *    multi-device models (anx_debug_small_replica_stats; results unchanged); anx_score_pairs / anx_score_pairs_packed and the
  *    struct anx_pair_score: the measures and the score of caller-chosen string pairs (additive, nothing else changed);
  *    anx_score_pairs_weighted / _packed, anx_model_confusable_weight_text and anx_debug_pairs_conf_stats: the confusable weight of
- *    such pairs (additive). */
+ *    such pairs (additive); the test hooks anx_debug_exclusive_scan and anx_debug_rank_rows (additive). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -486,6 +486,22 @@ int anx_debug_band_bound(int device, const uint8_t *q_rows, const uint8_t *c_row
  * sums of in[0 .. n) (out[n] = the total), copy (may be NULL) receives out[0 .. n) through the kernel's second output.
  * tests/test_gpu_prefix_sum.py compares it with numpy.cumsum on both sides of the point where the two-kernel form ends. */
 int anx_debug_exclusive_scan(int device, const uint32_t *in, size_t n, uint32_t *out, uint32_t *copy);
+/* Test hook: the ranking kernel (k_rank: sort, duplicate removal, crop with its tie rule, cutoff) alone, on HIP device `device`, without
+ * a model.  nq queries of counts[q] candidate rows, all rows back to back in the physical order the caller chose: score, entry order,
+ * expansion position (< 2^20), vocab, freq (1 everywhere without have_freq), via (NULL: no row has one; UINT32_MAX = none).  maxfreq[q] /
+ * qexpand[q]: the query's largest frequency and whether one of its candidates had a variant list (read with any_variants only).
+ * seg_cap = 0: every row lies in the candidate row buffer.  seg_cap = C > 0 (only any_variants == 0, positions 0, no via): rows i < C
+ * of a query as the per-query segment records plus entry records the hook makes up, rows i >= C in the row buffer, as a run lays them
+ * out.  row_cap and overflow are the kernel's early-return inputs (it does nothing when the total exceeds row_cap or overflow != 0); the
+ * hook's buffers hold the total whatever row_cap says.  out_count[nq] and out_rows start as 0xFF bytes; out_rows is the whole ranked
+ * row buffer, one 24-byte record {uint32 vocab_id, uint32 via, double dist_score, double freq_score} per candidate row: query q's
+ * out_count[q] ranked rows start at record counts[0] + .. + counts[q - 1].  The launch is the run's own (same kernel instance choice).
+ * tests/test_gpu_rank_rows.py compares them exactly with the tail of the twin's score_and_rank (oracle/twin.py rank_tail). */
+int anx_debug_rank_rows(int device, size_t nq, const uint32_t *counts, const uint32_t *maxfreq, const uint32_t *qexpand,
+                        const double *score, const uint32_t *order, const uint32_t *position, const uint32_t *vocab,
+                        const uint32_t *freq, const uint32_t *via, double cutoff_threshold, uint64_t max_matches, float freq_weight,
+                        int have_freq, int any_variants, uint32_t seg_cap, uint32_t row_cap, uint32_t overflow, uint32_t *out_count,
+                        void *out_rows);
 
 /* ---- output of `analiticcl query` --------------------------------------------------
  * The TSV lines / JSON items of output_matches_as_tsv / output_matches_as_json (src/bin/analiticcl.rs:21-187) for n

@@ -459,6 +459,63 @@ class VariantResult:  # src/types.rs:326-365
         return (self.dist_score + (fw * self.freq_score)) / (1.0 + fw)
 
 
+def rank_tail(results: List[VariantResult], max_freq: float, has_expandable_variants: bool, max_matches: int,
+              cutoff_threshold: float, freq_weight: float, late_rescore=None) -> List[VariantResult]:
+    """The tail of score_and_rank (src/lib.rs:1521-1622) on the candidate rows in enumeration order: frequency normalisation, the
+    stable rank_results, dedup_by_key, the crop with its tie rule, the cutoff.  late_rescore(results): the late confusable weighting
+    between crop and cutoff (src/lib.rs:1591-1595), followed by a second rank_results.  Changes the rows it is given."""
+    if max_freq > 0.0:
+        for r in results:
+            r.freq_score = r.freq_score / max_freq
+    # rank_results: stable sort with rank_cmp (src/types.rs:344-365)
+    def rank_results(rs):
+        if freq_weight > 0.0:
+            rs.sort(key=lambda r: -r.score(freq_weight))
+        else:
+            rs.sort(key=lambda r: (-r.dist_score, -r.freq_score))
+    rank_results(results)
+    if has_expandable_variants:  # Vec::dedup_by_key: consecutive duplicates only (src/lib.rs:1530-1533)
+        ded = []
+        for r in results:
+            if not ded or ded[-1].vocab_id != r.vocab_id:
+                ded.append(r)
+        results = ded
+    if max_matches > 0 and len(results) > max_matches:
+        last_score = results[max_matches - 1].score(freq_weight)
+        cropped_score = results[max_matches].score(freq_weight)
+        if cropped_score < last_score:
+            del results[max_matches:]
+        else:
+            early_cutoff = 0
+            late_cutoff = 0
+            for i, r in enumerate(results):
+                if r.dist_score == cropped_score and early_cutoff == 0:
+                    early_cutoff = i
+                if r.dist_score < cropped_score:
+                    late_cutoff = i
+                    break
+            if early_cutoff > 0:
+                del results[early_cutoff + 1:]
+            elif late_cutoff > 0:
+                del results[late_cutoff + 1:]
+    if late_rescore is not None:
+        late_rescore(results)
+        rank_results(results)
+    cutoff = 0
+    bestscore = None
+    if cutoff_threshold >= 1.0:
+        for i, r in enumerate(results):
+            if bestscore is not None:
+                if r.score(freq_weight) <= bestscore / cutoff_threshold:
+                    cutoff = i
+                    break
+            else:
+                bestscore = r.score(freq_weight)
+    if cutoff > 0:
+        del results[cutoff:]
+    return results
+
+
 @dataclass
 class Distance:  # src/types.rs:289-305
     ld: int
@@ -741,56 +798,10 @@ class VariantModel:
             for r in results:
                 if r.freq_score > max_freq:
                     max_freq = r.freq_score
-        if max_freq > 0.0:
-            for r in results:
-                r.freq_score = r.freq_score / max_freq
-        # rank_results: stable sort with rank_cmp (src/types.rs:344-365)
-        def rank_results(rs):
-            if freq_weight > 0.0:
-                rs.sort(key=lambda r: -r.score(freq_weight))
-            else:
-                rs.sort(key=lambda r: (-r.dist_score, -r.freq_score))
-        rank_results(results)
-        if has_expandable_variants:  # Vec::dedup_by_key: consecutive duplicates only (src/lib.rs:1530-1533)
-            ded = []
-            for r in results:
-                if not ded or ded[-1].vocab_id != r.vocab_id:
-                    ded.append(r)
-            results = ded
-        if max_matches > 0 and len(results) > max_matches:
-            last_score = results[max_matches - 1].score(freq_weight)
-            cropped_score = results[max_matches].score(freq_weight)
-            if cropped_score < last_score:
-                del results[max_matches:]
-            else:
-                early_cutoff = 0
-                late_cutoff = 0
-                for i, r in enumerate(results):
-                    if r.dist_score == cropped_score and early_cutoff == 0:
-                        early_cutoff = i
-                    if r.dist_score < cropped_score:
-                        late_cutoff = i
-                        break
-                if early_cutoff > 0:
-                    del results[early_cutoff + 1:]
-                elif late_cutoff > 0:
-                    del results[late_cutoff + 1:]
+        late = None
         if confusables and not early:  # late rescoring, the default (src/lib.rs:1591-1595)
-            self.rescore_confusables(results, input)
-            rank_results(results)
-        cutoff = 0
-        bestscore = None
-        if cutoff_threshold >= 1.0:
-            for i, r in enumerate(results):
-                if bestscore is not None:
-                    if r.score(freq_weight) <= bestscore / cutoff_threshold:
-                        cutoff = i
-                        break
-                else:
-                    bestscore = r.score(freq_weight)
-        if cutoff > 0:
-            del results[cutoff:]
-        return results
+            late = lambda rs: self.rescore_confusables(rs, input)
+        return rank_tail(results, max_freq, has_expandable_variants, max_matches, cutoff_threshold, freq_weight, late)
 
     def find_variants(self, text: str, params: SearchParameters, trace: Optional[dict] = None
                       ) -> List[VariantResult]:
