@@ -75,6 +75,18 @@ class PairScore(C.Structure):  # anx_pair_score, 24 bytes
                 ("status", C.c_int8), ("_pad", C.c_uint32)]
 
 
+class GoldEval(C.Structure):  # anx_gold_eval, 32 bytes
+    _fields_ = [("gold_vocab_id", C.c_uint32), ("rank", C.c_int32), ("n_results", C.c_uint32), ("top_vocab_id", C.c_uint32),
+                ("gold_score", C.c_double), ("ld", C.c_uint16), ("k", C.c_uint8), ("d", C.c_uint8), ("status", C.c_int8),
+                ("reason", C.c_uint8), ("_pad", C.c_uint16)]
+
+
+# anx.h ANX_GOLD_*: why a gold answer is (not) among the ranked rows, in the order of the reference's pipeline
+GOLD_REASONS = ("RANKED", "STATUS", "NOT_A_RESULT", "EXACT_STOP", "ANAGRAM", "EDIT", "THRESHOLD", "CROPPED")
+(ANX_GOLD_RANKED, ANX_GOLD_STATUS, ANX_GOLD_NOT_A_RESULT, ANX_GOLD_EXACT_STOP, ANX_GOLD_ANAGRAM, ANX_GOLD_EDIT, ANX_GOLD_THRESHOLD,
+ ANX_GOLD_CROPPED) = range(8)
+
+
 class BatchStats(C.Structure):
     _fields_ = [("n_queries", C.c_uint64), ("n_pairs", C.c_uint64), ("n_class_tests", C.c_uint64),
                 ("n_results", C.c_uint64), ("n_scan_blocks", C.c_uint64), ("n_tests_kind", C.c_uint64 * 5),
@@ -206,6 +218,11 @@ def lib():
         "anx_score_pairs_weighted_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(PairScore), C.POINTER(C.c_double)]),
         "anx_model_confusable_weight_text": (C.c_int, [vp, cp, cp, C.POINTER(C.c_double)]),
         "anx_debug_pairs_conf_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+        "anx_evaluate_gold": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(GoldEval), C.POINTER(PairScore)]),
+        "anx_evaluate_gold_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(Params), C.POINTER(GoldEval),
+                                               C.POINTER(PairScore)]),
+        "anx_debug_evaluate_gold_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(GoldEval),
+                                                    C.POINTER(PairScore), sz]),
         "anx_batch_pair_counts": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_uint32))]),
         "anx_counts_free": (None, [C.POINTER(C.c_uint32)]),
         "anx_batch_export_topk": (C.c_int, [vp, vp, C.c_uint32, vp]),

@@ -1,4 +1,4 @@
-"""`python -m analiticcl_amd query|search|learn|score ...` -- the `analiticcl query` / `search` / `learn` command line
+"""`python -m analiticcl_amd query|search|learn|score|evaluate ...` -- the `analiticcl query` / `search` / `learn` command line
 (/root/reference/src/bin/analiticcl.rs) on top of the MI355X engine.
 
 Same option names and defaults (note the CLI's own weight defaults 0.5/0.125/0.125/0.125/0.125, bin:760-800, and
@@ -10,6 +10,9 @@ find_all_matches) and writes the weighted variant list (bin:186-365; `-O`: one f
 and field quirks).  `score` has no counterpart in the reference's binary: it reads `a<TAB>b` lines and writes the model's measures
 for each pair (score_pairs: the reference's public distance functions, src/distance.rs:101-231, and the score of src/lib.rs:1433-1452); `--weighted` adds the pair's confusable weight under `--confusables`
 (src/lib.rs:1733-1756) and score * weight, the dist_score a ranked row carries on such a model.
+`evaluate` has none either: it reads `input<TAB>gold` lines, takes the model and parameter options of `query`, and writes per pair the
+1-based rank of gold among the ranked variants (`-`: not there), the top variant, gold's score, the pair's edit distance and the stage
+that lost a gold that is not ranked (evaluate_arrays); the summary (accuracy@1, MRR, count per reason) goes to stderr or `--summary-json`.
 Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
@@ -21,6 +24,7 @@ import sys
 from decimal import Decimal
 from typing import List, Optional
 
+from ._lib import GOLD_REASONS
 from .model import SearchParameters, VariantModel, VocabParams, Weights
 
 
@@ -91,7 +95,7 @@ def json_item(inp: str, variants: Optional[List[dict]], seqnr: int, offset=None,
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m analiticcl_amd", description=__doc__.split("\n\n")[0])
-    p.add_argument("mode", choices=["query", "search", "learn", "score"])
+    p.add_argument("mode", choices=["query", "search", "learn", "score", "evaluate"])
     p.add_argument("files", nargs="*", help="input files (default: standard input)")
     p.add_argument("--lexicon", "-l", action="append", default=[])
     p.add_argument("--variants", "-V", action="append", default=[])
@@ -125,6 +129,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight-contextrules", type=float, default=1.0)
     p.add_argument("--batch-size", type=int, default=100000, help="query mode: lines per device batch")
     p.add_argument("--weighted", action="store_true", help="score mode: two more columns / keys, weight (the confusable weight of the pair under --confusables) and weighted_score = score * weight")
+    p.add_argument("--summary-json", default=None, help="evaluate mode: write the summary as JSON to this file instead of as text to standard error")
     p.add_argument("--index-cache", default=None, help="image of the built model: loaded if the file exists (lexicons are then not read), written after build() otherwise")
     p.add_argument("--device", type=int, default=None)
     p.add_argument("--single-thread", "-1", action="store_true", help="accepted for compatibility, no effect")
@@ -434,6 +439,61 @@ def run_score(model, a, out) -> None:
     flush()
 
 
+def evaluate_tsv_line(inp: str, gold: str, r: dict, top_text: str) -> str:
+    """input, gold, 1-based rank of gold in the ranked variants (`-`: not among them), the text of the top variant (empty: none),
+    gold_score (the ranked row's dist_score, else the pair's own score), ld (unbounded Damerau-Levenshtein of the pair), reason"""
+    return "\t".join([inp, gold, "-" if r["rank"] is None else str(r["rank"] + 1), top_text, rust_f64(r["gold_score"]), str(r["ld"]), r["reason"]])
+
+
+def evaluate_summary_text(s: dict) -> str:
+    lines = ["pairs: %d" % s["n"], "gold known: %d" % s["gold_known"], "accuracy@1: %s" % rust_f64(s["accuracy_at_1"]),
+             "ranked: %s" % rust_f64(s["ranked_share"]), "MRR: %s" % rust_f64(s["mrr"])]
+    lines += ["%s: %d" % (k, v) for k, v in s["reasons"].items()]
+    return "\n".join(lines) + "\n"
+
+
+def run_evaluate(model, params, a, out) -> None:
+    """`evaluate`: every input line is `input<TAB>gold`; the pairs of --batch-size lines are one evaluate call (the ranked variants stay
+    on the device).  One TSV line per pair; the summary over all pairs goes to standard error, or as JSON to --summary-json."""
+    import json
+
+    import numpy as np
+    pa: List[str] = []
+    pg: List[str] = []
+    recs = []
+
+    def flush():
+        if not pa:
+            return
+        arr = model.evaluate_arrays(pa, pg, params)
+        recs.append(arr)
+        for i, (x, y) in enumerate(zip(pa, pg)):
+            rk, top = int(arr["rank"][i]), int(arr["top_vocab_id"][i])
+            r = {"rank": None if rk < 0 else rk, "gold_score": float(arr["gold_score"][i]), "ld": int(arr["ld"][i]),
+                 "reason": GOLD_REASONS[int(arr["reason"][i])]}
+            out.write(evaluate_tsv_line(x, y, r, "" if top == 0xFFFFFFFF else model.vocab_text(top)) + "\n")
+        out.flush()
+        pa.clear()
+        pg.clear()
+
+    limit = 1 if a.interactive else max(1, a.batch_size)
+    for line in _lines(a.files):
+        x, _, y = (line[:-1] if line.endswith("\r") else line).partition("\t")
+        pa.append(x)
+        pg.append(y.split("\t", 1)[0])
+        if len(pa) >= limit:
+            flush()
+    flush()
+    allrec = np.concatenate(recs) if recs else np.zeros(0, dtype=np.dtype(VariantModel.GOLD_DTYPE))
+    summary = VariantModel.evaluate_summary(allrec)
+    if a.summary_json:
+        with open(a.summary_json, "w") as f:
+            json.dump(summary, f, indent=1)
+            f.write("\n")
+    else:
+        sys.stderr.write(evaluate_summary_text(summary))
+
+
 def main(argv=None) -> int:
     a = build_parser().parse_intermixed_args(argv)
     if a.mode == "learn" and not 0 <= a.iterations <= 255:
@@ -444,6 +504,9 @@ def main(argv=None) -> int:
     out = sys.stdout
     if a.mode == "learn":
         run_learn(model, params, a, out)
+        return 0
+    if a.mode == "evaluate":
+        run_evaluate(model, params, a, out)
         return 0
     if a.json:
         out.write("[\n")

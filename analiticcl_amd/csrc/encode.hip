@@ -666,12 +666,18 @@ int small_encode_launch(const HostModel& m, const DeviceLexicon* dl, const Small
 // or more than 255 symbols); the thresholds behind meta's k / d bits are nobody's, so they are Absolute(0).
 int pairs_encode_launch(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n, hipStream_t st,
                         std::string& err) {
-  anx_params p{};
+  return pairs_encode_launch_thr(m, dl, e, blob, off, n, anx_params{}, st, err);
+}
+// the same launch with the caller's thresholds: meta's k / d bits are the clamped max_anagram_distance / max_edit_distance of every string
+int pairs_encode_launch_thr(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n,
+                            const anx_params& p, hipStream_t st, std::string& err) {
   EncArgs ea = enc_args_of(m, dl, p);
   ea.blob = blob; ea.off = off; ea.n = n;
   ea.codes = e.codes; ea.meta = e.meta; ea.bits = e.bits; ea.sig = e.sig; ea.kind = e.kind; ea.cv = e.cv; ea.key = e.key; ea.blk = e.blk;
   ea.zero_cv = 1;  // (no memset launch ahead of the kernel)
+  const int kt = ktimer_begin("k_enc_strings_pairs", st);  // (off unless anx_debug_kernel_timer(1): no event, no launch)
   hipLaunchKernelGGL(k_enc_strings<false>, dim3((n + 255) / 256), dim3(256), 0, st, ea);
+  ktimer_end(kt, st);
   HIP_TRY(hipGetLastError());
   return ANX_OK;
 }

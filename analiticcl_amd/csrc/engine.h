@@ -192,6 +192,17 @@ struct LearnSection { const void* base; size_t n; size_t lo; const uint32_t* idx
 int learn_fold_device(const HostModel& m, int device, LearnVocab** vocab, const char* blob, const uint32_t* soff, size_t n,
                       const std::vector<LearnSection>& secs, size_t n_rows, LearnFold& out, std::string& err);
 
+// ---- gold evaluation (eval.hip): anx_evaluate_gold -----------------------------------------------------------------------------------
+// One chunk of at most PAIRS_CHUNK (input, gold) pairs whose ranked rows lie in compact export sections on replica 0's device (the
+// layout learn mode gathers: LearnSection, inputs relative to the chunk; sec_rows[s] = the records of section s).  out[i] = the
+// anx_gold_eval record of pair i; pairs (may be nullptr): what score_pairs_chunk writes for the same pairs.  One upload of the 2 n
+// strings, the encoder with `p`'s thresholds, the pair kernels, the vocabulary lookup of the gold strings, k_eval_rows over the
+// gathered rows, k_eval_classify, one download.  *vocab: the model's learn table (the caller holds the learn lock).
+void* eval_device_alloc(int device, size_t bytes);  // a gather buffer from the device's scratch pool (nullptr: out of memory / HIP error)
+void eval_device_free(int device, void* p);
+int evaluate_chunk(const HostModel& m, const DeviceLexicon* dl, LearnVocab** vocab, const PairSpan* a, const PairSpan* gold, size_t n, const anx_params& p,
+                   const std::vector<LearnSection>& secs, const std::vector<size_t>& sec_rows, anx_gold_eval* out, anx_pair_score* pairs, std::string& err);
+
 // ---- search mode in one device pass (lattice.hip): the lattices are built on the device from the rows of the part's batches --------------
 // What the host knows without any result: the segments ("matches") of every stretch, in the order of the stretch's match list
 // (order-major), the states they connect, and the layout of the arcs ("groups", listed per destination state in (source state,

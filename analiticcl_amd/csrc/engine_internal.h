@@ -119,5 +119,77 @@ struct PairConfRun {
 };
 size_t conf_pairs_sort_tmp_bytes(uint32_t n);
 int conf_launch_pairs(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, const PairConfRun& r, std::string& err);
+// pairs_encode_launch with the caller's thresholds behind meta's k / d bits (anx_evaluate_gold reads them there)
+int pairs_encode_launch_thr(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n,
+                            const anx_params& thr, hipStream_t st, std::string& err);
+// pool blocks and pinned host blocks of one call released together, and the private stream of the call
+struct PairScratch {
+  std::vector<void*> blocks, host;
+  int device;
+  hipStream_t st;
+  explicit PairScratch(int dev) : device(dev), st(encoder_stream_acquire(dev)) {}
+  PairScratch(const PairScratch&) = delete;
+  PairScratch& operator=(const PairScratch&) = delete;
+  template <typename T>
+  int get(T** p, size_t count, std::string& err) {
+    void* q = nullptr;
+    const size_t bytes = count * sizeof(T) < 16 ? 16 : count * sizeof(T);
+    const hipError_t e = pool_malloc(&q, bytes);
+    if (e != hipSuccess) { err = std::string("pool_malloc: ") + hipGetErrorString(e); return ANX_ENODEVICE; }
+    blocks.push_back(q);
+    *p = static_cast<T*>(q);
+    return ANX_OK;
+  }
+  void* pinned(size_t bytes) {
+    void* q = host_result_alloc(bytes < 16 ? 16 : bytes);
+    if (q) host.push_back(q);
+    return q;
+  }
+  // nothing enqueued by this call may still use the blocks when they return to their pools (an error path has not waited yet)
+  ~PairScratch() {
+    (void)hipStreamSynchronize(st);
+    for (void* q : blocks) pool_free(q);
+    for (void* q : host) host_result_free(q);
+    encoder_stream_release(device, st);
+  }
+};
+// The front half of score_pairs_chunk (pairs.hip): staging, one upload, the encoder over the 2 n strings and the pair kernels, all
+// enqueued on sc.st; the records stay on the device.  thr: the thresholds behind meta's k / d bits (nullptr: Absolute(0), nobody reads them).
+struct PairsOnDevice {
+  const uint8_t* blob = nullptr;   // the 2 n strings: a of pair i = string i, its b = string n + i
+  const uint32_t* off = nullptr;   // [2 n + 1]
+  SmallEnc e;                      // codes, meta, bits, kind, cv, key, sig, blk
+  anx_pair_score* out = nullptr;   // [n]
+};
+int pairs_chunk_enqueue(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, const anx_params* thr, PairScratch& sc,
+                        PairsOnDevice& pd, std::string& err);
+
+// ---- the vocabulary table of learn mode and anx_evaluate_gold (built by learn.hip): text hash -> id -----------------------------------------
+struct LearnVocab {
+  int device = -1;
+  size_t V = 0;
+  uint8_t* pool = nullptr;
+  uint32_t* voff = nullptr;
+  unsigned long long* vh = nullptr;
+  uint32_t* slots = nullptr;
+  uint32_t mask = 0;
+  unsigned long long hmask = 0;  // what lf_hash keeps of FNV-1a (the table's hashes and the lookups' must agree)
+};
+constexpr uint32_t LF_EMPTY = 0xFFFFFFFFu;    // free table slot
+// FNV-1a under hmask: its low 63 bits, or fewer under the test switch ANX_LEARN_HASH_BITS (collisions on demand)
+__device__ inline unsigned long long lf_hash(const uint8_t* p, uint32_t len, unsigned long long hmask) {
+  unsigned long long h = 1469598103934665603ull;
+  for (uint32_t i = 0; i < len; ++i) { h ^= p[i]; h *= 1099511628211ull; }
+  return h & hmask;
+}
+__device__ inline bool lf_eq(const uint8_t* a, uint32_t la, const uint8_t* b, uint32_t lb) {
+  if (la != lb) return false;
+  for (uint32_t i = 0; i < la; ++i)
+    if (a[i] != b[i]) return false;
+  return true;
+}
+// the table of `m`'s vocabulary on `device` in *cache: built on first use, rebuilt when the vocabulary size or ANX_LEARN_HASH_BITS changed
+// (the caller holds the learn lock); waits on `st`
+int learn_vocab_ensure(const HostModel& m, int device, LearnVocab** cache, hipStream_t st, std::string& err);
 
 }  // namespace anx

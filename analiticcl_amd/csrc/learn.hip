@@ -45,24 +45,12 @@ namespace anx {
   } while (0)
 
 namespace {
-constexpr uint32_t LF_EMPTY = 0xFFFFFFFFu;    // free table slot
 constexpr uint32_t LF_NONE = 0xFFFFFFFFu;     // input without rows: no id
 constexpr uint32_t LF_PENDING = 0xFFFFFFFEu;  // input with rows whose string is not in the vocabulary (yet)
 constexpr unsigned long long LF_NOKEY = ~0ull;  // sorts behind every real key (hashes have the top bit clear)
 constexpr int LF_BLOCK = 256;
 
-// FNV-1a under hmask: its low 63 bits, or fewer under the test switch ANX_LEARN_HASH_BITS (collisions on demand)
-__device__ inline unsigned long long lf_hash(const uint8_t* p, uint32_t len, unsigned long long hmask) {
-  unsigned long long h = 1469598103934665603ull;
-  for (uint32_t i = 0; i < len; ++i) { h ^= p[i]; h *= 1099511628211ull; }
-  return h & hmask;
-}
-__device__ inline bool lf_eq(const uint8_t* a, uint32_t la, const uint8_t* b, uint32_t lb) {
-  if (la != lb) return false;
-  for (uint32_t i = 0; i < la; ++i)
-    if (a[i] != b[i]) return false;
-  return true;
-}
+// (LF_EMPTY, lf_hash, lf_eq and LearnVocab: engine_internal.h -- eval.hip probes the same table)
 inline unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>(1, (n + LF_BLOCK - 1) / LF_BLOCK); }
 
 // vocabulary table: open addressing, linear probing, capacity a power of two >= 2 V (every probe ends at a free slot)
@@ -276,17 +264,6 @@ bool learn_device_upload(int device, void* dst, const void* src, size_t bytes) {
   return true;
 }
 
-struct LearnVocab {
-  int device = -1;
-  size_t V = 0;
-  uint8_t* pool = nullptr;
-  uint32_t* voff = nullptr;
-  unsigned long long* vh = nullptr;
-  uint32_t* slots = nullptr;
-  uint32_t mask = 0;
-  unsigned long long hmask = 0;  // what lf_hash keeps of FNV-1a (the table's hashes and the lookups' must agree)
-};
-
 void learn_vocab_free(LearnVocab* t) {
   if (!t) return;
   if (t->device >= 0) (void)hipSetDevice(t->device);
@@ -334,6 +311,10 @@ static int learn_vocab_build(const HostModel& m, int device, LearnVocab** cache,
   if (rc) { learn_vocab_free(t); return rc; }
   *cache = t;
   return ANX_OK;
+}
+
+int learn_vocab_ensure(const HostModel& m, int device, LearnVocab** cache, hipStream_t st, std::string& err) {
+  return learn_vocab_build(m, device, cache, st, err);
 }
 
 int learn_fold_device(const HostModel& m, int device, LearnVocab** vocab, const char* blob, const uint32_t* soff, size_t n,

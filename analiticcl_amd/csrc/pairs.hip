@@ -298,32 +298,6 @@ __global__ __launch_bounds__(64) void k_pairs_long(PairKArgs k) {
 
 // ---- host driver --------------------------------------------------------------------------------------------------------------------
 namespace {
-struct PairScratch {  // pool blocks and pinned host blocks released together, and the private stream of the call
-  std::vector<void*> blocks, host;
-  int device;
-  hipStream_t st;
-  explicit PairScratch(int dev) : device(dev), st(encoder_stream_acquire(dev)) {}
-  template <typename T>
-  int get(T** p, size_t count, std::string& err) {
-    void* q = nullptr;
-    HIP_TRY(pool_malloc(&q, std::max<size_t>(count * sizeof(T), 16)));
-    blocks.push_back(q);
-    *p = static_cast<T*>(q);
-    return ANX_OK;
-  }
-  void* pinned(size_t bytes) {
-    void* q = host_result_alloc(std::max<size_t>(bytes, 16));
-    if (q) host.push_back(q);
-    return q;
-  }
-  // nothing enqueued by this call may still use the blocks when they return to their pools (an error path has not waited yet)
-  ~PairScratch() {
-    (void)hipStreamSynchronize(st);
-    for (void* q : blocks) pool_free(q);
-    for (void* q : host) host_result_free(q);
-    encoder_stream_release(device, st);
-  }
-};
 std::atomic<uint64_t> g_cf_seen{0}, g_cf_screened{0}, g_cf_scripts{0}, g_cf_host{0};
 
 // weight[i] on the host for the pairs `pick` selects: HostModel::confusable_weight_text, on up to 16 threads when there are many
@@ -355,17 +329,14 @@ void pairs_conf_stats(uint64_t out[4]) {
   out[2] = g_cf_scripts.load(std::memory_order_relaxed); out[3] = g_cf_host.load(std::memory_order_relaxed);
 }
 
-int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, anx_pair_score* out, std::string& err,
-                      double* weight) {
-  if (n == 0) return ANX_OK;
-  if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
-  if (n > PAIRS_CHUNK) { err = "score_pairs_chunk: more than 2^20 pairs"; return ANX_EINVAL; }
+// Staging, the upload, the encoder and the pair kernels of one chunk, enqueued on sc.st (engine_internal.h): what score_pairs_chunk
+// downloads, and what eval.hip (anx_evaluate_gold) reads where it lies.
+int pairs_chunk_enqueue(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, const anx_params* thr, PairScratch& sc,
+                        PairsOnDevice& pd, std::string& err) {
   const size_t N2 = 2 * n;
   size_t text = 0;
   for (size_t i = 0; i < n; ++i) text += a[i].len + b[i].len + 2;
   if (text + 4 * N2 + 16 >= ((size_t)1 << 32)) { err = "pairs exceed 4 GB of text per 2^20 pairs (bytes + 4 per string)"; return ANX_ELIMIT; }
-  HIP_TRY(hipSetDevice(dl->device));
-  PairScratch sc(dl->device);
   hipStream_t st = sc.st;
   // ---- one staging block: offsets [2 n + 1] | tier lists [n] (short pairs from the front, long ones from the back) | the blob ----
   const size_t o_idx = (N2 + 1) * sizeof(uint32_t), o_blob = (o_idx + n * sizeof(uint32_t) + 15) & ~(size_t)15, in_bytes = o_blob + text + 16;
@@ -406,6 +377,46 @@ int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpa
       (rc = sc.get(&e.key, N2, err)) || (rc = sc.get(&e.sig, N2, err)) || (rc = sc.get(&e.blk, 3 * ((N2 + 255) / 256), err)) ||
       (rc = sc.get(&d_out, n, err)))
     return rc;
+  HIP_TRY(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, st));
+  const uint32_t* d_off = reinterpret_cast<const uint32_t*>(d_in);
+  const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_in + o_idx);
+  if ((rc = thr ? pairs_encode_launch_thr(m, dl, e, reinterpret_cast<const uint8_t*>(d_in + o_blob), d_off, (uint32_t)N2, *thr, st, err)
+                : pairs_encode_launch(m, dl, e, reinterpret_cast<const uint8_t*>(d_in + o_blob), d_off, (uint32_t)N2, st, err)))
+    return rc;
+  PairKArgs k{};
+  k.n = (uint32_t)n; k.off = d_off; k.codes = e.codes; k.meta = e.meta; k.out = d_out; k.quot = dl->quot;
+  k.w_ld = m.weights.ld; k.w_lcs = m.weights.lcs; k.w_prefix = m.weights.prefix; k.w_suffix = m.weights.suffix; k.w_case = m.weights.casew;
+  k.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;  // src/types.rs:69-73, as launch_plan.hpp
+  if (nshort) {
+    k.idx = d_idx; k.count = nshort;
+    const int kt = ktimer_begin("k_pairs_short", st);
+    hipLaunchKernelGGL(k_pairs_short, dim3((nshort + PS_THREADS - 1) / PS_THREADS), dim3(PS_THREADS), 0, st, k);
+    ktimer_end(kt, st);
+  }
+  if (nlong) {
+    k.idx = d_idx + (n - nlong); k.count = nlong;
+    const int kt = ktimer_begin("k_pairs_long", st);
+    if (long_max <= 64) hipLaunchKernelGGL(k_pairs_long<64>, dim3(nlong), dim3(64), 0, st, k);
+    else hipLaunchKernelGGL(k_pairs_long<255>, dim3(nlong), dim3(64), 0, st, k);
+    ktimer_end(kt, st);
+  }
+  HIP_TRY(hipGetLastError());
+  pd.blob = reinterpret_cast<const uint8_t*>(d_in + o_blob); pd.off = d_off; pd.e = e; pd.out = d_out;
+  return ANX_OK;
+}
+
+int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, anx_pair_score* out, std::string& err,
+                      double* weight) {
+  if (n == 0) return ANX_OK;
+  if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
+  if (n > PAIRS_CHUNK) { err = "score_pairs_chunk: more than 2^20 pairs"; return ANX_EINVAL; }
+  HIP_TRY(hipSetDevice(dl->device));
+  PairScratch sc(dl->device);
+  hipStream_t st = sc.st;
+  PairsOnDevice pd;
+  int rc;
+  if ((rc = pairs_chunk_enqueue(m, dl, a, b, n, nullptr, sc, pd, err))) return rc;
+  anx_pair_score* d_out = pd.out;
   anx_pair_score* h_out = static_cast<anx_pair_score*>(sc.pinned(n * sizeof(anx_pair_score)));
   if (!h_out) { err = "out of host memory"; return ANX_EINVAL; }
   // ---- confusable weights: on the device unless the model has no list, the switch says host, or the working set finds no room ----
@@ -433,30 +444,8 @@ int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpa
       if (!h_w) { err = "out of host memory"; return ANX_EINVAL; }
     }
   }
-  HIP_TRY(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, st));
-  const uint32_t* d_off = reinterpret_cast<const uint32_t*>(d_in);
-  const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_in + o_idx);
-  if ((rc = pairs_encode_launch(m, dl, e, reinterpret_cast<const uint8_t*>(d_in + o_blob), d_off, (uint32_t)N2, st, err))) return rc;
-  PairKArgs k{};
-  k.n = (uint32_t)n; k.off = d_off; k.codes = e.codes; k.meta = e.meta; k.out = d_out; k.quot = dl->quot;
-  k.w_ld = m.weights.ld; k.w_lcs = m.weights.lcs; k.w_prefix = m.weights.prefix; k.w_suffix = m.weights.suffix; k.w_case = m.weights.casew;
-  k.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;  // src/types.rs:69-73, as launch_plan.hpp
-  if (nshort) {
-    k.idx = d_idx; k.count = nshort;
-    const int kt = ktimer_begin("k_pairs_short", st);
-    hipLaunchKernelGGL(k_pairs_short, dim3((nshort + PS_THREADS - 1) / PS_THREADS), dim3(PS_THREADS), 0, st, k);
-    ktimer_end(kt, st);
-  }
-  if (nlong) {
-    k.idx = d_idx + (n - nlong); k.count = nlong;
-    const int kt = ktimer_begin("k_pairs_long", st);
-    if (long_max <= 64) hipLaunchKernelGGL(k_pairs_long<64>, dim3(nlong), dim3(64), 0, st, k);
-    else hipLaunchKernelGGL(k_pairs_long<255>, dim3(nlong), dim3(64), 0, st, k);
-    ktimer_end(kt, st);
-  }
-  HIP_TRY(hipGetLastError());
   if (on_device) {
-    cr.n = (uint32_t)n; cr.blob = reinterpret_cast<const uint8_t*>(d_in + o_blob); cr.off = d_off; cr.rec = d_out;
+    cr.n = (uint32_t)n; cr.blob = pd.blob; cr.off = pd.off; cr.rec = d_out;
     if ((rc = conf_launch_pairs(m, dl, st, cr, err))) return rc;
   }
   HIP_TRY(hipMemcpyAsync(h_out, d_out, n * sizeof(anx_pair_score), hipMemcpyDeviceToHost, st));

@@ -682,6 +682,78 @@ class VariantModel:
         L.check(L.lib().anx_debug_pairs_conf_stats(out))
         return {"pairs": int(out[0]), "screened": int(out[1]), "device_scripts": int(out[2]), "host_pairs": int(out[3])}
 
+    # -- gold evaluation ---------------------------------------------------------------------------------
+    GOLD_DTYPE = [("gold_vocab_id", "<u4"), ("rank", "<i4"), ("n_results", "<u4"), ("top_vocab_id", "<u4"), ("gold_score", "<f8"),
+                  ("ld", "<u2"), ("k", "u1"), ("d", "u1"), ("status", "i1"), ("reason", "u1"), ("_pad", "<u2")]
+    PAIR_DTYPE = [("score", "<f8"), ("ld", "<u2"), ("lcs", "<u2"), ("prefixlen", "<u2"), ("suffixlen", "<u2"),
+                  ("len_a", "u1"), ("len_b", "u1"), ("samecase", "u1"), ("status", "i1"), ("_pad", "<u4")]
+    GOLD_KEYS = ("gold_vocab_id", "rank", "n_results", "top_vocab_id", "gold_score", "ld", "k", "d", "status", "reason")
+
+    def evaluate_arrays(self, inputs: Sequence[str], gold: Sequence[str], params: SearchParameters, with_pairs: bool = False,
+                        packed: bool = True, chunk: Optional[int] = None):
+        """anx_evaluate_gold: one record per pair (inputs[i], gold[i]) as a numpy structured array (anx_gold_eval: gold_vocab_id,
+        rank, n_results, top_vocab_id, gold_score, ld, k, d, status, reason) -- where gold[i] stands in what find_variants(inputs[i],
+        params) returns on this model (rank, -1 = not there) and, if it is not there, the first stage of the pipeline that lost it
+        (reason, an index into GOLD_REASONS).  The ranked rows never leave the device.  with_pairs: returns (records, pairs), pairs =
+        the anx_pair_score records anx_score_pairs writes for the same pairs.  packed = False: the pointer form of the call; chunk:
+        the test hook with a caller-chosen chunk size (pointer form)."""
+        import numpy as np
+        n = len(inputs)
+        if len(gold) != n:
+            raise ValueError("evaluate: inputs and gold differ in length")
+        dt = np.dtype(self.GOLD_DTYPE)
+        assert dt.itemsize == C.sizeof(L.GoldEval)
+        out = np.zeros(max(n, 1), dtype=dt)
+        optr = out.ctypes.data_as(C.POINTER(L.GoldEval))
+        pairs = np.zeros(max(n, 1), dtype=np.dtype(self.PAIR_DTYPE)) if with_pairs else None
+        pptr = pairs.ctypes.data_as(C.POINTER(L.PairScore)) if with_pairs else None
+        cp = params._c()
+        if packed and chunk is None:
+            ba, bg = _pack(inputs), _pack(gold)
+            L.check(L.lib().anx_evaluate_gold_packed(self.h, ba, len(ba), bg, len(bg), n, C.byref(cp), optr, pptr))
+        else:
+            aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
+            ag = (C.c_char_p * max(n, 1))(*[_b(t) for t in gold])
+            if chunk is None:
+                L.check(L.lib().anx_evaluate_gold(self.h, aa, ag, n, C.byref(cp), optr, pptr))
+            else:
+                L.check(L.lib().anx_debug_evaluate_gold_chunk(self.h, aa, ag, n, C.byref(cp), optr, pptr, int(chunk)))
+        return (out[:n], pairs[:n]) if with_pairs else out[:n]
+
+    def evaluate(self, inputs: Sequence[str], gold: Sequence[str], params: SearchParameters) -> List[dict]:
+        """evaluate_arrays as one dict per pair: the record's fields, rank None when gold is not among the rows, gold_vocab_id /
+        top_vocab_id None when there is none, and reason as its name (GOLD_REASONS)."""
+        rec = self.evaluate_arrays(inputs, gold, params)
+        lists = {k: rec[k].tolist() for k in self.GOLD_KEYS}
+        out = []
+        for i in range(len(inputs)):
+            d = {k: lists[k][i] for k in self.GOLD_KEYS}
+            d["rank"] = None if d["rank"] < 0 else d["rank"]
+            for k in ("gold_vocab_id", "top_vocab_id"):
+                d[k] = None if d[k] == 0xFFFFFFFF else d[k]
+            d["reason"] = L.GOLD_REASONS[d["reason"]]
+            out.append(d)
+        return out
+
+    @staticmethod
+    def evaluate_summary(records) -> dict:
+        """What a tuning run reads off evaluate_arrays' records, computed on the host: n, gold_known (pairs whose gold text is a
+        vocabulary item), accuracy_at_1 (gold at rank 0), ranked_share (gold anywhere in the rows), mrr (mean of 1 / (rank + 1), 0 for
+        a gold that is not ranked) -- all three over n -- and the count per reason."""
+        import numpy as np
+        n = int(len(records))
+        rank = np.asarray(records["rank"], dtype=np.int64)
+        ranked = rank >= 0
+        rr = np.zeros(n, dtype=np.float64)
+        rr[ranked] = 1.0 / (rank[ranked] + 1.0)
+        counts = np.bincount(np.asarray(records["reason"], dtype=np.int64), minlength=len(L.GOLD_REASONS))
+        return {"n": n,
+                "gold_known": int(np.count_nonzero(np.asarray(records["gold_vocab_id"]) != 0xFFFFFFFF)),
+                "accuracy_at_1": float(np.count_nonzero(rank == 0)) / n if n else 0.0,
+                "ranked_share": float(np.count_nonzero(ranked)) / n if n else 0.0,
+                "mrr": float(rr.sum()) / n if n else 0.0,
+                "reasons": {name: int(counts[i]) for i, name in enumerate(L.GOLD_REASONS)}}
+
     def query_output(self, inputs: Sequence[str], params: SearchParameters, json: bool = False,
                      output_lexmatch: bool = False, first_seqnr: int = 1) -> str:
         """One device batch + the text `analiticcl query` prints for it (anx_format_query_output: the TSV lines or JSON

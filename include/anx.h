@@ -39,7 +39,9 @@ extern "C" {
  *    multi-device models (anx_debug_small_replica_stats; results unchanged); anx_score_pairs / anx_score_pairs_packed and the
  *    struct anx_pair_score: the measures and the score of caller-chosen string pairs (additive, nothing else changed);
  *    anx_score_pairs_weighted / _packed, anx_model_confusable_weight_text and anx_debug_pairs_conf_stats: the confusable weight of
- *    such pairs (additive); the test hooks anx_debug_exclusive_scan and anx_debug_rank_rows (additive). */
+ *    such pairs (additive); the test hooks anx_debug_exclusive_scan and anx_debug_rank_rows (additive); anx_evaluate_gold /
+ *    anx_evaluate_gold_packed, the struct anx_gold_eval, the ANX_GOLD_* reasons and the test hook anx_debug_evaluate_gold_chunk
+ *    (additive, nothing else changed). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -618,6 +620,64 @@ int anx_debug_learn_times(double out[6]);
  * collision branches run; results do not depend on it. */
 int anx_debug_learn_fold_rows(anx_model *, const char *const *utf8, size_t n, const anx_result *rows, const size_t *offsets, int n_sections,
                               int by_index, uint64_t *count);
+
+/* ---- gold evaluation: where did the correct form end up, and if nowhere, which stage lost it -------------------------------------------
+ * For pair i = (inputs[i], gold[i]) and the caller's parameters P, out[i] describes gold[i] against rows_i = exactly what
+ * find_variants(inputs[i], P) returns on this model (ranked, variant lists expanded, confusables weighted late or early):
+ *   gold_vocab_id  the vocabulary item whose text equals gold[i] byte for byte, UINT32_MAX if none
+ *   rank           index of the first row of rows_i with vocab_id == gold_vocab_id, -1 if none.  On a model with variant lists a row
+ *                  reached through `via` counts: the row's vocab_id is what is compared
+ *   n_results, top_vocab_id   len(rows_i); rows_i[0].vocab_id or UINT32_MAX
+ *   gold_score     rank >= 0: that row's dist_score, bit for bit; else the unweighted score anx_score_pairs gives for the pair (0 when
+ *                  the pair has a status)
+ *   k, d           the input's clamped max_anagram_distance / max_edit_distance (src/lib.rs:972-1027); 0 when the input is empty or
+ *                  has more than 255 symbols
+ *   ld, status     as anx_score_pairs gives them for (inputs[i], gold[i]): unbounded Damerau-Levenshtein; ANX_OK / ANX_EEMPTY / ANX_ELIMIT
+ *   reason         the first ANX_GOLD_* that applies, in the order of the reference's pipeline.  The reasons other than RANKED always
+ *                  describe the DIRECT pair (input, gold), also on a model with variant lists.
+ * pairs (may be NULL): pairs[i] = byte for byte what anx_score_pairs writes for (inputs[i], gold[i]).
+ * The ranked rows come from the staged batch path (never the small call) and stay on the device: every shard is gathered onto replica
+ * 0 (anx_batch_gather_compact_via), whose device looks the gold strings up, encodes both sides, runs the pair kernels, searches the
+ * rows (k_eval_rows) and classifies (k_eval_classify); 32 bytes per pair come back (56 with pairs).  Chunks of at most 2^20 pairs.
+ * Limits: 255 symbols a side (status ANX_ELIMIT beyond); the pass runs on replica 0 alone; holds the learn lock for the call (the
+ * vocabulary table is learn mode's).  Returns ANX_OK for n == 0; ANX_EINVAL for a NULL argument or string, and for a model whose
+ * confusables are weighted on the host (ANX_CONFUSABLES=host, or a row the device could not weight: the rows exist on the host only);
+ * ANX_ENOTBUILT before anx_model_build; ANX_ENODEVICE for a model that is not resident on a device; ANX_ELIMIT as anx_score_pairs.
+ * _packed: inputs = the first n NUL-terminated spans of blob_in[0, len_in), gold likewise (as anx_score_pairs_packed). */
+enum {
+  ANX_GOLD_RANKED = 0,       /* rank >= 0 */
+  ANX_GOLD_STATUS = 1,       /* status != ANX_OK */
+  ANX_GOLD_NOT_A_RESULT = 2, /* no vocabulary item has that text, or one find_variants never returns: not INDEXED (src/lib.rs:198), or TRANSPARENT */
+  ANX_GOLD_EXACT_STOP = 3,   /* P.stop_at_exact_match, the index holds the input's own anagram class and gold is not in it (src/lib.rs:1164-1173) */
+  ANX_GOLD_ANAGRAM = 4,      /* gold's anagram class is not among the candidates at k: L1 of the count vectors > k, or no shared symbol */
+  ANX_GOLD_EDIT = 5,         /* ld > d: the bounded Damerau-Levenshtein returns None (src/distance.rs:109-130) */
+  ANX_GOLD_THRESHOLD = 6,    /* the unweighted pair score is below P.score_threshold (src/lib.rs:1475) */
+  ANX_GOLD_CROPPED = 7       /* everything else: cutoff_threshold, max_matches, tie rules, the re-rank after confusable weights */
+};
+typedef struct anx_gold_eval {
+  uint32_t gold_vocab_id;
+  int32_t rank;
+  uint32_t n_results;
+  uint32_t top_vocab_id;
+  double gold_score;
+  uint16_t ld;
+  uint8_t k, d;
+  int8_t status;
+  uint8_t reason;
+  uint16_t _pad;
+} anx_gold_eval; /* 32 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(anx_gold_eval) == 32, "anx_gold_eval is 32 bytes");
+#else
+_Static_assert(sizeof(anx_gold_eval) == 32, "anx_gold_eval is 32 bytes");
+#endif
+int anx_evaluate_gold(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const anx_params *, anx_gold_eval *out,
+                      anx_pair_score *pairs);
+int anx_evaluate_gold_packed(anx_model *, const char *blob_in, size_t len_in, const char *blob_gold, size_t len_gold, size_t n,
+                             const anx_params *, anx_gold_eval *out, anx_pair_score *pairs);
+/* Test hook: the same contract with a caller-chosen chunk size (1 .. 2^20 pairs), so that chunk seams are reached with small calls. */
+int anx_debug_evaluate_gold_chunk(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const anx_params *,
+                                  anx_gold_eval *out, anx_pair_score *pairs, size_t chunk);
 
 #ifdef __cplusplus
 }
