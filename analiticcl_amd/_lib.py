@@ -250,6 +250,7 @@ def lib():
         "anx_debug_exclusive_scan": (C.c_int, [C.c_int, vp, C.c_size_t, vp, vp]),
         "anx_debug_rank_rows": (C.c_int, [C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_uint64, C.c_float, C.c_int,
                                           C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
+        "anx_debug_score_slots": (C.c_int, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
         "anx_batch_free": (None, [vp]),
         "anx_device_pool_trim": (None, [C.c_int]),
     }

@@ -1507,6 +1507,33 @@ int anx_batch_fetch_pairs(const anx_batch* b, anx_pair** out, size_t* n) {
   return ANX_OK;
 }
 void anx_pairs_free(anx_pair* p) { free(p); }
+int anx_debug_score_slots(const anx_model* m, const anx_batch* b, uint32_t region_shift, const uint32_t* fills, const uint32_t* slots, uint32_t seg_cap,
+                          uint32_t surv_region_cap, uint32_t list_cap, uint32_t blk, int one_launch, uint32_t* out_meta, double* out_score, uint32_t* out_qcount,
+                          void* out_surv, uint32_t* out_ctr, void* out_seg, uint32_t* out_skipped) {
+  if (!m || !b || !fills || !out_qcount || !out_surv || !out_ctr || !out_skipped || (seg_cap && !out_seg)) return fail(ANX_EINVAL, "NULL argument");
+  if (b->model != m) return fail(ANX_EINVAL, "the batch was encoded with another model");
+  size_t total = 0;
+  for (int r = 0; r < 64; ++r) total += fills[r];
+  if (total && (!slots || !out_meta || !out_score)) return fail(ANX_EINVAL, "NULL argument");
+  // every output starts as 0xFF bytes: what the call did not write stays visible, and a refused call wrote nothing
+  // (the survivor list and the segments once their capacities, which size them, are known to be in range)
+  if (total) { memset(out_meta, 0xFF, total * sizeof(uint32_t)); memset(out_score, 0xFF, total * sizeof(double)); }
+  memset(out_qcount, 0xFF, 3 * b->n_input * sizeof(uint32_t));
+  memset(out_ctr, 0xFF, 5 * 64 * sizeof(uint32_t));
+  *out_skipped = 0xFFFFFFFFu;
+  if (surv_region_cap == 0 || surv_region_cap > (1u << 16) || seg_cap > 1024) return fail(ANX_EINVAL, "score slots: survivor capacity outside 1 .. 65536 or segments beyond 1024");
+  memset(out_surv, 0xFF, (size_t)64 * surv_region_cap * 16);
+  if (seg_cap) memset(out_seg, 0xFF, b->n_input * seg_cap * 16);
+  if (check_resident(m)) return g_code;
+  if (m->replicas.size() != 1 || b->shards.size() != 1 || scattered(b)) return fail(ANX_EINVAL, "score slots: a single-device model and a batch of one shard");
+  if (b->rescore) return fail(ANX_EINVAL, "score slots: not with host-side confusable weighting");
+  const anx::DebugScoreIn in{region_shift, fills, slots, seg_cap, surv_region_cap, list_cap, blk, one_launch ? 1 : 0};
+  const anx::DebugScoreOut out{out_meta, out_score, out_qcount, out_surv, out_ctr, out_seg, out_skipped};
+  return on_shards(b, [&](size_t g, std::string& err) {
+    const Shard& s = b->shards[g];
+    return anx::debug_score_slots(m->host, m->replicas[(size_t)s.replica].dev, s.b, in, out, err);
+  });
+}
 int anx_batch_pair_counts(anx_batch* b, uint32_t** out) {
   if (!b || !out) return fail(ANX_EINVAL, "NULL argument");
   const size_t S = b->shards.size();

@@ -40,6 +40,28 @@ struct DebugRankIn {
   uint32_t seg_cap, row_cap, overflow;
 };
 int debug_rank_rows(int device, const DebugRankIn& in, uint32_t* out_count, void* out_rows, std::string& err);
+// test hook: the scoring stage alone (engine.hip debug_score_slots: k_filter_score and the slot-list kernels, launched by the function a
+// run launches them with) on an encoded batch and a pair list the caller laid out.  fills[SCAN_REGIONS = 64] slots per region, back to
+// back in `slots` as (query input index, entry id | flags) or (0xFFFFFFFF, -) = an unused slot.  Every check of the slots runs on the host
+// before the first launch (ANX_EINVAL).  The outputs (sizes in include/anx.h) are the hook's device buffers, which start as 0xFF bytes.
+struct DebugScoreIn {
+  uint32_t region_shift;           // log2(slots per region), 10 .. 16
+  const uint32_t* fills;
+  const uint32_t* slots;
+  uint32_t seg_cap;                // 0, or C: per-query segments
+  uint32_t surv_region_cap, list_cap, blk;
+  int one_launch;                  // the slot-list kernels as k_small_lists
+};
+struct DebugScoreOut {
+  uint32_t* meta;                  // [slots]
+  double* score;                   // [slots]
+  uint32_t* qcount;                // [3][inputs]: qsurv, qmaxfreq, qexpand
+  void* surv;                      // [64][surv_region_cap] {u32 input, u32 entry, f64 score}
+  uint32_t* ctr;                   // [5][64]: fills of the survivor list, list8, listg, listw; selected pairs
+  void* seg;                       // [inputs][seg_cap] {f64 score, u32 entry, u32 0}
+  uint32_t* skipped;
+};
+int debug_score_slots(const HostModel& m, const DeviceLexicon* dl, const Batch* b, const DebugScoreIn& in, const DebugScoreOut& out, std::string& err);
 void kernel_timer_enable(bool on);  // also clears the totals
 bool kernel_timer_read(const char* name, double* total_ms, uint64_t* launches);  // waits for the recorded launches
 void device_pool_trim(int device);  // hands the cached scratch blocks of the device (and the pinned result buffers) back to the driver

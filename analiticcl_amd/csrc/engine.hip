@@ -1399,58 +1399,103 @@ int Run::scan() {
   return ANX_OK;
 }
 
-int Run::score() {
-  int rc;
-  HIP_TRY(hipMemsetAsync(b->qsurv, 0, (dl->any_variants ? 3 : 2) * (size_t)nq * sizeof(uint32_t), st));  // qsurv, qmaxfreq (, qexpand)
-  ScorePlan plan = score_plan_of(m, dl, b->params.score_threshold, b->qw, b->dmax);
+// ---- the scoring stage: what Run::score and the test hook debug_score_slots (below) both launch ------------------------------------------
+// The plan of a stage (launch_plan.hpp) with the caller's debug choices; refuses a per-lane state beyond the LDS budget.
+static int score_stage_plan(const HostModel& m, const DeviceLexicon* dl, double score_threshold, uint32_t qw, uint32_t dmax, bool store_pairs, ScorePlan& plan, std::string& err) {
+  plan = score_plan_of(m, dl, score_threshold, qw, dmax);
   ScoreArgs& sa = plan.sa;
 #ifdef ANX_DEBUG_SWITCHES
   { const char* e = getenv("ANX_SCORE_DBG"); sa.dbg = e ? atoi(e) : 0; }
 #endif
-  sa.store_pairs = b->keep_all_pairs ? 1 : 0;
-  if (sa.store_pairs && (rc = ensure_pair_outputs(b, err))) return rc;
+  sa.store_pairs = store_pairs ? 1 : 0;
   if (!plan.fits()) { err = "per-lane scoring state exceeds the LDS budget"; return ANX_ELIMIT; }  // (the small call hands such a call to this path)
+  return ANX_OK;
+}
+// slot lists for the pairs the fused kernel cannot score inline: strings of 17..32 symbols (8-word kernel) and everything
+// else (longer strings, d > 3).  Only a batch that can have such pairs allocates and walks them (the small call: fixed buffers, always)
+static bool score_stage_needs_lists(const ScorePlan& plan, const DeviceLexicon* dl) { return !plan.fastD || plan.have_long_q || dl->max_len > 16; }
+struct ScoreStage {   // the arrays and sizes of one scoring stage (the caller owns and has sized all of them)
+  uint32_t nq;
+  int stop;                          // StopAtExactMatch
+  uint32_t region_shift, fill_cap;   // the pair list: log2(slots per region), slots per region the grid covers
+  uint32_t blk;                      // slots per block of k_filter_score (FilterArgs::blk)
+  bool one_launch;                   // the slot-list kernels as the small call's single launch, k_small_lists (plan.threads == 256), else the batch path's separate launches
+  const uint2* raw;
+  const uint32_t* q_meta;
+  const uint4 *q_rows, *q_rec;
+  const uint32_t* qexact;
+  double* p_score;                   // per-slot outputs, or nullptr (store_pairs == 0)
+  uint32_t* p_meta;
+  uint32_t* qsurv;                   // [3][nq]: qsurv, qmaxfreq, qexpand
+  uint32_t *rctr, *sctr, *lctr, *counters;
+  SurvOut so;
+  bool need_lists;
+  uint32_t *list8, *listg, *listw;
+  uint32_t list_cap;
+  FsCold* h_cold;                    // pinned staging copy of k_filter_score's rarely used arguments, and where they go on the device
+  void* d_cold;
+  hipEvent_t ev_fs0, ev_fs1;         // around k_filter_score alone (nullptr: not recorded)
+};
+static int score_stage_launch(const DeviceLexicon* dl, const ScorePlan& plan, const ScoreStage& S, hipStream_t st, std::string& err) {
+  const uint32_t nq = S.nq;
+  HIP_TRY(hipMemsetAsync(S.qsurv, 0, (dl->any_variants ? 3 : 2) * (size_t)nq * sizeof(uint32_t), st));  // qsurv, qmaxfreq (, qexpand)
+  const ScoreArgs& sa = plan.sa;
   const int fastD = plan.fastD;
+  const SurvOut& so = S.so;
+  const SlotLists sl = slot_lists_of(S.list8, S.listg, S.listw, S.lctr, S.list_cap);
+  const PairArgs pa = pair_args_of(dl, S.raw, S.q_meta, S.q_rows, S.q_rec, S.p_score, S.p_meta, S.qsurv + nq, S.qsurv, S.qsurv + 2 * (size_t)nq);
+  FilterArgs fa;
+  fa.region_shift = S.region_shift; fa.rctr = S.rctr; fa.qexact = S.qexact; fa.stop = S.stop; fa.enable = plan.enable_filter;
+  // pairs with a string of 17..32 symbols go to the 8-word register DL also when no QUERY is that long (the few 17..19-symbol candidates
+  // of a short-query batch): until round 6 those went to the general LDS kernel, whose one round cost 0.05 ms (scoring stage of BASELINE
+  // configs[1] 0.555 -> 0.53 ms; the three slot-list kernels as ONE launch, k_small_lists, on top of that: 0.527, not kept)
+  // (the small call: only when k_small_lists runs, threads == 256)
+  fa.use_nw8 = (plan.have_long_q || fastD > 0) ? 1 : 0; fa.counters = S.counters; fa.stat_ctr = S.sctr; fa.fill_cap = S.fill_cap; fa.blk = S.blk;
+  const dim3 fgrid(((S.fill_cap + S.blk - 1) / S.blk) * SCAN_REGIONS);
+  // k_filter_score's rarely used arguments: uploaded with every run (the small call keeps them on the device until they change)
+  *S.h_cold = FsCold{sa, so, sl.l8, sl.lg, sl.lw};
+  HIP_TRY(hipMemcpyAsync(S.d_cold, S.h_cold, sizeof(FsCold), hipMemcpyHostToDevice, st));
+  if (S.ev_fs0) HIP_TRY(hipEventRecord(S.ev_fs0, st));  // ev_fs0 .. ev_fs1 = k_filter_score alone (anx_batch_stats.ms_filter_score_kernel)
+  // (split_wide, round 6: for batches with long queries as well -- BASELINE configs[2]: 9.68 -> 9.52 ms per pass, configs[3]'s share:
+  // 6.73 -> 6.42 ms per 1 M queries)
+  launch_filter_score(plan, fgrid, st, fa, pa, static_cast<const FsCold*>(S.d_cold));
+  if (S.ev_fs1) HIP_TRY(hipEventRecord(S.ev_fs1, st));
+  const int do_wide = (plan.split_wide && plan.enable_filter) ? 1 : 0;
+  if (S.need_lists && S.one_launch) {  // as small_find launches them (small_path.hpp), a block per region
+    launch_small_lists_of(plan, st, sl, fa, pa, so);
+  } else if (S.need_lists) {  // the list fills are only known on the device: fixed grids walk the lists in strides
+    const dim3 lgrid(LIST_P * SCAN_REGIONS);
+    if (do_wide) hipLaunchKernelGGL(k_filter_wide, lgrid, dim3(256), 0, st, sl.lw, fa, pa, sa, fastD, sl.l8, sl.lg);
+    if (fastD) launch_score_fast8(fastD, lgrid, st, sl.l8, pa, sa, so);  // (the small call's separate launches: only with long queries)
+    hipLaunchKernelGGL(k_score_pairs, lgrid, dim3(plan.threads), plan.lds_bytes(), st, sl.lg, pa, sa, so);
+  }
+  return ANX_OK;
+}
+
+int Run::score() {
+  int rc;
+  ScorePlan plan;
+  if ((rc = score_stage_plan(m, dl, b->params.score_threshold, b->qw, b->dmax, b->keep_all_pairs, plan, err))) return rc;
+  if (plan.sa.store_pairs && (rc = ensure_pair_outputs(b, err))) return rc;
   // survivor records: region r of the survivor list takes the survivors of region r of the pair list.  Sized from the
   // previous run (first run: half the slots the grid covers -- ~10 % of the slots survive on config 2); an overflow is
   // detected by batch_finish and the run repeated with the measured size
   if ((rc = ensure_surv_records(b, b->prev_surv_fill ? (size_t)b->prev_surv_fill + (b->prev_surv_fill >> 3) + 256 : (size_t)fill_cap / 2 / cap_div() + 256, err))) return rc;
   so = SurvOut{b->surv, b->sctr, (uint32_t)b->surv_region_cap, nullptr, seg_capacity(dl, b)};
   so.seg = so.seg_cap ? b->sseg : nullptr;
-  // slot lists for the pairs the fused kernel cannot score inline: strings of 17..32 symbols (8-word kernel) and everything
-  // else (longer strings, d > 3).  Only a batch that can have such pairs allocates and walks them (the small call: fixed buffers, always)
-  const bool need_lists = !fastD || plan.have_long_q || dl->max_len > 16;
+  const bool need_lists = score_stage_needs_lists(plan, dl);
   // without the inline DL (d > 3) every length-compatible pair goes to the general list; else the prefilter passes ~1/3
-  if (need_lists && (rc = ensure_slot_lists(b, b->prev_list_fill ? (size_t)b->prev_list_fill + (b->prev_list_fill >> 3) + 256 : (fastD ? (size_t)fill_cap / 2 : (size_t)fill_cap) / cap_div() + 256, err)))
+  if (need_lists && (rc = ensure_slot_lists(b, b->prev_list_fill ? (size_t)b->prev_list_fill + (b->prev_list_fill >> 3) + 256 : (plan.fastD ? (size_t)fill_cap / 2 : (size_t)fill_cap) / cap_div() + 256, err)))
     return rc;
-  const SlotLists sl = slot_lists_of(b->list8, b->listg, b->listw, b->lctr, (uint32_t)b->list_cap);
-  const PairArgs pa = pair_args_of(dl, b->raw, b->q_meta, b->q_rows, b->q_rec, b->p_score, b->p_meta, b->qmaxfreq, b->qsurv, b->qexpand);
-  FilterArgs fa;
-  fa.region_shift = b->region_shift; fa.rctr = b->rctr; fa.qexact = b->qexact; fa.stop = stop; fa.enable = plan.enable_filter;
-  // pairs with a string of 17..32 symbols go to the 8-word register DL also when no QUERY is that long (the few 17..19-symbol candidates
-  // of a short-query batch): until round 6 those went to the general LDS kernel, whose one round cost 0.05 ms (scoring stage of BASELINE
-  // configs[1] 0.555 -> 0.53 ms; the three slot-list kernels as ONE launch, k_small_lists, on top of that: 0.527, not kept)
-  // (the small call: only when k_small_lists runs, threads == 256)
-  fa.use_nw8 = (plan.have_long_q || fastD > 0) ? 1 : 0; fa.counters = b->counters; fa.stat_ctr = b->sctr; fa.fill_cap = fill_cap; fa.blk = FS_BLK;
-  const dim3 fgrid(((fill_cap + FS_BLK - 1) / FS_BLK) * SCAN_REGIONS);
-  {
-    // k_filter_score's rarely used arguments: uploaded with every run (the small call keeps them on the device until they change)
-    FsCold* cold = reinterpret_cast<FsCold*>(reinterpret_cast<char*>(b->h_read) + HR_COLD_OFF);  // pinned: a truly asynchronous copy
-    *cold = FsCold{sa, so, sl.l8, sl.lg, sl.lw};
-    if (!b->d_cold && (rc = dalloc(reinterpret_cast<char**>(&b->d_cold), sizeof(FsCold), err))) return rc;
-    HIP_TRY(hipMemcpyAsync(b->d_cold, cold, sizeof(FsCold), hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(hipEventRecord(b->ev_fs0, st));  // ev_fs0 .. ev_fs1 = k_filter_score alone (anx_batch_stats.ms_filter_score_kernel)
-  // (split_wide, round 6: for batches with long queries as well -- BASELINE configs[2]: 9.68 -> 9.52 ms per pass, configs[3]'s share:
-  // 6.73 -> 6.42 ms per 1 M queries)
-  launch_filter_score(plan, fgrid, st, fa, pa, static_cast<const FsCold*>(b->d_cold));
-  HIP_TRY(hipEventRecord(b->ev_fs1, st));
-  if (need_lists) {  // the list fills are only known on the device: fixed grids walk the lists in strides
-    const dim3 lgrid(LIST_P * SCAN_REGIONS);
-    if (plan.split_wide && plan.enable_filter) hipLaunchKernelGGL(k_filter_wide, lgrid, dim3(256), 0, st, sl.lw, fa, pa, sa, fastD, sl.l8, sl.lg);
-    if (fastD) launch_score_fast8(fastD, lgrid, st, sl.l8, pa, sa, so);  // (the small call's separate launches: only with long queries)
-    hipLaunchKernelGGL(k_score_pairs, lgrid, dim3(plan.threads), plan.lds_bytes(), st, sl.lg, pa, sa, so);
-  }
+  if (!b->d_cold && (rc = dalloc(reinterpret_cast<char**>(&b->d_cold), sizeof(FsCold), err))) return rc;
+  ScoreStage S{};
+  S.nq = nq; S.stop = stop; S.region_shift = b->region_shift; S.fill_cap = fill_cap; S.blk = FS_BLK; S.one_launch = false;
+  S.raw = b->raw; S.q_meta = b->q_meta; S.q_rows = b->q_rows; S.q_rec = b->q_rec; S.qexact = b->qexact; S.p_score = b->p_score; S.p_meta = b->p_meta;
+  S.qsurv = b->qsurv; S.rctr = b->rctr; S.sctr = b->sctr; S.lctr = b->lctr; S.counters = b->counters; S.so = so;
+  S.need_lists = need_lists; S.list8 = b->list8; S.listg = b->listg; S.listw = b->listw; S.list_cap = (uint32_t)b->list_cap;
+  S.h_cold = reinterpret_cast<FsCold*>(reinterpret_cast<char*>(b->h_read) + HR_COLD_OFF);  // pinned: a truly asynchronous copy
+  S.d_cold = b->d_cold; S.ev_fs0 = b->ev_fs0; S.ev_fs1 = b->ev_fs1;
+  if ((rc = score_stage_launch(dl, plan, S, st, err))) return rc;
   HIP_TRY(hipEventRecord(b->ev[2], st));
   return ANX_OK;
 }
@@ -2167,6 +2212,153 @@ int debug_rank_rows(int device, const DebugRankIn& in, uint32_t* out_count, void
       (total && (e = hipMemcpy(out_rows, d_out, total * sizeof(DevRow), hipMemcpyDeviceToHost)) != hipSuccess))
     return fail_hip(e);
   cleanup();
+  return ANX_OK;
+}
+
+// ---- test hook: the scoring stage alone on a pair list the caller laid out (anx_debug_score_slots; tests/test_gpu_score_slots.py) ------
+// The band-match bound (kernels_swar.hpp band_bound_rejects) on the host: positions of either string without an equal symbol of the other
+// one within +-d positions; more than d of them on a side rejects the pair.
+static bool host_band_bound_rejects(const uint8_t* q, int lq, const uint8_t* c, int lc, int d) {
+  int unA = 0, unB = 0;
+  for (int i = 0; i < lq; ++i) {
+    bool hit = false;
+    for (int j = std::max(0, i - d); j <= std::min(lc - 1, i + d); ++j) hit = hit || q[i] == c[j];
+    unA += !hit;
+  }
+  for (int j = 0; j < lc; ++j) {
+    bool hit = false;
+    for (int i = std::max(0, j - d); i <= std::min(lq - 1, j + d); ++i) hit = hit || q[i] == c[j];
+    unB += !hit;
+  }
+  return unA > d || unB > d;
+}
+// Everything is checked on the host before the first launch (a wrong test input is refused, never gathered from); the device buffers of
+// the stage are the hook's own (the batch keeps its pair list and results), filled with 0xFF bytes, and launched through
+// score_stage_launch like a run's.
+int debug_score_slots(const HostModel& m, const DeviceLexicon* dl, const Batch* b, const DebugScoreIn& in, const DebugScoreOut& out, std::string& err) {
+  if (!dl || !b) { err = "score slots: the model is not resident on a device"; return ANX_ENODEVICE; }
+  const size_t nq = b->nq, n_input = b->n_input, C = in.seg_cap;
+  const uint32_t region_cap = 1u << (in.region_shift & 31u);
+  auto refuse = [&](const std::string& msg) { err = "score slots: " + msg; return ANX_EINVAL; };
+  if (in.region_shift < 10 || in.region_shift > 16) return refuse("region_shift outside 10 .. 16");
+  if (in.surv_region_cap == 0 || in.list_cap == 0) return refuse("a capacity of 0");
+  if (in.surv_region_cap > (1u << 16) || in.list_cap > (1u << 16)) return refuse("a capacity beyond 65536 per region");
+  if (in.blk == 0 || in.blk % 256 != 0 || in.blk > FS_BLK) return refuse("blk is no multiple of 256 up to " + std::to_string(FS_BLK));
+  if (nq == 0 || nq >= ((size_t)1 << 20)) return refuse("the batch holds no query (or more than 2^20)");
+  if (C && (C > 1024 || seg_wanted(b) == 0 || dl->any_variants)) return refuse("no per-query segments for this model and batch (variant lists, StopAtExactMatch, freq_weight, switch)");
+  for (uint32_t r = 0; r < SCAN_REGIONS; ++r)
+    if (in.fills[r] > region_cap) return refuse("fill of region " + std::to_string(r) + " beyond the region");
+  HIP_TRY(hipSetDevice(dl->device));
+  { const int rc = ensure_order(b, err); if (rc) return rc; }
+  const int stop = b->params.stop_at_exact_match ? 1 : 0;
+  ScorePlan plan;
+  { const int rc = score_stage_plan(m, dl, b->params.score_threshold, b->qw, b->dmax, true, plan, err); if (rc) return rc; }
+  if (in.one_launch && plan.threads != 256) return refuse("the one-launch list kernels take 256 threads: the per-lane state of this model and batch allows " + std::to_string(plan.threads));
+  // what the checks read: the queries' and entries' records (first 16 symbols, meta)
+  std::vector<uint32_t> pos_of(n_input, 0xFFFFFFFFu);
+  for (size_t q = 0; q < nq; ++q) if (b->order[q] < n_input) pos_of[b->order[q]] = (uint32_t)q;
+  std::vector<uint4> qrec(2 * nq), erec(2 * (size_t)dl->nentries + 2);
+  HIP_TRY(hipMemcpy(qrec.data(), b->q_rec, 2 * nq * sizeof(uint4), hipMemcpyDeviceToHost));
+  if (dl->nentries) HIP_TRY(hipMemcpy(erec.data(), dl->e_rec, 2 * (size_t)dl->nentries * sizeof(uint4), hipMemcpyDeviceToHost));
+  const bool bit_planes = dl->nsym <= 32 && !switches().scan_sad;
+  std::vector<uint2> raw((size_t)SCAN_REGIONS << in.region_shift, make_uint2(RAW_INVALID, 0xFFFFFFFFu));
+  {
+    size_t i = 0;
+    for (uint32_t r = 0; r < SCAN_REGIONS; ++r)
+      for (uint32_t k = 0; k < in.fills[r]; ++k, ++i) {
+        const uint32_t qi = in.slots[2 * i], ew = in.slots[2 * i + 1];
+        if (qi == RAW_INVALID) continue;
+        const std::string at = " (slot " + std::to_string(k) + " of region " + std::to_string(r) + ")";
+        if (qi >= n_input || pos_of[qi] == 0xFFFFFFFFu) return refuse("query index out of range or not encoded" + at);
+        // the entry id as the GENERAL round reads it (30 bits): a flagged slot of a mixed wave is gathered there, not under the short round's 26-bit mask
+        const uint32_t q = pos_of[qi], e = ew & RAW_ENTRY_MASK;
+        if (e >= dl->nentries) return refuse("entry id out of range" + at);
+        if ((ew & 0x80000000u) && !stop) return refuse("bit 31 (exact class) outside a StopAtExactMatch batch" + at);
+        if (ew & RAW_PREFILTERED) {  // the scan's contract (kernels_scan.hpp, the fused prefilter of emit_dense)
+          const uint32_t qm = qrec[2 * (size_t)q + 1].x, em = erec[2 * (size_t)e + 1].x;
+          const int lq = qm & 0xFF, d = (qm >> 16) & 0xFF, lc = em & 0xFF;
+          if (!bit_planes || stop || (ew & 0x80000000u)) return refuse("RAW_PREFILTERED outside a bit-plane model or in a StopAtExactMatch batch" + at);
+          if (e >= (1u << 26)) return refuse("RAW_PREFILTERED with an entry id beyond 2^26" + at);
+          if (lq > 16 || lc > 16 || d > 3 || std::abs(lq - lc) > d) return refuse("RAW_PREFILTERED on a pair the scan does not filter (lengths, d)" + at);
+          if (host_band_bound_rejects(reinterpret_cast<const uint8_t*>(&qrec[2 * (size_t)q]), lq, reinterpret_cast<const uint8_t*>(&erec[2 * (size_t)e]), lc, d))
+            return refuse("RAW_PREFILTERED on a pair the band-match bound rejects" + at);
+        }
+        raw[((size_t)r << in.region_shift) + k] = make_uint2(q, ew);
+      }
+  }
+  // ---- device buffers of the stage ------------------------------------------------------------------------------------------------------
+  const size_t R = raw.size(), nsurv = (size_t)SCAN_REGIONS * in.surv_region_cap, nlist = (size_t)SCAN_REGIONS * in.list_cap;
+  uint2* d_raw = nullptr;
+  double* d_pscore = nullptr;
+  uint32_t *d_pmeta = nullptr, *d_ctl = nullptr, *d_q3 = nullptr, *d_lists = nullptr;
+  SurvRec* d_surv = nullptr;
+  SurvSeg* d_seg = nullptr;
+  void* d_cold = nullptr;
+  FsCold* h_cold = nullptr;
+  auto cleanup = [&]() {
+    for (void* p : {(void*)d_raw, (void*)d_pscore, (void*)d_pmeta, (void*)d_ctl, (void*)d_q3, (void*)d_lists, (void*)d_surv, (void*)d_seg, d_cold}) if (p) (void)hipFree(p);
+    if (h_cold) (void)hipHostFree(h_cold);
+  };
+  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
+  hipError_t e;
+  if ((e = hipMalloc(reinterpret_cast<void**>(&d_raw), R * sizeof(uint2))) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_pscore), R * 8)) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_pmeta), R * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_ctl), HR_N * 4)) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_q3), 3 * nq * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_lists), 3 * nlist * 4)) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_surv), nsurv * sizeof(SurvRec))) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_seg), (nq * C + 1) * sizeof(SurvSeg))) != hipSuccess ||
+      (e = hipMalloc(&d_cold, sizeof(FsCold))) != hipSuccess || (e = hipHostMalloc(reinterpret_cast<void**>(&h_cold), sizeof(FsCold), hipHostMallocDefault)) != hipSuccess)
+    return fail_hip(e);
+  std::vector<uint32_t> ctl(HR_N, 0u);
+  for (uint32_t r = 0; r < SCAN_REGIONS; ++r) ctl[HR_RCTR + r * RC_STRIDE + RC_RAW] = in.fills[r];
+  if ((e = hipMemcpy(d_raw, raw.data(), R * sizeof(uint2), hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_ctl, ctl.data(), HR_N * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemset(d_pscore, 0xFF, R * 8)) != hipSuccess || (e = hipMemset(d_pmeta, 0xFF, R * 4)) != hipSuccess || (e = hipMemset(d_q3, 0xFF, 3 * nq * 4)) != hipSuccess ||
+      (e = hipMemset(d_lists, 0xFF, 3 * nlist * 4)) != hipSuccess || (e = hipMemset(d_surv, 0xFF, nsurv * sizeof(SurvRec))) != hipSuccess ||
+      (e = hipMemset(d_seg, 0xFF, (nq * C + 1) * sizeof(SurvSeg))) != hipSuccess)
+    return fail_hip(e);
+  ScoreStage S{};
+  S.nq = (uint32_t)nq; S.stop = stop; S.region_shift = in.region_shift; S.fill_cap = region_cap; S.blk = in.blk; S.one_launch = in.one_launch != 0;
+  S.raw = d_raw; S.q_meta = b->q_meta; S.q_rows = b->q_rows; S.q_rec = b->q_rec; S.qexact = b->qexact; S.p_score = d_pscore; S.p_meta = d_pmeta;
+  S.qsurv = d_q3; S.rctr = d_ctl + HR_RCTR; S.sctr = d_ctl + HR_SCTR; S.lctr = d_ctl + HR_LCTR; S.counters = d_ctl + HR_CTR;
+  S.so = SurvOut{d_surv, d_ctl + HR_SCTR, in.surv_region_cap, C ? d_seg : nullptr, (uint32_t)C};
+  S.need_lists = score_stage_needs_lists(plan, dl); S.list8 = d_lists; S.listg = d_lists + nlist; S.listw = d_lists + 2 * nlist; S.list_cap = in.list_cap;
+  S.h_cold = h_cold; S.d_cold = d_cold; S.ev_fs0 = nullptr; S.ev_fs1 = nullptr;
+  { const int rc = score_stage_launch(dl, plan, S, 0, err); if (rc) { cleanup(); return rc; } }
+  // ---- everything back, in the caller's terms (input indices, slots in the caller's order) ---------------------------------------------
+  std::vector<uint32_t> pmeta(R), q3(3 * nq);
+  std::vector<double> pscore(R);
+  std::vector<SurvRec> surv(nsurv);
+  std::vector<SurvSeg> seg(nq * C + 1);
+  if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(pmeta.data(), d_pmeta, R * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (e = hipMemcpy(pscore.data(), d_pscore, R * 8, hipMemcpyDeviceToHost)) != hipSuccess || (e = hipMemcpy(q3.data(), d_q3, 3 * nq * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (e = hipMemcpy(ctl.data(), d_ctl, HR_N * 4, hipMemcpyDeviceToHost)) != hipSuccess || (e = hipMemcpy(surv.data(), d_surv, nsurv * sizeof(SurvRec), hipMemcpyDeviceToHost)) != hipSuccess ||
+      (e = hipMemcpy(seg.data(), d_seg, (nq * C + 1) * sizeof(SurvSeg), hipMemcpyDeviceToHost)) != hipSuccess)
+    return fail_hip(e);
+  cleanup();
+  {
+    size_t i = 0;
+    for (uint32_t r = 0; r < SCAN_REGIONS; ++r)
+      for (uint32_t k = 0; k < in.fills[r]; ++k, ++i) {
+        out.meta[i] = pmeta[((size_t)r << in.region_shift) + k];
+        out.score[i] = pscore[((size_t)r << in.region_shift) + k];
+      }
+  }
+  for (size_t q = 0; q < nq; ++q) {
+    const uint32_t qi = b->order[q];
+    if (qi >= n_input) continue;
+    for (int k = 0; k < 3; ++k) out.qcount[k * n_input + qi] = q3[k * nq + q];
+    if (C) memcpy(static_cast<char*>(out.seg) + (size_t)qi * C * sizeof(SurvSeg), &seg[q * C], C * sizeof(SurvSeg));
+  }
+  for (uint32_t r = 0; r < SCAN_REGIONS; ++r) {
+    const uint32_t fill = ctl[HR_SCTR + r * RC_STRIDE];
+    for (uint32_t k = 0; k < std::min(fill, in.surv_region_cap); ++k) {  // (written records: the query as its input index)
+      SurvRec& s = surv[(size_t)r * in.surv_region_cap + k];
+      if (s.q < nq) s.q = b->order[s.q];
+    }
+    out.ctr[0 * SCAN_REGIONS + r] = fill;
+    for (uint32_t l = 0; l < 3; ++l) out.ctr[(1 + l) * SCAN_REGIONS + r] = ctl[HR_LCTR + (l * SCAN_REGIONS + r) * RC_STRIDE];
+    out.ctr[4 * SCAN_REGIONS + r] = ctl[HR_SCTR + r * RC_STRIDE + 1];
+  }
+  memcpy(out.surv, surv.data(), nsurv * sizeof(SurvRec));
+  *out.skipped = ctl[HR_CTR + CTR_SKIPPED];
   return ANX_OK;
 }
 

@@ -124,6 +124,13 @@ static inline void launch_small_lists(const ScorePlan& pl, hipStream_t st, const
   else hipLaunchKernelGGL(k_small_lists<0>, grid, dim3(256), dyn, st, L, fa, pa, pl.sa, so);
 }
 
+// the one launch as small_find and the scoring door (engine.hip score_stage_launch) both make it, for a plan of 256 threads: the deferred wide
+// prefilter when the plan splits it off, k_score_fast8's part whenever the batch has the inline DL (long queries or not: use_nw8 is on then)
+static inline void launch_small_lists_of(const ScorePlan& pl, hipStream_t st, const SlotLists& sl, const FilterArgs& fa, const PairArgs& pa, const SurvOut& so) {
+  const int do_wide = (pl.split_wide && pl.enable_filter) ? 1 : 0;
+  launch_small_lists(pl, st, SmallListArgs{sl.lw, sl.l8, sl.lg, do_wide, pl.fastD ? 1 : 0, pl.fastD}, fa, pa, so);
+}
+
 // ---- rank ------------------------------------------------------------------------------------------------------------------------------
 // cutoff: the caller's cutoff_threshold, or 0 when something after k_rank cuts off instead (batch path, late device confusables)
 static inline RankArgs rank_args_of(const HostModel& m, const DeviceLexicon* dl, const anx_params& p, double cutoff) {

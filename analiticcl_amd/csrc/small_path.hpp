@@ -299,7 +299,7 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   launch_filter_score(plan, dim3(((fs_cap + SMALL_FS_BLK - 1) / SMALL_FS_BLK) * SCAN_REGIONS), st, fa, pa, static_cast<const FsCold*>(c->d_cold));
   const int do_wide = (plan.split_wide && plan.enable_filter) ? 1 : 0;
   if (threads == 256) {  // the slot-list kernels as one launch, a block per region (k_small_lists): k_score_fast8's part also for the long candidates of short queries
-    launch_small_lists(plan, st, SmallListArgs{sl.lw, sl.l8, sl.lg, do_wide, (fastD && (plan.have_long_q || use8)) ? 1 : 0, fastD}, fa, pa, so);
+    launch_small_lists_of(plan, st, sl, fa, pa, so);  // (use8 == fastD > 0 here: k_score_fast8's part runs whenever the inline DL does)
   } else {  // the per-lane state of k_score_pairs does not fit 256 lanes: the three kernels one by one, SMALL_LIST_BLOCKS blocks per region
     const dim3 lgrid(SMALL_LIST_BLOCKS * SCAN_REGIONS);
     if (do_wide) hipLaunchKernelGGL(k_filter_wide, lgrid, dim3(256), 0, st, sl.lw, fa, pa, sa, fastD, sl.l8, sl.lg);

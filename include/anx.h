@@ -41,7 +41,7 @@ extern "C" {
  *    anx_score_pairs_weighted / _packed, anx_model_confusable_weight_text and anx_debug_pairs_conf_stats: the confusable weight of
  *    such pairs (additive); the test hooks anx_debug_exclusive_scan and anx_debug_rank_rows (additive); anx_evaluate_gold /
  *    anx_evaluate_gold_packed, the struct anx_gold_eval, the ANX_GOLD_* reasons and the test hook anx_debug_evaluate_gold_chunk
- *    (additive, nothing else changed). */
+ *    (additive, nothing else changed); the test hook anx_debug_score_slots (additive). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -504,6 +504,36 @@ int anx_debug_rank_rows(int device, size_t nq, const uint32_t *counts, const uin
                         const uint32_t *freq, const uint32_t *via, double cutoff_threshold, uint64_t max_matches, float freq_weight,
                         int have_freq, int any_variants, uint32_t seg_cap, uint32_t row_cap, uint32_t overflow, uint32_t *out_count,
                         void *out_rows);
+/* Test hook: the scoring stage (k_filter_score, k_filter_wide, k_score_fast8, k_score_pairs / k_small_lists) alone, on a pair list the
+ * caller laid out.  `batch` = anx_batch_encode[_packed] on a resident single-device model (one shard); it need not have run and is left
+ * as it is: the stage's buffers are the hook's own.  The pair list has 64 regions of 2^region_shift slots (10 <= region_shift <= 16):
+ * fills[64] = the slots of every region, `slots` = those slots back to back, region after region, two words each: (query, entry word) or
+ * (UINT32_MAX, anything) = an unused slot of a chunk tail.  The query is the INPUT index (the hook translates to the batch's sorted
+ * order); the entry word is the entry id in anx_debug_entries' order, | 1 << 30 = "the scan applied its prefilter" (RAW_PREFILTERED),
+ * | 1 << 31 = "exact anagram class" (StopAtExactMatch batches only).
+ * seg_cap: 0, or C > 0 = per-query survivor segments of C records (refused where a run of this model and batch would not use them:
+ * variant lists, StopAtExactMatch, freq_weight != 0, ANX_SURV_SEG=0).  surv_region_cap / list_cap (1 .. 65536): records per region of the
+ * survivor list / entries per region of the three slot lists.  blk: slots per block of k_filter_score, a multiple of 256 up to 4096 (a
+ * run: 4096, the small call: 512).  one_launch != 0: the slot-list kernels as the small call's k_small_lists (refused when the model's
+ * longest entry leaves k_score_pairs fewer than 256 threads), else as the run's separate launches.  Thresholds, weights, score_threshold
+ * and StopAtExactMatch are the batch's; the launch is the run's own function (same kernel instances), with the per-slot outputs on.
+ * Everything is validated on the host BEFORE anything is launched, ANX_EINVAL otherwise: query < inputs (and encoded), entry < entries,
+ * fills <= 2^region_shift, capacities and blk in range, bit 31 only in a StopAtExactMatch batch, and bit 30 only on a pair inside the
+ * scan's contract (analiticcl_amd/csrc/kernels_scan.hpp, the fused prefilter: an alphabet of <= 32 symbols, no StopAtExactMatch, query and
+ * entry <= 16 symbols, the query's d <= 3, |lq - lc| <= d, and the band-match bound of anx_debug_band_bound does not reject the pair).
+ * Outputs, each starting as 0xFF bytes (also after a refusal; out_surv / out_seg only when the capacity that sizes them is in range,
+ * <= 65536 / <= 1024): out_meta[slots] (ld | samecase << 7 | lcs << 8 | prefix << 16 |
+ * suffix << 24; ld 0x7F = None; UINT32_MAX = skipped) and out_score[slots] in the order of `slots`; out_qcount[3][inputs] = qsurv,
+ * qmaxfreq, qexpand (the last only with variant lists); out_surv[64][surv_region_cap] 16-byte records {uint32 input, uint32 entry,
+ * double score}; out_ctr[5][64] = per region the survivor list's counter, the counters of the slot lists of the 8-word kernel, the
+ * general kernel and the deferred wide prefilter, and the selected pairs; out_seg[inputs][seg_cap] 16-byte records {double score,
+ * uint32 entry, uint32 0} (may be NULL with seg_cap 0); *out_skipped = pairs StopAtExactMatch dropped.
+ * tests/test_gpu_score_slots.py compares all of it exactly with the twin's measures and score (oracle/twin.py) on the slot layouts of
+ * tests/score_cases.py. */
+int anx_debug_score_slots(const anx_model *model, const anx_batch *batch, uint32_t region_shift, const uint32_t *fills,
+                          const uint32_t *slots, uint32_t seg_cap, uint32_t surv_region_cap, uint32_t list_cap, uint32_t blk,
+                          int one_launch, uint32_t *out_meta, double *out_score, uint32_t *out_qcount, void *out_surv,
+                          uint32_t *out_ctr, void *out_seg, uint32_t *out_skipped);
 
 /* ---- output of `analiticcl query` --------------------------------------------------
  * The TSV lines / JSON items of output_matches_as_tsv / output_matches_as_json (src/bin/analiticcl.rs:21-187) for n

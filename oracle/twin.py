@@ -525,6 +525,17 @@ class Distance:  # src/types.rs:289-305
     samecase: bool
 
 
+def pair_score(w: Weights, d: Distance, input_length: int) -> float:
+    """The distance score of one instance (src/lib.rs:1433-1452), f64 in the reference's association: what score_and_rank computes
+    per pair, by itself (tests/score_cases.py scores caller-chosen pairs with it)."""
+    distance_score = 0.0 if d.ld > input_length else 1.0 - (float(d.ld) / float(input_length))
+    lcs_score = float(d.lcs) / float(input_length)
+    prefix_score = float(d.prefixlen) / float(input_length)
+    suffix_score = float(d.suffixlen) / float(input_length)
+    return (w.ld * distance_score + w.lcs * lcs_score + w.prefix * prefix_score
+            + w.suffix * suffix_score + (w.case if d.samecase else 0.0)) / w.sum()
+
+
 class VariantModel:
     """src/lib.rs:50-100, query path only (no LM, no variant lists, no confusables)."""
 
@@ -773,17 +784,10 @@ class VariantModel:
         results: List[VariantResult] = []
         max_freq = 0.0
         has_expandable_variants = False
-        w = self.weights
-        weights_sum = w.sum()
         assert input_length > 0
         for vocab_id, d in instances:
             item = self.decoder[vocab_id]
-            distance_score = 0.0 if d.ld > input_length else 1.0 - (float(d.ld) / float(input_length))
-            lcs_score = float(d.lcs) / float(input_length)
-            prefix_score = float(d.prefixlen) / float(input_length)
-            suffix_score = float(d.suffixlen) / float(input_length)
-            score = (w.ld * distance_score + w.lcs * lcs_score + w.prefix * prefix_score
-                     + w.suffix * suffix_score + (w.case if d.samecase else 0.0)) / weights_sum
+            score = pair_score(self.weights, d, input_length)
             freq_score = float(item.frequency) if self.have_freq else 1.0
             if freq_score > max_freq:
                 max_freq = freq_score

@@ -165,6 +165,33 @@ static int shards_mode(const std::string& alphabet, const std::string& lexicon) 
         }
         anx_counts_free(counts);
         anx_pairs_free(pairs);
+        {  // the scoring stage's test hook: the C-level argument checks (every refusal leaves the outputs as 0xFF bytes; the fake device has no stage)
+          const size_t n_in = in.size();
+          uint32_t fills[64] = {}, slots[4] = {0u, 0u, 0xFFFFFFFFu, 0u}, meta[2] = {1u, 1u}, ctr[5 * 64], skipped = 7u;
+          fills[0] = 1; fills[63] = 1;
+          double score[2] = {0.0, 0.0};
+          std::vector<uint32_t> qcount(3 * n_in, 0u);
+          std::vector<char> surv((size_t)64 * 8 * 16, 0), seg(n_in * 2 * 16, 0);
+          auto call = [&](const anx_model* mm, const anx_batch* bb, const uint32_t* f, const uint32_t* s, uint32_t segc, uint32_t cap, uint32_t* om, void* osg) {
+            return anx_debug_score_slots(mm, bb, 10, f, s, segc, cap, 8, 256, 0, om, score, qcount.data(), surv.data(), ctr, osg, &skipped);
+          };
+          CHECK(call(nullptr, b, fills, slots, 0, 8, meta, nullptr) == ANX_EINVAL && call(m, nullptr, fills, slots, 0, 8, meta, nullptr) == ANX_EINVAL);
+          CHECK(call(m, b, nullptr, slots, 0, 8, meta, nullptr) == ANX_EINVAL && call(m, b, fills, nullptr, 0, 8, meta, nullptr) == ANX_EINVAL);
+          CHECK(call(m, b, fills, slots, 0, 8, nullptr, nullptr) == ANX_EINVAL && call(m, b, fills, slots, 2, 8, meta, nullptr) == ANX_EINVAL);
+          CHECK(meta[0] == 1u && skipped == 7u);  // (NULL arguments: nothing touched)
+          CHECK(call(m, b, fills, slots, 0, 0, meta, nullptr) == ANX_EINVAL && call(m, b, fills, slots, 0, (1u << 16) + 1u, meta, nullptr) == ANX_EINVAL);
+          CHECK(call(m, b, fills, slots, 2000, 8, meta, seg.data()) == ANX_EINVAL);
+          // (capacities out of range: the survivor list and the segments, which they size, are not touched; the other outputs are 0xFF)
+          CHECK(meta[0] == 0xFFFFFFFFu && skipped == 0xFFFFFFFFu && surv[0] == 0 && seg[0] == 0);
+          const int rc = call(m, b, fills, slots, 2, 8, meta, seg.data());
+          CHECK(rc == (nrep == 1 && anx_batch_num_shards(b) == 1 ? ANX_ENODEVICE : ANX_EINVAL));  // several replicas / shards: refused; else the stub has no device
+          bool ff = meta[0] == 0xFFFFFFFFu && meta[1] == 0xFFFFFFFFu && skipped == 0xFFFFFFFFu;
+          for (size_t i = 0; i < qcount.size() && ff; ++i) ff = qcount[i] == 0xFFFFFFFFu;
+          for (size_t i = 0; i < surv.size() && ff; ++i) ff = (unsigned char)surv[i] == 0xFFu;
+          for (size_t i = 0; i < seg.size() && ff; ++i) ff = (unsigned char)seg[i] == 0xFFu;
+          for (size_t i = 0; i < 5 * 64 && ff; ++i) ff = ctr[i] == 0xFFFFFFFFu;
+          CHECK(ff);
+        }
         if (nrep != 3) {  // compact records over the shards == the anx_result rows
           anx_topk_record* cr = nullptr; uint32_t* co = nullptr;
           CHECK(anx_batch_fetch_compact(b, &cr, &co) == ANX_OK);
