@@ -1172,6 +1172,7 @@ bool kernel_timer_read(const char* name, double* total_ms, uint64_t* launches) {
 template <int NP>
 static void launch_scan(ScanArgs A, uint32_t nadj, uint32_t nbits, uint32_t nsad, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   // tiles: [bit-plane tiles with an adjacency list | other bit-plane tiles | SAD kind]
+  const int kt = ktimer_begin("k_scan", st);  // (off unless anx_debug_kernel_timer(1); its launch count = the runs of a batch, repeats after an overflow included)
   (void)hipEventRecord(e0, st);  // e0 .. e1 = k_scan_adj + k_scan_bits (anx_batch_stats.ms_scan_kernel)
   const bool gen = A.want_exact || A.qpairs || !A.drop_len;
   if (nadj) {
@@ -1193,6 +1194,7 @@ static void launch_scan(ScanArgs A, uint32_t nadj, uint32_t nbits, uint32_t nsad
     A.ntiles = nsad;
     hipLaunchKernelGGL((k_scan_sad<NP>), dim3((nsad + 3) / 4), dim3(256), 0, st, A);
   }
+  ktimer_end(kt, st);
 }
 
 static int ensure_raw(Batch* b, size_t slots_per_region, std::string& err) {
@@ -1372,6 +1374,7 @@ int Run::scan() {
     A.tiles = b->d_tiles; A.ntiles = b->ntiles; A.q_bits = b->q_bits; A.q_cv = b->q_cv;
     A.chunk = SCAN_CHUNK;  // (the small call: 64 / 32)
     A.chunk_fused = switches().scan_chunk_fused ? (uint32_t)switches().scan_chunk_fused : SCAN_CHUNK_FUSED;
+    A.chunk_first = switches().scan_chunk_first ? (uint32_t)switches().scan_chunk_first : SCAN_CHUNK_FIRST;  // (the kernel caps it at the tile's chunk)
 #ifdef ANX_DEBUG_SWITCHES
     { const char* e = getenv("ANX_SCAN_CHUNK"); const int v = e ? atoi(e) : 0; if (v >= 32 && v <= 1024) A.chunk = (uint32_t)v; }
 #endif
@@ -1620,6 +1623,18 @@ static int batch_finish(const HostModel& m, const DeviceLexicon* dl, Batch* b, b
   // ---- did the run fit what the launch assumed? ------------------------------------------------------------
   int rc;
   bool again = false;
+  size_t surv_need = total_surv;
+  {
+    // a pair list that overflowed, or reached beyond the scoring grid, gave the later stages only the slots that fit: what they
+    // measured is scaled up to the whole list, so that the repeated run does not overflow their buffers in turn (a second repeat)
+    const uint32_t covered = std::min(1u << b->region_shift, b->fill_cap_launched);
+    if (maxfill > covered && covered) {
+      const double f = (double)maxfill / covered;
+      surv_fill = (uint32_t)std::min(surv_fill * f, 4.0e9);
+      list_fill = (uint32_t)std::min(list_fill * f, 4.0e9);
+      surv_need = (size_t)(total_surv * f);
+    }
+  }
   if (maxfill > (1u << b->region_shift)) {  // pair list
     if ((rc = ensure_raw(b, (size_t)maxfill + (maxfill >> 3) + 4096, err))) return rc;
     again = true;
@@ -1627,8 +1642,8 @@ static int batch_finish(const HostModel& m, const DeviceLexicon* dl, Batch* b, b
   if (maxfill > b->fill_cap_launched) again = true;  // slots the scoring grid did not cover
   if ((size_t)surv_fill > b->surv_region_cap) again = true;
   if (list_fill && (size_t)list_fill > b->list_cap) again = true;
-  if (!dl->any_variants && (size_t)total_surv > b->surv_cap) {
-    if ((rc = ensure_surv(b, (size_t)total_surv + (total_surv >> 2) + 1024, err))) return rc;
+  if (!dl->any_variants && surv_need > b->surv_cap) {
+    if ((rc = ensure_surv(b, surv_need + (surv_need >> 2) + 1024, err))) return rc;
     again = true;
   }
   b->prev_maxfill = std::max(b->prev_maxfill, maxfill);

@@ -543,6 +543,7 @@ const SwitchDef kSwitches[] = {
     {"ANX_ADJ_BUILD", [](Switches& s, const char* v) { s.adj_build_host = v && strcmp(v, "host") == 0; }},
     {"ANX_ADJ_CLOSURE", [](Switches& s, const char* v) { const int x = v ? atoi(v) : 2; s.adj_closure = x >= 0 && x <= kAdjMaxClosure ? x : kAdjMaxClosure; }},
     {"ANX_SCAN_CHUNK_FUSED", [](Switches& s, const char* v) { const int x = v ? atoi(v) : 0; s.scan_chunk_fused = x >= 32 && x <= 1024 ? x : 0; }},
+    {"ANX_SCAN_CHUNK_FIRST", [](Switches& s, const char* v) { const int x = v ? atoi(v) : 0; s.scan_chunk_first = x >= 32 && x <= 1024 ? x / 32 * 32 : 0; }},
     {"ANX_ADJ_FAIL", [](Switches& s, const char* v) { s.adj_fail = flag01(v, 0); }},
     {"ANX_SMALL", [](Switches& s, const char* v) { s.small_path = flag01(v, 1); }},
     {"ANX_SURV_SEG", [](Switches& s, const char* v) { const int x = v ? atoi(v) : 32; s.surv_seg = x >= 0 && x <= 256 ? x : 32; }},

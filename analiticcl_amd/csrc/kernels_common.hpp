@@ -47,7 +47,8 @@ constexpr uint32_t SCAN_MASKW = 2048;    // stream positions per window of run-e
 constexpr uint32_t SCAN_PBUF = 128;      // per-wave LDS ring of dense pairs awaiting the fused filter (< 64 waiting + <= 64 new)
 constexpr uint32_t SCAN_CHUNK = 256;     // pair slots a wave reserves per global atomic
 constexpr uint32_t SCAN_CHUNK_FUSED = 128;  // ... in tiles whose pairs pass the fused prefilter first (a third survives)
-constexpr uint32_t SCAN_REGIONS = 64;     // pair-list regions with one reservation counter each
+constexpr uint32_t SCAN_CHUNK_FIRST = 32;   // a wave's first reservation; every further one doubles, up to the chunk (tiles of <= 4 queries are half the tiles and hold a handful of pairs)
+constexpr uint32_t SCAN_REGIONS = 64;    // pair-list regions with one reservation counter each
 constexpr uint32_t RC_STRIDE = 32;        // uint32 words per region counter block (128 B)
 constexpr uint32_t RAW_INVALID = 0xFFFFFFFFu;
 constexpr uint32_t RAW_ENTRY_MASK = 0x3FFFFFFFu;   // entry id of a pair (bit 31: exact anagram class, StopAtExactMatch)

@@ -17,8 +17,11 @@
 //   every query of the tile (query planes broadcast from LDS).  On eng.aspell k<=3 this leaves 4.6 k of the
 //   68 k class tests per query that the plain charcount window needs.
 //   The query loop is branch-free: every lane keeps one hit bit per (class, query) in registers; after the loop
-//   the hits of the chunk (1-2 % of the remaining tests) are expanded through the class -> entries CSR into
-//   wave-private 256-slot chunks of the pair list.  The pair list is split into SCAN_REGIONS regions with one
+//   the hits of the chunk (1-2 % of the remaining tests) go to the wave's LDS hit list -- rows of an adjacency list whose
+//   record length fails the DL's length test are only counted (production instance) -- and the list is expanded, when
+//   another chunk could overflow it, through the class -> entries CSR (bit-plane tiles: the entry id is in the list) into
+//   wave-private reservations of the pair list (256 slots; behind the fused filter they start at SCAN_CHUNK_FIRST slots
+//   and double up to 128).  The pair list is split into SCAN_REGIONS regions with one
 //   reservation counter each (128 B apart): a single contended counter word sustains only ~88 M atomics/s, which
 //   at ~1.5 ms per million queries would be the bottleneck.
 // ------------------------------------------------------------------------------------------------
@@ -32,8 +35,12 @@ struct WaveOut {
   uint32_t split;       // run indices < split go to [base..), the rest to [nbase..)
   uint32_t rbase, rend; // this wave's region of the pair list: slots [rbase, rend)
   uint32_t* ctr;        // the region's counter block
-  uint32_t chunk;       // slots reserved per global atomic
+  uint32_t sizes;       // low half: slots the NEXT reservation takes; high half: the most a reservation takes (ScanArgs::chunk / chunk_fused,
+                        // <= 1024).  Every reservation doubles the size up to that cap: most tiles hold a handful of pairs and left nearly
+                        // a whole chunk of RAW_INVALID slots for k_filter_score to stream; a tile that fills chunks reaches the full
+                        // size after two reservations and pays no atomic more.  (One register: the GEN instance has none to spare.)
 };
+__device__ inline uint32_t wave_sizes(uint32_t first, uint32_t cap) { return (first < cap ? first : cap) | cap << 16; }
 // Wave-wide exclusive prefix sum of ntot + chunk reservation.  Returns this lane's first index g in the
 // wave's appended run; wave_slot(g) maps run indices to pair-list slots.  A run that does not fit in the
 // rest of the current chunk fills it up and continues in a freshly reserved chunk (ONE atomic).
@@ -57,7 +64,7 @@ __device__ inline uint32_t wave_reserve(WaveOut& w, uint32_t ntot, uint32_t lane
   w.split = w.left;
   if (total > w.left) {
     const uint32_t rest = total - w.left;
-    const uint32_t need = rest > w.chunk ? rest : w.chunk;
+    const uint32_t size = w.sizes & 0xFFFFu, need = rest > size ? rest : size;
     uint32_t b = 0;
     if (lane == 0) b = atomicAdd(&w.ctr[RC_RAW], need);
     w.nbase = w.rbase + __shfl(b, 0);
@@ -69,7 +76,7 @@ __device__ inline void wave_reserve_total(WaveOut& w, uint32_t total, uint32_t l
   w.split = w.left;
   if (total > w.left) {
     const uint32_t rest = total - w.left;
-    const uint32_t need = rest > w.chunk ? rest : w.chunk;
+    const uint32_t size = w.sizes & 0xFFFFu, need = rest > size ? rest : size;
     uint32_t b = 0;
     if (lane == 0) b = atomicAdd(&w.ctr[RC_RAW], need);
     w.nbase = w.rbase + (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
@@ -81,9 +88,11 @@ __device__ inline uint32_t wave_slot(const WaveOut& w, uint32_t g) {
 __device__ inline void wave_commit(WaveOut& w, uint32_t total) {
   if (total > w.left) {
     const uint32_t rest = total - w.left;
-    const uint32_t need = rest > w.chunk ? rest : w.chunk;
+    const uint32_t size = w.sizes & 0xFFFFu, need = rest > size ? rest : size;
     w.base = w.nbase + rest;
     w.left = need - rest;
+    const uint32_t cap = w.sizes >> 16;
+    w.sizes = (size * 2u < cap ? size * 2u : cap) | cap << 16;
   } else {
     w.base += total;
     w.left -= total;
@@ -124,6 +133,7 @@ struct ScanArgs {
   uint32_t region_cap;  // pair-list slots per region
   uint32_t chunk;       // pair-list slots a wave reserves per global atomic (SCAN_CHUNK; ANX_SCAN_CHUNK)
   uint32_t chunk_fused; // ... in tiles that run the fused prefilter
+  uint32_t chunk_first; // slots of a wave's FIRST reservation (WaveOut::sizes; ANX_SCAN_CHUNK_FIRST); at least chunk / chunk_fused: flat reservations
   uint32_t* rctr;       // [SCAN_REGIONS][RC_STRIDE]
   const uint32_t* qexact;  // per query: class id of its exact anagram class (0xFFFFFFFF = none); stop mode only
   int want_exact;
@@ -136,7 +146,8 @@ struct ScanArgs {
   uint32_t* qpairs;         // per query: scored pairs of THIS run, counted where they are produced (materialised or only counted);
                             // nullptr in normal runs (anx_batch_pair_counts: the per-query check of the production pair list)
   int dbg;  // ANX_SCAN_DBG (timing experiments only; results are wrong when set): 1 one query per pass, 2 skip process(), 4 no run staging,
-            // 8 no hit expansion, 16 pairs dropped before the band filter, 32 filtered pairs not written
+            // 8 no hit expansion, 16 pairs dropped before the band filter, 32 filtered pairs not written; result-neutral A/B of HISTORY.md
+            // section 19: 64 count-only rows take the hit list like any other, 128 the list is expanded after every chunk
 };
 
 __device__ inline int32_t bcnt_acc(uint32_t x, int32_t acc) {  // acc + popcount(x) in one v_bcnt_u32_b32
@@ -177,7 +188,7 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
   uint2* __restrict__ raw = A.raw;
   const uint32_t cstride = A.cstride;
   const uint32_t region = item % SCAN_REGIONS;
-  WaveOut wo{0, 0, 0, 0, 0, region * A.region_cap, (region + 1) * A.region_cap, A.rctr + region * RC_STRIDE, A.chunk};
+  WaveOut wo{0, 0, 0, 0, 0, region * A.region_cap, (region + 1) * A.region_cap, A.rctr + region * RC_STRIDE, 0};
   uint32_t ns = 0;  // staged class ids (wave-uniform)
   uint32_t nchunks = 0;
   uint32_t arend = 0;               // ADJ: end of the tile's rows (absolute row number, wave-uniform)
@@ -205,7 +216,9 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
   // Fused prefilter (bit-plane tiles of queries <= 16 symbols with d <= 3): the first 16 symbols of the tile's queries sit in LDS,
   // the expansion below makes the pairs DENSE in an LDS buffer and tests 64 of them at a time against the band-match bound.
   const bool fuse = BITS && A.fuse && t.lq <= 16u && t.d <= 3u;  // wave-uniform
-  if (fuse) wo.chunk = A.chunk_fused;  // a third of the pairs survive the filter: smaller reservations waste fewer slots
+  // fused tiles: a third of the pairs survive the filter, so the reservations are smaller and grow from chunk_first; the others write every
+  // pair and keep flat reservations of a whole chunk (tests/test_gpu_switches.py compares their slot count with the default's)
+  wo.sizes = fuse ? wave_sizes(A.chunk_first, A.chunk_fused) : wave_sizes(A.chunk, A.chunk);
   if (BITS && fuse && lane < t.nq) qsym[lane] = rec32(A.q_rec, t.q0 + lane)[0];
   constexpr uint32_t PBUF = SCAN_PBUF;
   uint32_t nfused = 0;          // pairs the fused filter tested (wave-uniform; statistics)
@@ -275,13 +288,14 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
         bool count_only;
         if (BITS) {
           // one scan record per lexicon ENTRY (the planes of its class): a hit is a (query, entry) pair already, there is no
-          // entries-per-class loop and no class gather here.  The list holds the record's position in the staged chunk (the
-          // stage keeps the chunk's ids until process() returns), bit 8 = pass, bit 9 = "fails the DL's length test"
-          const uint32_t hx = reinterpret_cast<const uint16_t*>(hits + SCAN_HITS)[idx];
+          // entries-per-class loop and no class gather here.  The list holds the record's entry id (< 2^26), so an entry outlives
+          // its chunk and the list is expanded when it is full, not after every chunk; bit 26 = pass, bit 27 = "fails the DL's
+          // length test" (tiles that stream a list count such rows in process() and never append them: GEN = false)
+          const uint32_t hx = hits[SCAN_HITS + idx];
           m = hits[idx];
-          qb = ((hx >> 8) & 1u) << 5;
-          count_only = (hx >> 9) & 1u;
-          e0 = stage[hx & 0xFFu];
+          qb = ((hx >> 26) & 1u) << 5;
+          count_only = (hx >> 27) & 1u;
+          e0 = hx & 0x3FFFFFFu;
           ne = 1;
           c = A.qpairs ? A.scan_rec[e0].w : 0u;  // class of the entry (pair-count runs only)
         } else {
@@ -358,10 +372,16 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
   // queries per pass; bit (npass-1-qi) of hm[j] = query qi of the pass hits class j of this lane.  The query loop is
   // branch-free: 2 ops per plane + ONE v_alignbit_b32 per test (it shifts the sign bit of acc = "miss" into the mask).
   auto process = [&]() {
-    ++nchunks;
+    if (!ADJ) ++nchunks;  // (a tile that streams a list knows its chunks beforehand)
     if (ANX_DBG(A.dbg) & 2) return;
     uint32_t cid[CPL], cw[CPL][W];
     int32_t thr[CPL];   // ADJ: wave-uniform (scalar registers)
+    // ADJ, production instance: a row whose record length fails the DL's length test (wave-uniform: one length per row) is only
+    // counted -- its hits never enter the hit list.  With k = 3 and d = 2 that is a quarter of the rows (sections lq - 3 and lq + 3).
+    // GEN keeps the list's flag: it counts per query (qpairs) and marks StopAtExactMatch.
+    constexpr bool ROWCOUNT = ADJ && !GEN;
+    bool conly[CPL] = {};
+    bool all_conly = ROWCOUNT;
     const bool need34 = BITS && ((t.kend >> 8) & 0xFFu) < t.nq;  // some query of the tile is of kind 3 or 4
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
@@ -371,13 +391,14 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
         // row j of the chunk: 64 consecutive records of the list, one per lane (adj_load: coalesced 8-byte and 4-byte loads)
         const uint2 pl = apl[j];
         const uint32_t id = aid[j];
-        stage[idx] = id;  // the hit list holds positions in the chunk (flush)
         uint2 hi = make_uint2(0u, 0u);
         if (need34) hi = A.scan_rec34[id];
         cw[j][0] = pl.x; cw[j][1] = pl.y;
         if (W > 2) { cw[j][2] = hi.x; cw[j][W - 1] = hi.y; }
         lc = alc[j];
         const int32_t diff = lc > (int32_t)t.lq ? lc - (int32_t)t.lq : (int32_t)t.lq - lc;
+        conly[j] = ROWCOUNT && diff > (int32_t)t.d && !(ANX_DBG(A.dbg) & 64);  // (dbg 64, timing: such rows take the list like any other)
+        all_conly = all_conly && conly[j];
         cid[j] = (A.drop_len && diff > (int32_t)t.d) ? id | (1u << 28) : id;
       } else {
       cid[j] = idx < ns ? stage[idx] : (BITS ? A.pad_rec : A.pad_class);
@@ -464,8 +485,13 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
 #pragma unroll
       for (int j = 0; j < CPL; ++j) {
         hm[j] = ~hm[j] & valid;
+        if (ADJ && conly[j]) {  // wave-uniform
+          counted_only += (uint32_t)__popc(hm[j]);
+          hm[j] = 0u;
+        }
         any |= hm[j];
       }
+      if (ADJ && all_conly) continue;  // wave-uniform: nothing of this chunk can enter the list
       if (__ballot(any != 0) == 0ull || (ANX_DBG(A.dbg) & 8)) continue;  // wave-uniform (dbg 8: timing without the expansion)
       // The non-empty (class, hit mask) pairs are appended to the wave's LDS hit list; flush() expands the list one
       // entry per lane whenever it gets full (and at the end of the tile), so the expansion rounds run with full
@@ -481,7 +507,7 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
             const uint32_t hmask = __brev(hm[j]) >> (32u - npass);  // shift-in order -> bit b = query b of the pass
             if (BITS) {
               hits[pos] = hmask;
-              reinterpret_cast<uint16_t*>(hits + SCAN_HITS)[pos] = (uint16_t)(((uint32_t)j * 64u + lane) | ((qb >> 5) << 8) | (((cid[j] >> 28) & 1u) << 9));
+              hits[SCAN_HITS + pos] = (cid[j] & 0x3FFFFFFu) | ((qb >> 5) << 26) | (((cid[j] >> 28) & 1u) << 27);
             } else {
               hits[2 * pos] = cid[j] | ((qb >> 5) << 27);  // class id, pass
               hits[2 * pos + 1] = hmask;
@@ -493,8 +519,11 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
       if (!BITS && nhits > SCAN_HITS - CHUNK) flush();  // a pass adds at most CHUNK entries
     }
     // bit-plane tiles expand after the passes, when the records' planes and thresholds are dead (the fused filter needs the
-    // registers): the two passes of a chunk add at most 2 * CHUNK = SCAN_HITS entries
-    if (BITS) flush();
+    // registers), and only when the next chunk could overflow the list: a pass adds at most CHUNK entries, so a tile of <= 32
+    // queries expands every second chunk at most (fuller rounds, fewer idle trips), a tile of 33..64 after every chunk.  The
+    // end of the tile expands what is left.  The GEN instance expands after every chunk: its scalar registers are all taken, and
+    // a list that is known to be empty at the head of a chunk costs none.
+    if (BITS && (GEN || nhits + ((t.nq + 31u) >> 5) * CHUNK > SCAN_HITS || (ANX_DBG(A.dbg) & 128))) flush();  // (dbg 128, timing: after every chunk)
   };
 
   // The tile's signature window [s0, s1) is aligned to whole 64-signature blocks (no bounds test is needed: the other
@@ -551,6 +580,17 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
     }
   };
   const uint4* __restrict__ sigtab = BITS ? A.sig_e : A.sig;  // runs of scan records (entries) / of classes
+  auto count_tests = [&](uint32_t nch) {  // class tests by planes compared (statistics)
+    if (lane != 0 || nch == 0u) return;
+    if (BITS) {
+      const uint32_t e[5] = {0u, t.kend & 0xFFu, (t.kend >> 8) & 0xFFu, (t.kend >> 16) & 0xFFu, t.nq};
+      for (int k = 1; k <= NBITPLANES; ++k)
+        if (e[k] > e[k - 1])
+          atomicAdd(reinterpret_cast<unsigned long long*>(wo.ctr + RC_TESTS + 2 * k), (unsigned long long)nch * CHUNK * (e[k] - e[k - 1]));
+    } else {
+      atomicAdd(reinterpret_cast<unsigned long long*>(wo.ctr + RC_TESTS), (unsigned long long)nch * CHUNK * t.nq);
+    }
+  };
   if (ADJ) {
     // the list of the tile's signature: rows [row0 + rbeg, row0 + rend) hold the records of the lengths lq - k .. lq + k (section i of the
     // list = length lq - 3 + i; a list holds the ball of radius 3, a tile with a smaller k tests a few records more than it has to)
@@ -564,6 +604,7 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
       atomicAdd(&wo.ctr[RC_ADJ], rend - rbeg);
       if (t.flags & 1u) atomicAdd(&wo.ctr[RC_ADJ_FIRST], rend - rbeg);
     }
+    if (rend > rbeg) count_tests((rend - rbeg + (uint32_t)CPL - 1u) / (uint32_t)CPL);  // here, where the rows are known: no chunk counter lives through the tile
     uint2 npl[4];
     uint32_t nid[4];
     if (rbeg < rend) adj_load(row0 + rbeg, npl, nid);
@@ -630,16 +671,7 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
   }
   wave_close(wo, lane, raw);
   if (BITS && lane == 0 && nfused) atomicAdd(&wo.ctr[RC_FUSED], nfused);
-  if (lane == 0 && nchunks) {  // class tests by planes compared (statistics)
-    if (BITS) {
-      const uint32_t e[5] = {0u, t.kend & 0xFFu, (t.kend >> 8) & 0xFFu, (t.kend >> 16) & 0xFFu, t.nq};
-      for (int k = 1; k <= NBITPLANES; ++k)
-        if (e[k] > e[k - 1])
-          atomicAdd(reinterpret_cast<unsigned long long*>(wo.ctr + RC_TESTS + 2 * k), (unsigned long long)nchunks * CHUNK * (e[k] - e[k - 1]));
-    } else {
-      atomicAdd(reinterpret_cast<unsigned long long*>(wo.ctr + RC_TESTS), (unsigned long long)nchunks * CHUNK * t.nq);
-    }
-  }
+  if (!ADJ) count_tests(nchunks);
 }
 
 // Every wave takes one tile; tiles are ordered by decreasing cost.  The bit-plane tiles (wave-uniform switch over
@@ -650,10 +682,15 @@ template <int NP, bool BITS, bool GEN, bool ADJ = false>
 __device__ inline void scan_wave(const ScanArgs& A) {
   constexpr int QWORDS = SCAN_TQ * (BITS ? NBITPLANES : NP);
   __shared__ uint32_t s_qlds[4][QWORDS];
-  __shared__ __attribute__((aligned(16))) uint32_t s_stage[4][ADJ ? 64 * 4 : SCAN_STAGE];  // (tiles that stream a list only keep the chunk's ids)
-  // per wave, entries awaiting expansion: bit-plane tiles hit mask u32[SCAN_HITS] + (position in the chunk | pass | flag) u16[SCAN_HITS];
+  uint32_t* stage = nullptr;  // (tiles that stream a list stage nothing: their records arrive in registers, the hit list holds entry ids)
+  if constexpr (!ADJ) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[4][SCAN_STAGE];
+    stage = s_stage[threadIdx.x >> 6];
+  }
+  // per wave, entries awaiting expansion: bit-plane tiles hit mask u32[SCAN_HITS] + (entry id | pass << 26 | flag << 27) u32[SCAN_HITS];
   // count-vector tiles (class | pass << 27, hit mask) pairs
-  __shared__ uint32_t s_hits[4][BITS ? SCAN_HITS + SCAN_HITS / 2 : 2 * SCAN_HITS];
+  // LDS per block: k_scan_adj 4 K queries + 16 K list + 4 K symbols + 2 K ring = 26 624 B (6 blocks per CU); k_scan_bits + 6 K stage = 32 768 B (5 blocks)
+  __shared__ uint32_t s_hits[4][2 * SCAN_HITS];
   __shared__ uint4 s_qsym[BITS ? 4 : 1][BITS ? SCAN_TQ : 1];     // first 16 symbols of the tile's queries (fused prefilter)
   __shared__ uint32_t s_pbuf[BITS ? 4 : 1][BITS ? SCAN_PBUF : 1];      // dense (entry | query << 26) pairs awaiting the filter / the write
   const uint32_t wid = threadIdx.x >> 6;
@@ -666,7 +703,7 @@ __device__ inline void scan_wave(const ScanArgs& A) {
   Tile t;
   t.q0 = tp[0]; t.nq = tp[1]; t.s0 = tp[2]; t.s1 = tp[3]; t.k = tp[4]; t.lq = tp[5]; t.sig_lo = tp[6]; t.sig_hi = tp[7]; t.kind = tp[8]; t.d = tp[9]; t.kend = tp[10]; t.ball0 = tp[11]; t.balln = tp[12]; t.adj = tp[13]; t.flags = tp[14];
   // the launches are split by the encoders' tile order: [tiles that stream an adjacency list | other bit-plane tiles | count-vector tiles]
-  scan_tile<BITS, NP, GEN, ADJ>(A, t, item, s_stage[wid], s_hits[wid], s_qlds[wid], s_qsym[BITS ? wid : 0], s_pbuf[BITS ? wid : 0]);
+  scan_tile<BITS, NP, GEN, ADJ>(A, t, item, stage, s_hits[wid], s_qlds[wid], s_qsym[BITS ? wid : 0], s_pbuf[BITS ? wid : 0]);
 }
 // <= 80 VGPRs = 6 waves per SIMD for the bit-plane kernel (measured: unconstrained 85 VGPRs -> 2.33 ms, 80 -> 2.20 ms,
 // 64 with spills -> 2.60 ms)

@@ -778,7 +778,9 @@ __global__ __launch_bounds__(256) void k_filter_score(FilterArgs f, PairArgs A, 
     const uint2 rp = rp_next;
     if (base + (r + 1) * 256 < lim) rp_next = A.raw[idx + 256 < lim ? p + 256 : p0];
     const bool invalid = !live || rp.x == RAW_INVALID;  // unused chunk tail
-    // RAW_PREFILTERED: a chunk comes from one tile, so whole waves take the short round (wave-uniform test)
+    // RAW_PREFILTERED: the scan reserves at least 32 slots at a time (growing to the chunk), so the 64 slots of a wave come from one or
+    // a few tiles; slots of several FUSED tiles (and RAW_INVALID tails) still take the short round together -- it reads lq, lc and d
+    // per lane -- and a wave that also holds a slot of a not-fused tile takes the general round (wave-uniform test)
     const bool pre = !invalid && (rp.y & RAW_PREFILTERED);
     bool selected = pre, wide = false, inl = false;
     int lq = 0, lc = 0, d = D;
@@ -811,8 +813,8 @@ __global__ __launch_bounds__(256) void k_filter_score(FilterArgs f, PairArgs A, 
         if (wide && lc > 16) { const uint4 C1 = A.rows[crow + 1]; c10[5] = C1.x; c10[6] = C1.y; c10[7] = C1.z; c10[8] = C1.w; }
         if (band_bound_rejects<8>(q8, c10, filt, d, lq, lc)) selected = false;
       } else if (__any(filt && !wide)) {
-        // as many 4-symbol words as the longest string of the WAVE needs (its 64 slots come from one scan chunk, i.e. one tile
-        // and one query length)
+        // as many 4-symbol words as the longest string of the WAVE needs (its 64 slots come from one or a few scan reservations,
+        // i.e. few tiles and query lengths: the __any below covers them all)
         const bool f4 = filt && !wide;
         const int ml = lq > lc ? lq : lc;
         // B7 (alphabets of <= 124 classes): symbols < 0x7E, the paddings 0xFE / 0xFF masked down to 0x7E / 0x7F

@@ -247,7 +247,7 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   {
     ScanArgs A = scan_args_of(dl);
     A.tiles = c->enc.tiles; A.ntiles = slots * n32; A.q_bits = c->enc.q_bits; A.q_cv = c->enc.q_cv;
-    A.chunk = 64; A.chunk_fused = 32;  // (SCAN_CHUNK / SCAN_CHUNK_FUSED of the batch path: 256 / 128 -- a wave here holds a share of ONE query's pairs)
+    A.chunk = 64; A.chunk_fused = 32; A.chunk_first = 64;  // flat reservations (SCAN_CHUNK / SCAN_CHUNK_FUSED of the batch path: 256 / 128 -- a wave here holds a share of ONE query's pairs)
     A.raw = c->raw; A.region_cap = region_cap; A.rctr = c->rctr; A.qexact = c->enc.qexact; A.want_exact = 0; A.drop_len = 1;
     A.q_rec = c->enc.q_rec;
     A.fuse = (switches().fuse_prefilter && switches().prefilter) ? 1 : 0;  // (the batch path: only with drop_len, which is always 1 here)
