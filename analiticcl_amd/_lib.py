@@ -75,6 +75,11 @@ class PairScore(C.Structure):  # anx_pair_score, 24 bytes
                 ("status", C.c_int8), ("_pad", C.c_uint32)]
 
 
+class RowMeasures(C.Structure):  # anx_row_measures, 16 bytes
+    _fields_ = [("score", C.c_double), ("ld", C.c_uint8), ("lcs", C.c_uint8), ("prefixlen", C.c_uint8), ("suffixlen", C.c_uint8),
+                ("len_input", C.c_uint8), ("len_entry", C.c_uint8), ("anagram_distance", C.c_uint8), ("flags", C.c_uint8)]
+
+
 class GoldEval(C.Structure):  # anx_gold_eval, 32 bytes
     _fields_ = [("gold_vocab_id", C.c_uint32), ("rank", C.c_int32), ("n_results", C.c_uint32), ("top_vocab_id", C.c_uint32),
                 ("gold_score", C.c_double), ("ld", C.c_uint16), ("k", C.c_uint8), ("d", C.c_uint8), ("status", C.c_int8),
@@ -210,6 +215,8 @@ def lib():
         "anx_compact_to_results": (None, [C.c_void_p, sz, C.POINTER(Result)]),
         "anx_batch_fetch_compact_via": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32))]),
         "anx_compact_to_results_via": (None, [C.c_void_p, C.POINTER(C.c_uint32), sz, C.POINTER(Result)]),
+        "anx_batch_fetch_measures": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint32))]),
+        "anx_measures_free": (None, [C.c_void_p, C.POINTER(C.c_uint32)]),
         "anx_batch_fetch_pairs": (C.c_int, [vp, C.POINTER(C.POINTER(Pair)), C.POINTER(sz)]),
         "anx_pairs_free": (None, [C.POINTER(Pair)]),
         "anx_score_pairs": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(PairScore)]),

@@ -55,21 +55,32 @@ def _esc(s: str) -> str:
     return s.replace('"', '\\"')
 
 
-def tsv_line(inp: str, variants: Optional[List[dict]], offset=None, output_lexmatch=False) -> str:
-    """output_matches_as_tsv / output_result_as_tsv (bin:21-76); `variants` already has the selected one first."""
+EXPLAIN_KEYS = ("ld", "lcs", "prefixlen", "suffixlen", "samecase", "anagram_distance", "len_input", "len_entry", "unweighted_score")
+
+
+def _explain_value(v: dict, k: str) -> str:
+    return rust_f64(v[k]) if k == "unweighted_score" else ("true" if v[k] else "false") if k == "samecase" else str(v[k])
+
+
+def tsv_line(inp: str, variants: Optional[List[dict]], offset=None, output_lexmatch=False, explain=False) -> str:
+    """output_matches_as_tsv / output_result_as_tsv (bin:21-76); `variants` already has the selected one first.
+    explain (query --explain, variants from explain_variants): after every variant's score the columns EXPLAIN_KEYS and the text of
+    the scored entry (empty unless the row was reached through a variant list)."""
     out = [inp]
     if offset is not None:
         out.append(f"\t{offset[0]}:{offset[1]}")
     for v in variants or []:
         out.append(f"\t{v['text']}\t{rust_f64(v['score'])}\t")
+        if explain:
+            out.append("\t".join([_explain_value(v, k) for k in EXPLAIN_KEYS] + [v.get("scored", "")]) + "\t")
         if output_lexmatch:
             out.append('\t"' + ";".join(v["lexicons"]) + '"')
     return "".join(out)
 
 
 def json_item(inp: str, variants: Optional[List[dict]], seqnr: int, offset=None, output_lexmatch=False,
-              tag=(), tag_seqnr=()) -> str:
-    """output_matches_as_json / output_result_as_json (bin:78-187)."""
+              tag=(), tag_seqnr=(), explain=False) -> str:
+    """output_matches_as_json / output_result_as_json (bin:78-187).  explain: the keys EXPLAIN_KEYS (and "scored") in every variant."""
     out = ["    ," if seqnr > 1 else "    ", '{ "input": "%s"' % _esc(inp)]
     if offset is not None:
         out.append(f', "begin": {offset[0]}, "end": {offset[1]}')
@@ -85,6 +96,10 @@ def json_item(inp: str, variants: Optional[List[dict]], seqnr: int, offset=None,
             _esc(v["text"]), rust_f64(v["score"]), rust_f64(v["dist_score"]), rust_f64(v["freq_score"]))
         if "via" in v:
             s += ', "via": "%s"' % _esc(v["via"])
+        if explain:
+            s += "".join(', "%s": %s' % (k, _explain_value(v, k)) for k in EXPLAIN_KEYS)
+            if "scored" in v:
+                s += ', "scored": "%s"' % _esc(v["scored"])
         if output_lexmatch:
             s += ', "lexicons": [ %s ]' % ", ".join('"%s"' % _esc(x) for x in v["lexicons"])
         items.append(s + " }")
@@ -129,6 +144,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight-contextrules", type=float, default=1.0)
     p.add_argument("--batch-size", type=int, default=100000, help="query mode: lines per device batch")
     p.add_argument("--weighted", action="store_true", help="score mode: two more columns / keys, weight (the confusable weight of the pair under --confusables) and weighted_score = score * weight")
+    p.add_argument("--explain", action="store_true", help="query mode: with every variant its edit distance, common substring / prefix / suffix, case flag, "
+                                                           "anagram distance, lengths and unweighted score (and the scored entry of a row reached through a variant list)")
     p.add_argument("--summary-json", default=None, help="evaluate mode: write the summary as JSON to this file instead of as text to standard error")
     p.add_argument("--index-cache", default=None, help="image of the built model: loaded if the file exists (lexicons are then not read), written after build() otherwise")
     p.add_argument("--device", type=int, default=None)
@@ -277,7 +294,12 @@ def run_query(model, params, a, out) -> None:
         if not batch:
             return
         # one device batch, formatted natively (anx_format_query_output = tsv_line / json_item of this module)
-        out.write(model.query_output(batch, params, a.json, a.output_lexmatch, seqnr + 1))
+        if getattr(a, "explain", False):  # the measures behind every row (explain_variants), formatted here
+            for i, r in enumerate(model.explain_variants(batch, params)):
+                out.write(json_item(r["input"], r["variants"], seqnr + 1 + i, output_lexmatch=a.output_lexmatch, explain=True) if a.json
+                          else tsv_line(r["input"], r["variants"], output_lexmatch=a.output_lexmatch, explain=True) + "\n")
+        else:
+            out.write(model.query_output(batch, params, a.json, a.output_lexmatch, seqnr + 1))
         seqnr += len(batch)
         out.flush()
         progress.show(seqnr, len(batch))  # bin:477-479

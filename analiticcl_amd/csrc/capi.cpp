@@ -2013,6 +2013,7 @@ int anx_learn_finish(anx_model* m, int auto_build, double* ms) {
   return rc;
 }
 bool anx_batch_host_rescored(const anx_batch* b) { return b->rescore; }
+const anx_model* anx_batch_model_of(const anx_batch* b) { return b->model; }  // explain_capi.cpp: the weights and the vocabulary size
 size_t anx_batch_rows(const anx_batch* b) {
   size_t r = 0;
   for (const Shard& s : b->shards) r += anx::batch_n_results(s.b);

@@ -117,6 +117,10 @@ int batch_fetch_into(const Batch* b, anx_result* rows, size_t* offs, size_t base
 // row was reached through, 0xFFFFFFFF = none; plain: a model without variant lists -- the words are written on the host, nothing
 // more crosses PCIe
 int batch_fetch_compact_into(const Batch* b, anx_topk_record* rows, uint32_t* offs, uint32_t* via, uint32_t base, bool plain, std::string& err);
+// the measures behind the same rows (anx_batch_fetch_measures, kernels_explain.hpp): rows[r] describes row r of batch_fetch_compact_into
+// with `via` -- edit distance, common substring / prefix / suffix, case flag, anagram distance and the unweighted score of (input,
+// scored entry), the scored entry being the `via` item where the row has one.  The model and the replica supply the weights and the tables
+int batch_fetch_measures_into(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_row_measures* rows, uint32_t* offs, uint32_t base, std::string& err);
 int batch_fetch_pairs(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_pair** out, size_t* n,
                       std::string& err);
 int batch_pair_counts(const HostModel& m, const DeviceLexicon* dl, Batch* b, uint32_t** out, std::string& err);

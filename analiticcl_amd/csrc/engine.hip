@@ -45,6 +45,7 @@ namespace anx {
 #include "kernels_prefix.hpp"
 #include "kernels_score.hpp"
 #include "kernels_rank.hpp"
+#include "kernels_explain.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // Host side
@@ -628,7 +629,7 @@ void lexicon_free(DeviceLexicon* d) {
                   (void*)d->ent_freq, (void*)d->ent_meta, (void*)d->ent_rowoff, (void*)d->ent_order, (void*)d->ent_rec, (void*)d->e_rec, (void*)d->e_planes, (void*)d->ent_var_off,
                   (void*)d->var_target, (void*)d->var_target_freq, (void*)d->var_score, (void*)d->rows, (void*)d->alpha.fast, (void*)d->alpha.coff,
                   (void*)d->alpha.cand, (void*)d->alpha.bytes, (void*)d->alpha.sym_group, (void*)d->alpha.lower, (void*)d->alpha.siglen_begin,
-                  (void*)d->adj_hash, (void*)d->adj_hdr, (void*)d->adj_planes, (void*)d->adj_ids, (void*)d->quot})
+                  (void*)d->adj_hash, (void*)d->adj_hdr, (void*)d->adj_planes, (void*)d->adj_ids, (void*)d->quot, (void*)d->vocab_ent})
     if (p) pool_free(p);
   conf_free(d->dconf);
   lm_free(d->dlm);
@@ -1798,6 +1799,88 @@ int batch_fetch_compact_into(const Batch* b, anx_topk_record* out, uint32_t* off
     return fetch_rows(b, out, off, via, base, [](anx_topk_record* d_out, uint32_t* d_via) { return EmitRecordVia{d_out, d_via}; }, err);
   const int rc = fetch_rows(b, out, off, nullptr, base, [](anx_topk_record* d_out, uint32_t*) { return EmitRecord{d_out}; }, err);
   if (rc == ANX_OK && via && b->n_results) memset(via, 0xFF, (size_t)b->n_results * sizeof(uint32_t));
+  return rc;
+}
+
+// anx_batch_fetch_measures for one shard: out[0 .. n_results) = the measures behind row r of batch_fetch_compact_into (same rows, same
+// order), off[0 .. n_input] = base + the CSR offsets.  The vocabulary id -> entry table of the replica is built on first use; the
+// offsets are the scan every fetch makes (k_fetch_counts + exclusive_scan); k_row_measures settles the short rows and lists the
+// long ones for k_row_measures_long (kernels_explain.hpp).  Runs on the stream of the batch's last run; every exit frees the blocks.
+static int vocab_entry_ensure(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, std::string& err) {
+  std::lock_guard<std::mutex> g(dl->explain_mu);
+  if (dl->vocab_ent) return ANX_OK;
+  const size_t V = std::max<size_t>(m.decoder.size(), 1);
+  if (V >= 0xFFFFFFFFull) { err = "more than 2^32 vocabulary items"; return ANX_ELIMIT; }
+  uint32_t* t = nullptr;
+  HIP_TRY(pool_malloc(reinterpret_cast<void**>(&t), V * sizeof(uint32_t)));
+  auto fill = [&]() -> int {
+    HIP_TRY(hipMemsetAsync(t, 0xFF, V * sizeof(uint32_t), st));
+    if (dl->nentries) hipLaunchKernelGGL(k_vocab_entry_scatter, dim3((dl->nentries + 255) / 256), dim3(256), 0, st, dl->nentries, dl->ent_vocab, (uint32_t)V, t);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));  // (another thread's stream may read the table as soon as the pointer is published)
+    return ANX_OK;
+  };
+  if (const int rc = fill()) { (void)hipStreamSynchronize(st); pool_free(t); return rc; }
+  dl->vocab_ent_n = (uint32_t)V;
+  dl->vocab_ent = t;
+  return ANX_OK;
+}
+int batch_fetch_measures_into(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_row_measures* out, uint32_t* off, uint32_t base, std::string& err) {
+  static_assert(sizeof(anx_row_measures) == sizeof(uint4), "the record leaves as one 16-byte store");
+  if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
+  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
+  HIP_TRY(hipSetDevice(b->device));
+  const size_t n = b->n_input;
+  if (!b->nq || !b->n_results) {
+    for (size_t i = 0; i <= n; ++i) off[i] = base;
+    return ANX_OK;
+  }
+  if (b->n_results >= 0xFFFFFFFFull || b->n_surv >= 0xFFFFFFFFull) { err = "more than 2^32 result rows"; return ANX_ELIMIT; }
+  hipStream_t st = reinterpret_cast<hipStream_t>(b->last_stream);
+  if (const int rc = vocab_entry_ensure(m, dl, st, err)) return rc;
+  const uint32_t total = (uint32_t)b->n_surv, n32 = (uint32_t)n, nq32 = (uint32_t)b->nq;
+  uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr, *d_list = nullptr;
+  uint4* d_out = nullptr;
+  auto body = [&]() -> int {
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), scan_tmp_bytes(n)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_out), b->n_results * sizeof(uint4)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_list), ((size_t)total + 4) * sizeof(uint32_t)));  // [0]: the list's length, rows from [4] on
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, n32 * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(d_list, 0, 4 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
+    exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
+    ExplainArgs k{};
+    k.nq = nq32; k.total = total; k.V = dl->vocab_ent_n; k.nentries = dl->nentries; k.qw = b->qw; k.cstride = dl->cstride; k.n_out = (uint32_t)b->n_results;
+    k.NP = dl->nplanes; k.bits_ok = (dl->nsym <= 32 && !scan_mode()) ? 1 : 0;
+    k.soff = b->soff; k.r_count = b->r_count; k.q_orig = b->q_orig; k.off_orig = d_off; k.q_meta = b->q_meta; k.r_rows = b->r_rows;
+    k.q_rec = b->q_rec; k.q_rows = b->q_rows; k.q_bits = reinterpret_cast<const uint4*>(b->q_bits); k.q_cv = b->q_cv;
+    k.vocab_ent = dl->vocab_ent; k.e_rec = dl->e_rec; k.scan_rec = dl->scan_rec; k.rows = dl->rows; k.cls_planes = dl->cls_planes; k.quot = dl->quot;
+    k.w_ld = m.weights.ld; k.w_lcs = m.weights.lcs; k.w_prefix = m.weights.prefix; k.w_suffix = m.weights.suffix; k.w_case = m.weights.casew;
+    k.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;  // src/types.rs:69-73, as launch_plan.hpp
+    k.out = d_out; k.list = d_list + 4; k.list_n = d_list;
+    {
+      const int kt = ktimer_begin("k_row_measures", st);
+      hipLaunchKernelGGL(k_row_measures, dim3((total + XM_THREADS - 1) / XM_THREADS), dim3(XM_THREADS), 0, st, k);
+      ktimer_end(kt, st);
+    }
+    {
+      const int kt = ktimer_begin("k_row_measures_long", st);
+      hipLaunchKernelGGL(k_row_measures_long, dim3(std::min<uint32_t>(XM_LONG_BLOCKS, total)), dim3(64), 0, st, k);
+      ktimer_end(kt, st);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(off, d_off, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out, d_out, b->n_results * sizeof(uint4), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (base)
+      for (size_t i = 0; i <= n; ++i) off[i] += base;
+    return ANX_OK;
+  };
+  const int rc = body();
+  if (rc) (void)hipStreamSynchronize(st);  // nothing of this call may still be in flight when its blocks return to the pool
+  for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_out, (void*)d_list}) pool_free(p);
   return rc;
 }
 

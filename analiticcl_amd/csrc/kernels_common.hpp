@@ -139,6 +139,9 @@ struct DeviceLexicon {
   mutable RunHints hints;
   mutable struct DeviceLm* dlm = nullptr;      // bigram terms + token lists of the vocabulary (lattice.hip), built on first use
   mutable struct DeviceConf* dconf = nullptr;  // confusable patterns + vocabulary texts of this replica (conf.hip), built on first use
+  mutable std::mutex explain_mu;               // guards the first build of vocab_ent
+  mutable uint32_t* vocab_ent = nullptr;       // [vocab_ent_n] vocabulary id -> lexicon entry, 0xFFFFFFFF = not indexed (kernels_explain.hpp), built on first use
+  mutable uint32_t vocab_ent_n = 0;
 };
 
 enum { CTR_SKIPPED = 2, CTR_MAXROWS = 3 /* longest ranked list of the run */, CTR_OVERFLOW = 4 /* survivor records dropped */, CTR_N = 8 };

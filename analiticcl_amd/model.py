@@ -308,6 +308,27 @@ class Batch:
             L.check(L.lib().anx_batch_fetch_compact(self.h, C.byref(rows), C.byref(offs)))
         return _compact_views(rows, offs, via if with_via else None, self.n)
 
+    MEASURES_DTYPE = [("score", "<f8"), ("ld", "u1"), ("lcs", "u1"), ("prefixlen", "u1"), ("suffixlen", "u1"), ("len_input", "u1"),
+                      ("len_entry", "u1"), ("anagram_distance", "u1"), ("flags", "u1")]
+
+    def fetch_measures(self):
+        """-> (offsets[n+1] uint32, measures): anx_batch_fetch_measures, why every ranked row got its score.  measures is a structured
+        array of 16-byte records (MEASURES_DTYPE); record r describes row r of fetch_compact(with_via=True) on this batch: the
+        unrestricted edit distance, common substring / prefix / suffix, the lengths in symbols, the anagram distance, flags (bit 0
+        samecase, bit 1 the row has a via: the scored entry is the via item) and the unweighted distance score of (input, scored
+        entry).  Views of the library's pinned block, which is released when the last of them is garbage collected."""
+        import weakref
+
+        import numpy as np
+        rows = C.c_void_p()
+        offs = C.POINTER(C.c_uint32)()
+        L.check(L.lib().anx_batch_fetch_measures(self.h, C.byref(rows), C.byref(offs)))
+        off_addr = C.addressof(offs.contents)
+        owner = (C.c_char * (off_addr - rows.value + (self.n + 1) * 4)).from_address(rows.value)
+        weakref.finalize(owner, L.lib().anx_measures_free, rows, offs)
+        off = np.frombuffer(owner, dtype="<u4", count=self.n + 1, offset=off_addr - rows.value)
+        return off, np.frombuffer(owner, dtype=np.dtype(self.MEASURES_DTYPE), count=int(off[-1]))
+
     def fetch_pairs(self) -> List[tuple]:
         """-> every scored pair (query, vocab_id, ld|-1, lcs, prefixlen, suffixlen, samecase, score)"""
         pairs = C.POINTER(L.Pair)()
@@ -798,6 +819,46 @@ class VariantModel:
         res = self.find_variants_ids(input, params, with_via=True)
         return [{"input": t, "variants": [self._to_dict(v, d, f, params.freq_weight, via) for v, d, f, via in r]}
                 for t, r in zip(input, res)]
+
+    EXPLAIN_KEYS = ("ld", "lcs", "prefixlen", "suffixlen", "samecase", "anagram_distance", "len_input", "len_entry", "unweighted_score")
+
+    def explain_variants(self, input: List[str], params: SearchParameters) -> List[dict]:
+        """find_variants_par with the reason for every score: each variant dict also has ld, lcs, prefixlen, suffixlen, samecase,
+        anagram_distance, len_input, len_entry (symbols), unweighted_score (the distance score of the input and the scored entry
+        without confusable weight and variant score) and, when the row has a `via`, scored: the text of the entry that was scored.
+        Always the staged batch path (the small call keeps no resident batch): Batch.run + anx_batch_fetch + Batch.fetch_measures."""
+        b = Batch(self, input, params)
+        try:
+            b.run()
+            rows = C.POINTER(L.Result)()
+            offs = C.POINTER(C.c_size_t)()
+            L.check(L.lib().anx_batch_fetch(b.h, C.byref(rows), C.byref(offs)))
+            try:
+                off = _offsets(offs, b.n)
+                v, d, f, via = _result_columns(rows, off[-1])
+            finally:
+                L.lib().anx_results_free(rows, offs)
+            moff, m = b.fetch_measures()
+            if moff.tolist() != off:
+                raise L.AnxError(L.ANX_EINVAL, "explain_variants: the measures do not describe the fetched rows")
+            cols = {k: m[k].tolist() for k, _t in Batch.MEASURES_DTYPE}
+        finally:
+            b.free()
+        out = []
+        for i, t in enumerate(input):
+            vs = []
+            for r in range(off[i], off[i + 1]):
+                has_via = via[r] != L.ANX_NO_VIA
+                e = self._to_dict(v[r], d[r], f[r], params.freq_weight, via[r] if has_via else None)
+                for k in ("ld", "lcs", "prefixlen", "suffixlen", "anagram_distance", "len_input", "len_entry"):
+                    e[k] = cols[k][r]
+                e["samecase"] = bool(cols["flags"][r] & 1)
+                e["unweighted_score"] = cols["score"][r]
+                if has_via:
+                    e["scored"] = e["via"]
+                vs.append(e)
+            out.append({"input": t, "variants": vs})
+        return out
 
     # -- search mode: the caller of the hot path (SURVEY.md section 8(f) row 1) ---------------------------
     def find_all_matches_ids(self, texts: Sequence[str], params: SearchParameters) -> List[List[dict]]:

@@ -41,7 +41,8 @@ extern "C" {
  *    anx_score_pairs_weighted / _packed, anx_model_confusable_weight_text and anx_debug_pairs_conf_stats: the confusable weight of
  *    such pairs (additive); the test hooks anx_debug_exclusive_scan and anx_debug_rank_rows (additive); anx_evaluate_gold /
  *    anx_evaluate_gold_packed, the struct anx_gold_eval, the ANX_GOLD_* reasons and the test hook anx_debug_evaluate_gold_chunk
- *    (additive, nothing else changed); the test hook anx_debug_score_slots (additive). */
+ *    (additive, nothing else changed); the test hook anx_debug_score_slots (additive); anx_batch_fetch_measures, anx_measures_free and
+ *    the struct anx_row_measures: the measures behind every ranked row of a batch (additive, nothing else changed). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -254,6 +255,31 @@ void anx_compact_to_results(const anx_topk_record *rows, size_t n_rows, anx_resu
  * anx_compact_to_results_via writes the anx_result view (via = ANX_NO_VIA for UINT32_MAX) of n_rows records into caller storage. */
 int anx_batch_fetch_compact_via(const anx_batch *, anx_topk_record **out_rows, uint32_t **out_offsets, uint32_t **out_via);
 void anx_compact_to_results_via(const anx_topk_record *rows, const uint32_t *via, size_t n_rows, anx_result *out);
+/* Why a ranked row got its score ("explain"): one 16-byte record per ranked row of a batch that has run, computed on the device from
+ * what is resident there.  Record r describes row r of anx_batch_fetch_compact_via on the same batch: the same rows, order and
+ * offsets, for every shard layout.  The scored entry is the lexicon entry of the row's vocab_id or, when the row has a `via`, the
+ * entry of `via` (the item that was matched before its variant list was expanded).  The measures are what anx_score_pairs returns for
+ * (input text, text of the scored item): unrestricted Damerau-Levenshtein, longest common substring, common prefix and suffix, the
+ * equality of the first-character case flags -- every one computed whatever its weight.  score is the distance score of
+ * src/lib.rs:1433-1452 under the model's weights WITHOUT the confusable weight and the variant score: on a plain model it equals
+ * the row's dist_score bit for bit; with confusables score * anx_model_confusable_weight(input, vocab_id) == dist_score.
+ * ANX_EINVAL: NULL arguments, a batch that has not run, a batch whose confusables were rescored on the host (as
+ * anx_batch_fetch_compact); ANX_ENODEVICE without a device.  A batch without rows returns ANX_OK and offsets that are all 0.
+ * Rows and offsets live in one cached pinned block: release both with anx_measures_free. */
+typedef struct anx_row_measures {
+  double score;                          /* unweighted: no confusable weight, no variant score */
+  uint8_t ld, lcs, prefixlen, suffixlen;
+  uint8_t len_input, len_entry;          /* symbols */
+  uint8_t anagram_distance;              /* L1 of the two count vectors: what the scan holds against k */
+  uint8_t flags;                         /* bit 0 samecase, bit 1 the row has a via (the scored entry is the via item, not vocab_id) */
+} anx_row_measures;                      /* 16 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(anx_row_measures) == 16, "anx_row_measures is 16 bytes");
+#else
+_Static_assert(sizeof(anx_row_measures) == 16, "anx_row_measures is 16 bytes");
+#endif
+int anx_batch_fetch_measures(const anx_batch *, anx_row_measures **out_rows, uint32_t **out_offsets);
+void anx_measures_free(anx_row_measures *rows, uint32_t *offsets);
 /* The staged calls as an asynchronous pipeline for ONE caller thread (the reference's counterpart: independent find_variants calls in
  * flight on rayon's pool, src/bin/analiticcl.rs:445-448): submit hands over a packed buffer (as anx_batch_encode_packed; it must stay
  * valid until that job's results were returned) and returns at once -- ANX_ELIMIT, nothing submitted, when `depth` jobs are in flight
