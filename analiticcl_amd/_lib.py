@@ -92,6 +92,25 @@ GOLD_REASONS = ("RANKED", "STATUS", "NOT_A_RESULT", "EXACT_STOP", "ANAGRAM", "ED
  ANX_GOLD_CROPPED) = range(8)
 
 
+class MineParams(C.Structure):  # anx_mine_params
+    _fields_ = [("context", C.c_uint32), ("anchors", C.c_uint32), ("no_sites", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class MineSite(C.Structure):  # anx_mine_site, 32 bytes
+    _fields_ = [("pair", C.c_uint32), ("a_pos", C.c_uint32), ("a_len", C.c_uint32), ("b_pos", C.c_uint32), ("b_len", C.c_uint32),
+                ("pattern", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class MineResult(C.Structure):  # anx_mine_result
+    _fields_ = [("n_patterns", C.c_size_t), ("text", C.c_void_p), ("text_off", C.POINTER(C.c_uint64)), ("count", C.POINTER(C.c_uint64)),
+                ("sites", C.POINTER(C.c_uint64)), ("flags", C.POINTER(C.c_uint32)), ("n_pairs", C.c_size_t), ("n_sites", C.c_size_t),
+                ("site_off", C.POINTER(C.c_uint64)), ("site", C.POINTER(MineSite))]
+
+
+ANX_MINE_SITE_FIRST, ANX_MINE_SITE_LAST = 1, 2
+ANX_MINE_UNREPRESENTABLE = 1
+
+
 class BatchStats(C.Structure):
     _fields_ = [("n_queries", C.c_uint64), ("n_pairs", C.c_uint64), ("n_class_tests", C.c_uint64),
                 ("n_results", C.c_uint64), ("n_scan_blocks", C.c_uint64), ("n_tests_kind", C.c_uint64 * 5),
@@ -230,6 +249,15 @@ def lib():
                                                C.POINTER(PairScore)]),
         "anx_debug_evaluate_gold_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(GoldEval),
                                                     C.POINTER(PairScore), sz]),
+        "anx_default_mine_params": (None, [C.POINTER(MineParams)]),
+        "anx_mine_confusables": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), C.POINTER(C.c_uint32), sz, C.POINTER(MineParams),
+                                           C.POINTER(C.POINTER(MineResult))]),
+        "anx_mine_confusables_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(C.c_uint32), sz, C.POINTER(MineParams),
+                                                  C.POINTER(C.POINTER(MineResult))]),
+        "anx_mine_result_free": (None, [C.POINTER(MineResult)]),
+        "anx_format_confusable_list": (C.c_int, [C.POINTER(MineResult), C.c_double, u64, C.POINTER(vp)]),
+        "anx_debug_mine_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+        "anx_debug_mine_chunk": (C.c_int, [sz]),
         "anx_batch_pair_counts": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_uint32))]),
         "anx_counts_free": (None, [C.POINTER(C.c_uint32)]),
         "anx_batch_export_topk": (C.c_int, [vp, vp, C.c_uint32, vp]),

@@ -1,4 +1,4 @@
-"""`python -m analiticcl_amd query|search|learn|score|evaluate ...` -- the `analiticcl query` / `search` / `learn` command line
+"""`python -m analiticcl_amd query|search|learn|score|evaluate|mine ...` -- the `analiticcl query` / `search` / `learn` command line
 (/root/reference/src/bin/analiticcl.rs) on top of the MI355X engine.
 
 Same option names and defaults (note the CLI's own weight defaults 0.5/0.125/0.125/0.125/0.125, bin:760-800, and
@@ -13,6 +13,9 @@ for each pair (score_pairs: the reference's public distance functions, src/dista
 `evaluate` has none either: it reads `input<TAB>gold` lines, takes the model and parameter options of `query`, and writes per pair the
 1-based rank of gold among the ranked variants (`-`: not there), the top variant, gold's score, the pair's edit distance and the stage
 that lost a gold that is not ranked (evaluate_arrays); the summary (accuracy@1, MRR, count per reason) goes to stderr or `--summary-json`.
+`mine` has none either: it reads `observed<TAB>correct[<TAB>count]` lines (an --errors list, the gold file of `evaluate`, pairs taken from a
+learned variant list) and writes the table of the change sites of their edit scripts in confusable-list notation, `pattern<TAB>count<TAB>sites`
+(mine_confusables; `--context N`, `--anchors`); `--as-confusables W --min-count N` writes the list `--confusables` reads instead.
 Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
@@ -110,7 +113,7 @@ def json_item(inp: str, variants: Optional[List[dict]], seqnr: int, offset=None,
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m analiticcl_amd", description=__doc__.split("\n\n")[0])
-    p.add_argument("mode", choices=["query", "search", "learn", "score", "evaluate"])
+    p.add_argument("mode", choices=["query", "search", "learn", "score", "evaluate", "mine"])
     p.add_argument("files", nargs="*", help="input files (default: standard input)")
     p.add_argument("--lexicon", "-l", action="append", default=[])
     p.add_argument("--variants", "-V", action="append", default=[])
@@ -146,6 +149,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weighted", action="store_true", help="score mode: two more columns / keys, weight (the confusable weight of the pair under --confusables) and weighted_score = score * weight")
     p.add_argument("--explain", action="store_true", help="query mode: with every variant its edit distance, common substring / prefix / suffix, case flag, "
                                                            "anagram distance, lengths and unweighted score (and the scored entry of a row reached through a variant list)")
+    p.add_argument("--context", type=int, default=0, help="mine mode: code points (0..8) of the neighbouring identities that become part of a pattern")
+    p.add_argument("--anchors", action="store_true", help="mine mode: `^` / `$` on a pattern whose site begins / ends the edit script")
+    p.add_argument("--as-confusables", type=float, default=None, metavar="W",
+                   help="mine mode: write a confusable list (`pattern<TAB>W`) of the representable patterns instead of the table")
+    p.add_argument("--min-count", type=int, default=1, help="mine mode, with --as-confusables: only patterns counted at least this often")
     p.add_argument("--summary-json", default=None, help="evaluate mode: write the summary as JSON to this file instead of as text to standard error")
     p.add_argument("--index-cache", default=None, help="image of the built model: loaded if the file exists (lexicons are then not read), written after build() otherwise")
     p.add_argument("--device", type=int, default=None)
@@ -461,6 +469,41 @@ def run_score(model, a, out) -> None:
     flush()
 
 
+def run_mine(model, a, out) -> None:
+    """`mine`: every input line is `observed<TAB>correct[<TAB>count]`; all pairs are ONE mine_confusables call (the table is over the
+    whole input).  Without lexicons the model is not built and the pairs are scripted on the host."""
+    import json
+    pa: List[str] = []
+    pb: List[str] = []
+    pc: List[int] = []
+    counted = False
+    for line in _lines(a.files):
+        f = (line[:-1] if line.endswith("\r") else line).split("\t")
+        if len(f) < 2:
+            continue
+        pa.append(f[0])
+        pb.append(f[1])
+        if len(f) > 2 and f[2].strip():
+            counted = True
+            pc.append(int(f[2]))
+        else:
+            pc.append(1)
+    conf = None if a.as_confusables is None else (a.as_confusables, a.min_count)
+    r = model.mine_confusables_arrays(pa, pb, pc if counted else None, context=a.context, anchors=a.anchors, as_confusables=conf)
+    if conf is not None:
+        out.write(r["confusables"])
+        return
+    off, text = r["text_off"].tolist(), r["text"]
+    rows = [(text[off[k]:off[k + 1]].decode("utf-8", "surrogateescape"), int(r["count"][k]), int(r["sites"][k]), not (int(r["flags"][k]) & 1))
+            for k in range(len(off) - 1)]
+    if a.json:
+        json.dump([{"pattern": t, "count": c, "sites": s, "representable": ok} for t, c, s, ok in rows], out, ensure_ascii=False, indent=1)
+        out.write("\n")
+    else:
+        for t, c, s, _ok in rows:
+            out.write(f"{t}\t{c}\t{s}\n")
+
+
 def evaluate_tsv_line(inp: str, gold: str, r: dict, top_text: str) -> str:
     """input, gold, 1-based rank of gold in the ranked variants (`-`: not among them), the text of the top variant (empty: none),
     gold_score (the ranked row's dist_score, else the pair's own score), ld (unbounded Damerau-Levenshtein of the pair), reason"""
@@ -521,9 +564,22 @@ def main(argv=None) -> int:
     if a.mode == "learn" and not 0 <= a.iterations <= 255:
         sys.stderr.write("ERROR: --iterations must be in 0..255\n")
         return 2
+    if a.mode == "mine" and not 0 <= a.context <= 8:
+        sys.stderr.write("ERROR: --context must be in 0..8\n")
+        return 2
+    if a.mode == "mine" and not (a.lexicon or a.variants or a.errors or a.index_cache):
+        # nothing to build: the pairs are scripted on the host (the switch ANX_MINE=host), which needs only the library
+        from ._lib import set_switch
+        set_switch("ANX_MINE", "host")
+        weights = Weights(ld=a.weight_ld, lcs=a.weight_lcs, prefix=a.weight_prefix, suffix=a.weight_suffix, case=a.weight_case)
+        run_mine(VariantModel(a.alphabet, weights, debug=a.debug, device=a.device), a, sys.stdout)
+        return 0
     model = make_model(a)
     params = make_params(a)
     out = sys.stdout
+    if a.mode == "mine":
+        run_mine(model, a, out)
+        return 0
     if a.mode == "learn":
         run_learn(model, params, a, out)
         return 0

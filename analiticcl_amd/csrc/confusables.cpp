@@ -96,6 +96,17 @@ std::string edit_script_string(const std::string& source, const std::string& tar
   return out;
 }
 
+void edit_script_ops(const uint32_t* a, size_t la, const uint32_t* b, size_t lb, std::vector<ScriptOp>& out) {
+  HostCtx& h = host_ctx();
+  for (unsigned scale = 1;; scale *= 2) {
+    h.size_for(la, lb, scale);
+    h.load(a, b);
+    if (HC::edit_script(h.c, h.in, h.cand)) break;
+  }
+  out.clear();
+  for (uint32_t i = 0; i < h.c.nd; ++i) out.push_back(ScriptOp{HC::d_op(h.c, i), HC::d_len(h.c, i)});
+}
+
 // the flattened pattern tables host and device read (confusables_core.hpp Patterns)
 void HostModel::rebuild_conf_tables() {
   ConfTables& t = conf_tables;

@@ -576,6 +576,8 @@ const SwitchDef kSwitches[] = {
     {"ANX_SEARCH_PARTS_MIN", [](Switches& s, const char* v) { const long x = v ? atol(v) : 0; s.search_parts_min = x > 0 ? x : (2l << 20); }},
     {"ANX_LEARN_FOLD", [](Switches& s, const char* v) { s.learn_fold_host = v && strcmp(v, "host") == 0; }},
     {"ANX_LEARN_HASH_BITS", [](Switches& s, const char* v) { const int x = v ? atoi(v) : 63; s.learn_hash_bits = x >= 1 && x <= 63 ? x : 63; }},
+    {"ANX_MINE", [](Switches& s, const char* v) { s.mine_host = v && strcmp(v, "host") == 0; }},
+    {"ANX_MINE_HASH_BITS", [](Switches& s, const char* v) { const int x = v ? atoi(v) : 63; s.mine_hash_bits = x >= 1 && x <= 63 ? x : 63; }},
 };
 }  // namespace
 Switches& switches() {

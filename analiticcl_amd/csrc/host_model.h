@@ -113,6 +113,8 @@ struct Switches {
                                      // through the region lists and k_compact_grouped, the path until round 7; A/B)
   int learn_fold_host = 0;           // ANX_LEARN_FOLD=host: learn mode folds its rows with the host loop instead of learn.hip (A/B reference)
   int learn_hash_bits = 63;          // ANX_LEARN_HASH_BITS=1..63 (test hook): bits of the string hash learn.hip keeps; fewer = collisions on demand, same results
+  int mine_host = 0;                 // ANX_MINE=host: anx_mine_confusables scripts every pair on the host (needs neither a built model nor a device; the reference of mine.hip)
+  int mine_hash_bits = 63;           // ANX_MINE_HASH_BITS=1..63 (test hook): bits of the site hash mine.hip keeps; fewer = collisions on demand, same results
 };
 Switches& switches();
 // name = the environment variable's name, value = what the variable would hold; false: unknown name
@@ -209,6 +211,10 @@ struct Confusable {  // src/confusables.rs:5-11; one edit-script pattern with '|
   std::vector<Screen> screen;
 };
 std::string edit_script_string(const std::string& source, const std::string& target);  // sesdiff notation, for tests
+// the same script of two code point strings as (op, length) runs: '=' and '-' runs walk a, '=' and '+' runs walk b, so the texts follow
+// from the positions (anx_mine_confusables' host path)
+struct ScriptOp { uint32_t op, len; };
+void edit_script_ops(const uint32_t* a, size_t la, const uint32_t* b, size_t lb, std::vector<ScriptOp>& out);
 
 // Context rules (src/search.rs:338-524): a pattern over the (vocab id, lexicon mask) pairs of a candidate sequence with a
 // bonus (> 1) or penalty (< 1) score and optional tags.

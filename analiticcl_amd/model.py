@@ -703,6 +703,104 @@ class VariantModel:
         L.check(L.lib().anx_debug_pairs_conf_stats(out))
         return {"pairs": int(out[0]), "screened": int(out[1]), "device_scripts": int(out[2]), "host_pairs": int(out[3])}
 
+    # -- confusable mining --------------------------------------------------------------------------------
+    MINE_SITE_DTYPE = [("pair", "<u4"), ("a_pos", "<u4"), ("a_len", "<u4"), ("b_pos", "<u4"), ("b_len", "<u4"), ("pattern", "<u4"),
+                       ("flags", "<u4"), ("_pad", "<u4")]
+
+    def _mine_call(self, a, b, counts, context, anchors, sites, packed, n=None):
+        import numpy as np
+        if n is None:
+            n = len(a)
+            if len(b) != n:
+                raise ValueError("mine_confusables: a, b and counts differ in length")
+        if counts is not None and len(counts) != n:
+            raise ValueError("mine_confusables: a, b and counts differ in length")
+        mp = L.MineParams()
+        L.lib().anx_default_mine_params(C.byref(mp))
+        mp.context, mp.anchors, mp.no_sites = int(context), 1 if anchors else 0, 0 if sites else 1
+        cnt = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        cptr = None if cnt is None else cnt.ctypes.data_as(C.POINTER(C.c_uint32))
+        res = C.POINTER(L.MineResult)()
+        if packed:
+            ba, bb = (a, b) if packed == "blobs" else (_pack(a), _pack(b))
+            L.check(L.lib().anx_mine_confusables_packed(self.h, ba, len(ba), bb, len(bb), cptr, n, C.byref(mp), C.byref(res)))
+        else:
+            aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in a])
+            ab = (C.c_char_p * max(n, 1))(*[_b(t) for t in b])
+            L.check(L.lib().anx_mine_confusables(self.h, aa, ab, cptr, n, C.byref(mp), C.byref(res)))
+        return res
+
+    def mine_confusables_arrays(self, a: Sequence[str], b: Sequence[str], counts=None, context: int = 0, anchors: bool = False,
+                                sites: bool = False, packed: bool = True, as_confusables: Optional[tuple] = None,
+                                n: Optional[int] = None) -> dict:
+        """anx_mine_confusables: the change sites of shortest_edit_script(a[i], b[i]) of every pair and the table of distinct sites in
+        confusable-list notation, as numpy arrays -- text (bytes: the patterns back to back), text_off (u64 [D + 1]), count, sites
+        (u64 [D]), flags (u32 [D]; bit 0: the pattern holds `[`, `]` or `|` and no list can carry it); rows by count descending, sites
+        descending, pattern bytes ascending.  counts: per-pair counts (u32; None: 1 each).  context: 0..8 code points of the
+        neighbouring identities; anchors: `^` / `$` where the site begins / ends the script.  sites = True adds site_off (u64 [n + 1])
+        and site (a structured array: pair, a_pos, a_len, b_pos, b_len, pattern, flags with bit 0 first / bit 1 last), pair i's sites
+        left to right at site[site_off[i]:site_off[i + 1]].  as_confusables = (weight, min_count): one more key, "confusables", the
+        list `read_confusablelist` reads (anx_format_confusable_list).  packed = "blobs": a and b are the two NUL-separated byte
+        strings anx_mine_confusables_packed takes and n the number of pairs in them."""
+        import numpy as np
+        res = self._mine_call(a, b, counts, context, anchors, sites, packed, n if packed == "blobs" else None)
+        try:
+            r = res.contents
+            D, n = r.n_patterns, r.n_pairs
+            text_off = np.ctypeslib.as_array(r.text_off, shape=(D + 1,)).copy()
+            out = {"text": C.string_at(r.text, int(text_off[D])) if D else b"", "text_off": text_off,
+                   "count": np.ctypeslib.as_array(r.count, shape=(D,)).copy() if D else np.zeros(0, np.uint64),
+                   "sites": np.ctypeslib.as_array(r.sites, shape=(D,)).copy() if D else np.zeros(0, np.uint64),
+                   "flags": np.ctypeslib.as_array(r.flags, shape=(D,)).copy() if D else np.zeros(0, np.uint32),
+                   "n_sites": int(r.n_sites)}
+            if sites:
+                out["site_off"] = np.ctypeslib.as_array(r.site_off, shape=(n + 1,)).copy()
+                dt = np.dtype(self.MINE_SITE_DTYPE)
+                assert dt.itemsize == C.sizeof(L.MineSite)
+                out["site"] = (np.frombuffer(C.string_at(r.site, r.n_sites * dt.itemsize), dtype=dt).copy() if r.n_sites
+                               else np.zeros(0, dtype=dt))
+            if as_confusables is not None:
+                txt = C.c_void_p()
+                L.check(L.lib().anx_format_confusable_list(res, float(as_confusables[0]), int(as_confusables[1]), C.byref(txt)))
+                try:
+                    out["confusables"] = C.string_at(txt.value).decode("utf-8", "surrogateescape")
+                finally:
+                    L.lib().anx_string_free(txt)
+            return out
+        finally:
+            L.lib().anx_mine_result_free(res)
+
+    def mine_confusables(self, a: Sequence[str], b: Sequence[str], counts=None, context: int = 0, anchors: bool = False,
+                         sites: bool = False):
+        """mine_confusables_arrays as a list of dicts (pattern, count, sites, representable) in table order; with sites = True a pair
+        (table, per-pair site lists), a site being a dict (a_pos, a_len, b_pos, b_len, pattern = row of the table, first, last)."""
+        r = self.mine_confusables_arrays(a, b, counts, context, anchors, sites)
+        off, text = r["text_off"].tolist(), r["text"]
+        table = [{"pattern": text[off[k]:off[k + 1]].decode("utf-8", "surrogateescape"), "count": c, "sites": s,
+                  "representable": not (f & L.ANX_MINE_UNREPRESENTABLE)}
+                 for k, (c, s, f) in enumerate(zip(r["count"].tolist(), r["sites"].tolist(), r["flags"].tolist()))]
+        if not sites:
+            return table
+        so, st = r["site_off"].tolist(), r["site"]
+        cols = {k: st[k].tolist() for k in ("a_pos", "a_len", "b_pos", "b_len", "pattern", "flags")}
+        recs = [{"a_pos": cols["a_pos"][j], "a_len": cols["a_len"][j], "b_pos": cols["b_pos"][j], "b_len": cols["b_len"][j],
+                 "pattern": cols["pattern"][j], "first": bool(cols["flags"][j] & L.ANX_MINE_SITE_FIRST),
+                 "last": bool(cols["flags"][j] & L.ANX_MINE_SITE_LAST)} for j in range(len(st))]
+        return table, [recs[so[i]:so[i + 1]] for i in range(len(a))]
+
+    @staticmethod
+    def mine_stats() -> dict:
+        """anx_debug_mine_stats: running totals of the mine calls."""
+        out = (C.c_uint64 * 8)()
+        L.check(L.lib().anx_debug_mine_stats(out))
+        keys = ("device_pairs", "host_pairs", "sites", "patterns", "collision_runs", "odd_shape_pairs", "bytes_up", "bytes_down")
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
+    @staticmethod
+    def mine_chunk(chunk: int) -> None:
+        """anx_debug_mine_chunk (test hook): pairs per chunk of the mine calls that follow; 0 = the default."""
+        L.check(L.lib().anx_debug_mine_chunk(int(chunk)))
+
     # -- gold evaluation ---------------------------------------------------------------------------------
     GOLD_DTYPE = [("gold_vocab_id", "<u4"), ("rank", "<i4"), ("n_results", "<u4"), ("top_vocab_id", "<u4"), ("gold_score", "<f8"),
                   ("ld", "<u2"), ("k", "u1"), ("d", "u1"), ("status", "i1"), ("reason", "u1"), ("_pad", "<u2")]

@@ -42,7 +42,10 @@ extern "C" {
  *    such pairs (additive); the test hooks anx_debug_exclusive_scan and anx_debug_rank_rows (additive); anx_evaluate_gold /
  *    anx_evaluate_gold_packed, the struct anx_gold_eval, the ANX_GOLD_* reasons and the test hook anx_debug_evaluate_gold_chunk
  *    (additive, nothing else changed); the test hook anx_debug_score_slots (additive); anx_batch_fetch_measures, anx_measures_free and
- *    the struct anx_row_measures: the measures behind every ranked row of a batch (additive, nothing else changed). */
+ *    the struct anx_row_measures: the measures behind every ranked row of a batch (additive, nothing else changed);
+ *    anx_mine_confusables / _packed, anx_mine_result_free, anx_default_mine_params, anx_format_confusable_list, the structs
+ *    anx_mine_params / anx_mine_site / anx_mine_result and the hooks anx_debug_mine_stats / anx_debug_mine_chunk: confusable patterns
+ *    mined from string pairs (additive, nothing else changed). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -734,6 +737,65 @@ int anx_evaluate_gold_packed(anx_model *, const char *blob_in, size_t len_in, co
 /* Test hook: the same contract with a caller-chosen chunk size (1 .. 2^20 pairs), so that chunk seams are reached with small calls. */
 int anx_debug_evaluate_gold_chunk(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const anx_params *,
                                   anx_gold_eval *out, anx_pair_score *pairs, size_t chunk);
+
+/* ---- anx_mine_confusables: confusable patterns from (observed, correct) string pairs ---------------------------------------------------
+ * For every pair (a[i], b[i]) the change sites of shortest_edit_script(a[i], b[i]) -- a site is a maximal run of consecutive non-`=`
+ * instructions -- and the table of distinct sites in confusable-list notation with their counts: what a confusable list
+ * (anx_model_read_confusablelist; src/confusables.rs) is written from.  Both strings are decoded as anx_model_confusable_weight_text
+ * decodes them (malformed UTF-8: one byte, one character); nothing is normalised.
+ * The text of a site under (context c, anchors): `^` if anchors and the site is the script's first instruction; `=[` + the last c code
+ * points of the preceding identity (fewer if it is shorter) + `]` if c > 0 and there is one; the site's instructions in sesdiff notation;
+ * `=[` + the first c code points of the following identity + `]` likewise; `$` if anchors and the site is the script's last instruction.
+ * The table has one row per distinct text: sites = how many sites have it, count = the sum of the pairs' counts over those sites
+ * (count[] == NULL: 1 per pair; two equal sites of one pair count twice), ordered by count descending, sites descending, text bytes
+ * ascending.  A text with `[`, `]` or `|` among its characters is flagged ANX_MINE_UNREPRESENTABLE: the list parser could not read it.
+ * The site list holds every pair's sites from left to right, pair i's at site[site_off[i] .. site_off[i + 1]).
+ * The scripts, the sites' keys and the histogram are computed on the model's first replica, in chunks of at most 2^20 pairs; the host
+ * builds the texts of the distinct sites, scripts the pairs the device hands back (a side above 64 code points, a script its working
+ * memory cannot hold) and merges the chunks' tables by text.  ANX_MINE=host (anx_debug_set_switch): every pair on the host -- then the
+ * call needs neither anx_model_build nor a device.  ANX_EINVAL: NULL argument, context > 8; ANX_ENOTBUILT / ANX_ENODEVICE as
+ * anx_score_pairs; ANX_ELIMIT: 2^32 pairs or more, or a packed blob of 4 GB or more.  Thread-safe; each call has its own stream. */
+typedef struct anx_mine_params {
+  uint32_t context;  /* 0 .. 8 code points of the neighbouring identities */
+  uint32_t anchors;  /* != 0: `^` / `$` */
+  uint32_t no_sites; /* != 0: the site list is left out (not downloaded): site == site_off == NULL, n_sites still counts them */
+  uint32_t _reserved;
+} anx_mine_params;
+enum { ANX_MINE_SITE_FIRST = 1, ANX_MINE_SITE_LAST = 2 }; /* anx_mine_site.flags: the site begins / ends the script */
+enum { ANX_MINE_UNREPRESENTABLE = 1 };                    /* anx_mine_result.flags[] */
+typedef struct anx_mine_site {
+  uint32_t pair;                       /* index into a[] / b[] */
+  uint32_t a_pos, a_len, b_pos, b_len; /* code points: a[a_pos, a_pos + a_len) is deleted, b[b_pos, b_pos + b_len) inserted */
+  uint32_t pattern;                    /* row of the table */
+  uint32_t flags;
+  uint32_t _pad;
+} anx_mine_site; /* 32 bytes */
+typedef struct anx_mine_result {
+  size_t n_patterns;
+  const char *text;         /* the texts back to back, UTF-8 */
+  const uint64_t *text_off; /* [n_patterns + 1]: row r = text[text_off[r] .. text_off[r + 1]) */
+  const uint64_t *count;    /* [n_patterns] */
+  const uint64_t *sites;    /* [n_patterns] */
+  const uint32_t *flags;    /* [n_patterns] */
+  size_t n_pairs, n_sites;
+  const uint64_t *site_off; /* [n_pairs + 1], or NULL */
+  const anx_mine_site *site; /* [n_sites], or NULL */
+} anx_mine_result;
+void anx_default_mine_params(anx_mine_params *out);
+int anx_mine_confusables(const anx_model *, const char *const *a, const char *const *b, const uint32_t *count, size_t n,
+                         const anx_mine_params *, anx_mine_result **out);
+int anx_mine_confusables_packed(const anx_model *, const char *blob_a, size_t len_a, const char *blob_b, size_t len_b,
+                                const uint32_t *count, size_t n, const anx_mine_params *, anx_mine_result **out);
+void anx_mine_result_free(anx_mine_result *);
+/* The rows with count >= min_count and no ANX_MINE_UNREPRESENTABLE flag as `pattern<TAB>weight` lines, in table order: a file
+ * anx_model_read_confusablelist reads.  *text: malloc'd (anx_string_free). */
+int anx_format_confusable_list(const anx_mine_result *, double weight, uint64_t min_count, char **text);
+/* Running totals of the mine calls: [0] pairs scripted on the device, [1] pairs scripted on the host, [2] sites, [3] distinct patterns
+ * (summed over calls), [4] hash runs that held more than one text, [5] pairs handed to the host because their script had a site that is
+ * not -[..], +[..] or -[..]+[..], [6] bytes uploaded, [7] bytes downloaded. */
+int anx_debug_mine_stats(uint64_t out[8]);
+/* Test hook: pairs per chunk of the calls that follow (1 .. 2^20; 0: the default, 2^20). */
+int anx_debug_mine_chunk(size_t chunk);
 
 #ifdef __cplusplus
 }
