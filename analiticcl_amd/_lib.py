@@ -92,6 +92,14 @@ GOLD_REASONS = ("RANKED", "STATUS", "NOT_A_RESULT", "EXACT_STOP", "ANAGRAM", "ED
  ANX_GOLD_CROPPED) = range(8)
 
 
+SWEEP_MAX_SETS, GOLD_RANK_BINS = 256, 64  # anx.h ANX_SWEEP_MAX_SETS, ANX_GOLD_RANK_BINS
+
+
+class GoldSummary(C.Structure):  # anx_gold_summary, 624 bytes
+    _fields_ = [("n", C.c_uint64), ("gold_known", C.c_uint64), ("reasons", C.c_uint64 * 8), ("rank_hist", C.c_uint64 * GOLD_RANK_BINS),
+                ("rr_fixed", C.c_uint64), ("n_results", C.c_uint64), ("gained_at_1", C.c_uint64), ("lost_at_1", C.c_uint64)]
+
+
 class MineParams(C.Structure):  # anx_mine_params
     _fields_ = [("context", C.c_uint32), ("anchors", C.c_uint32), ("no_sites", C.c_uint32), ("_reserved", C.c_uint32)]
 
@@ -249,6 +257,13 @@ def lib():
                                                C.POINTER(PairScore)]),
         "anx_debug_evaluate_gold_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(GoldEval),
                                                     C.POINTER(PairScore), sz]),
+        "anx_evaluate_sweep": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), sz, C.POINTER(GoldSummary),
+                                         C.POINTER(GoldEval), C.POINTER(PairScore)]),
+        "anx_evaluate_sweep_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(Params), sz, C.POINTER(GoldSummary),
+                                                C.POINTER(GoldEval), C.POINTER(PairScore)]),
+        "anx_debug_evaluate_sweep_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), sz, C.POINTER(GoldSummary),
+                                                     C.POINTER(GoldEval), C.POINTER(PairScore), sz]),
+        "anx_debug_sweep_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
         "anx_default_mine_params": (None, [C.POINTER(MineParams)]),
         "anx_mine_confusables": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), C.POINTER(C.c_uint32), sz, C.POINTER(MineParams),
                                            C.POINTER(C.POINTER(MineResult))]),

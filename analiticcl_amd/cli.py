@@ -1,4 +1,4 @@
-"""`python -m analiticcl_amd query|search|learn|score|evaluate|mine ...` -- the `analiticcl query` / `search` / `learn` command line
+"""`python -m analiticcl_amd query|search|learn|score|evaluate|mine|sweep ...` -- the `analiticcl query` / `search` / `learn` command line
 (/root/reference/src/bin/analiticcl.rs) on top of the MI355X engine.
 
 Same option names and defaults (note the CLI's own weight defaults 0.5/0.125/0.125/0.125/0.125, bin:760-800, and
@@ -16,6 +16,10 @@ that lost a gold that is not ranked (evaluate_arrays); the summary (accuracy@1, 
 `mine` has none either: it reads `observed<TAB>correct[<TAB>count]` lines (an --errors list, the gold file of `evaluate`, pairs taken from a
 learned variant list) and writes the table of the change sites of their edit scripts in confusable-list notation, `pattern<TAB>count<TAB>sites`
 (mine_confusables; `--context N`, `--anchors`); `--as-confusables W --min-count N` writes the list `--confusables` reads instead.
+`sweep` has none either: it reads the `input<TAB>gold` lines of `evaluate` and a `--grid` of parameter sets (a TSV whose header names
+columns among `k d n t T s freq-weight`; every further line is one set in the syntax of those options, absent columns take the command
+line's value, the first set is the baseline) and writes one TSV line per set (evaluate_sweep: the set's seven parameters, pairs,
+accuracy@1, mrr, ranked share, the eight reason counts, gained@1 / lost@1 against the first set, mean list length).
 Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
@@ -113,7 +117,7 @@ def json_item(inp: str, variants: Optional[List[dict]], seqnr: int, offset=None,
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m analiticcl_amd", description=__doc__.split("\n\n")[0])
-    p.add_argument("mode", choices=["query", "search", "learn", "score", "evaluate", "mine"])
+    p.add_argument("mode", choices=["query", "search", "learn", "score", "evaluate", "mine", "sweep"])
     p.add_argument("files", nargs="*", help="input files (default: standard input)")
     p.add_argument("--lexicon", "-l", action="append", default=[])
     p.add_argument("--variants", "-V", action="append", default=[])
@@ -154,7 +158,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--as-confusables", type=float, default=None, metavar="W",
                    help="mine mode: write a confusable list (`pattern<TAB>W`) of the representable patterns instead of the table")
     p.add_argument("--min-count", type=int, default=1, help="mine mode, with --as-confusables: only patterns counted at least this often")
-    p.add_argument("--summary-json", default=None, help="evaluate mode: write the summary as JSON to this file instead of as text to standard error")
+    p.add_argument("--summary-json", default=None, help="evaluate mode: write the summary as JSON to this file instead of as text to standard error; "
+                                                        "sweep mode: write the summaries as JSON to this file as well")
+    p.add_argument("--grid", default=None, help="sweep mode: TSV file of parameter sets; the header names columns among `k d n t T s freq-weight`, every further "
+                                                "line is one set in the syntax of those options; the first set is the baseline")
     p.add_argument("--index-cache", default=None, help="image of the built model: loaded if the file exists (lexicons are then not read), written after build() otherwise")
     p.add_argument("--device", type=int, default=None)
     p.add_argument("--single-thread", "-1", action="store_true", help="accepted for compatibility, no effect")
@@ -559,6 +566,88 @@ def run_evaluate(model, params, a, out) -> None:
         sys.stderr.write(evaluate_summary_text(summary))
 
 
+GRID_COLUMNS = ("k", "d", "n", "t", "T", "s", "freq-weight")   # the grid's columns, named after query's options (freq-weight: --freq-ranking)
+
+
+def parse_grid(lines, a) -> List[dict]:
+    """The parameter sets of a `sweep --grid` file.  The first line names tab-separated columns among GRID_COLUMNS; every further
+    non-empty line is one set, its cells in the syntax of the options (k / d: an integer, a ratio, or `ratio;limit`; s: 0 or 1).  A
+    column the grid does not have takes the command line's value (`a`: the parsed arguments).  -> one dict per set, GRID_COLUMNS -> the
+    cell as text, in file order; the first set is the baseline."""
+    rows = [ln.rstrip("\r\n") for ln in lines]
+    rows = [ln for ln in rows if ln.strip()]
+    if not rows:
+        raise ValueError("grid: no header line")
+    header = rows[0].split("\t")
+    for c in header:
+        if c not in GRID_COLUMNS:
+            raise ValueError("grid: unknown column %r (known: %s)" % (c, " ".join(GRID_COLUMNS)))
+    if len(set(header)) != len(header):
+        raise ValueError("grid: a column is named twice")
+    base = {"k": str(a.max_anagram_distance), "d": str(a.max_edit_distance), "n": str(a.max_matches), "t": rust_f64(a.score_threshold),
+            "T": rust_f64(a.cutoff_threshold), "s": "1" if a.stop_exact else "0",
+            "freq-weight": rust_f64(a.freq_ranking if a.freq_ranking is not None else 0.0)}
+    sets = []
+    for ln in rows[1:]:
+        cells = ln.split("\t")
+        if len(cells) != len(header):
+            raise ValueError("grid: %r has %d cells, the header %d" % (ln, len(cells), len(header)))
+        d = dict(base)
+        d.update(zip(header, (c.strip() for c in cells)))
+        if d["s"] not in ("0", "1"):
+            raise ValueError("grid: column s is 0 or 1, not %r" % d["s"])
+        sets.append(d)
+    if not sets:
+        raise ValueError("grid: no parameter set")
+    return sets
+
+
+def grid_params(d: dict, a) -> SearchParameters:
+    """One set of parse_grid as SearchParameters (everything the grid cannot name: the command line's)."""
+    import copy
+    b = copy.copy(a)
+    b.max_anagram_distance, b.max_edit_distance, b.max_matches = d["k"], d["d"], int(d["n"])
+    b.score_threshold, b.cutoff_threshold, b.stop_exact, b.freq_ranking = float(d["t"]), float(d["T"]), d["s"] == "1", float(d["freq-weight"])
+    return make_params(b)
+
+
+def sweep_tsv_line(d: dict, s: dict) -> str:
+    """The set's parameters (GRID_COLUMNS), pairs, accuracy@1, mrr, ranked share, the eight reason counts (GOLD_REASONS order), gained@1,
+    lost@1 against the first set, the mean number of variants per input.  s: VariantModel.sweep_summary."""
+    n = s["n"]
+    return "\t".join([d[c] for c in GRID_COLUMNS] + [str(n), rust_f64(s["accuracy_at_1"]), rust_f64(s["mrr"]), rust_f64(s["ranked_share"])] +
+                     [str(s["reasons"][r]) for r in GOLD_REASONS] +
+                     [str(s["gained_at_1"]), str(s["lost_at_1"]), rust_f64(s["n_results"] / n if n else 0.0)])
+
+
+def run_sweep(model, a, out) -> None:
+    """`sweep`: the `input<TAB>gold` lines of the input under every parameter set of --grid in one evaluate_sweep call: one TSV line per
+    set (sweep_tsv_line), in grid order; --summary-json: the same as a JSON list (the set's parameters under "params")."""
+    import json
+    if not a.grid:
+        sys.stderr.write("ERROR: sweep needs --grid\n")
+        sys.exit(2)
+    with open(a.grid, encoding="utf-8", newline="") as f:
+        sets = parse_grid(f.read().split("\n"), a)
+    if len(sets) > 256:
+        sys.stderr.write("ERROR: --grid holds more than 256 parameter sets\n")
+        sys.exit(2)
+    pa: List[str] = []
+    pg: List[str] = []
+    for line in _lines(a.files):
+        x, _, y = (line[:-1] if line.endswith("\r") else line).partition("\t")
+        pa.append(x)
+        pg.append(y.split("\t", 1)[0])
+    summaries = model.evaluate_sweep(pa, pg, [grid_params(d, a) for d in sets])
+    for d, s in zip(sets, summaries):
+        out.write(sweep_tsv_line(d, s) + "\n")
+    out.flush()
+    if a.summary_json:
+        with open(a.summary_json, "w") as f:
+            json.dump([dict(s, params=d) for d, s in zip(sets, summaries)], f, indent=1)
+            f.write("\n")
+
+
 def main(argv=None) -> int:
     a = build_parser().parse_intermixed_args(argv)
     if a.mode == "learn" and not 0 <= a.iterations <= 255:
@@ -585,6 +674,9 @@ def main(argv=None) -> int:
         return 0
     if a.mode == "evaluate":
         run_evaluate(model, params, a, out)
+        return 0
+    if a.mode == "sweep":
+        run_sweep(model, a, out)
         return 0
     if a.json:
         out.write("[\n")

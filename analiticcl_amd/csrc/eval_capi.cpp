@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "eval_gather.h"
 #include "host_model.h"
 
 anx::HostModel& anx_learn_host(anx_model* m);
@@ -27,28 +28,26 @@ int anx_learn_code();
 
 namespace {
 void release_vocab(void* p) { anx::learn_vocab_free(static_cast<anx::LearnVocab*>(p)); }
+}  // namespace
 
-// the ranked rows of the chunk's inputs as sections on replica 0's device (inputs relative to the chunk), then the device pass
-// in == nullptr: the inputs are consecutive NUL-terminated spans of one blob (the packed call): a round's part of it goes to the batch encoder as it is
-int evaluate_chunk(anx_model* m, const char* const* in, const anx::PairSpan* sa, const anx::PairSpan* sg, size_t n, const anx_params* p, anx_gold_eval* out,
-                   anx_pair_score* pairs) {
+// the ranked rows of the chunk's inputs as sections on replica 0's device (inputs relative to the chunk): eval_gather.h
+int anx_eval_gather_rows(anx_model* m, const char* const* in, const anx::PairSpan* sa, size_t n, const anx_params* p, anx_eval_gather& out) {
   const int R = anx_model_num_replicas(m);
-  const int dev0 = anx_model_replica_device(m, 0);
+  const int dev0 = out.dev0 = anx_model_replica_device(m, 0);
   const size_t per_round = std::max<size_t>(1, (size_t)anx::switches().max_batch * (size_t)R);
-  std::vector<void*> bufs;
-  std::vector<anx::LearnSection> secs;
-  std::vector<size_t> sec_rows;
-  std::deque<std::vector<uint32_t>> idx_store;
-  auto release = [&]() { for (void* b : bufs) anx::eval_device_free(dev0, b); };
+  std::vector<void*>& bufs = out.bufs;
+  std::vector<anx::LearnSection>& secs = out.secs;
+  std::vector<size_t>& sec_rows = out.sec_rows;
+  std::deque<std::vector<uint32_t>>& idx_store = out.idx_store;
   for (size_t lo = 0; lo < n; lo += per_round) {
     const size_t cnt = std::min(per_round, n - lo);
     anx_batch* b = in ? anx_batch_encode(m, in + lo, cnt, p)
                       : anx_batch_encode_packed(m, sa[lo].p, (size_t)(sa[lo + cnt - 1].p + sa[lo + cnt - 1].len + 1 - sa[lo].p), cnt, p);
-    if (!b) { release(); const int c = anx_learn_code(); return c ? c : ANX_EINVAL; }
+    if (!b) { const int c = anx_learn_code(); return c ? c : ANX_EINVAL; }
     int rc = anx_batch_run(m, b, nullptr);
+    ++out.batch_runs;
     if (rc == ANX_OK && anx_batch_host_rescored(b)) {
       anx_batch_free(b);
-      release();
       return anx_fail(ANX_EINVAL, "evaluate: confusables are weighted on the host for this model: its ranked rows exist on the host only");
     }
     size_t need = 0;
@@ -88,12 +87,19 @@ int evaluate_chunk(anx_model* m, const char* const* in, const anx::PairSpan* sa,
       sec_rows.push_back(rows);
     }
     anx_batch_free(b);
-    if (rc) { release(); return rc; }
+    if (rc) return rc;
   }
+  return ANX_OK;
+}
+
+namespace {
+int evaluate_chunk(anx_model* m, const char* const* in, const anx::PairSpan* sa, const anx::PairSpan* sg, size_t n, const anx_params* p, anx_gold_eval* out,
+                   anx_pair_score* pairs) {
+  anx_eval_gather rows;
+  if (int rc = anx_eval_gather_rows(m, in, sa, n, p, rows)) return rc;
   std::string err;
   anx::LearnVocab** vocab = reinterpret_cast<anx::LearnVocab**>(anx_learn_vocab_slot(m, release_vocab));
-  const int rc = anx::evaluate_chunk(anx_learn_host(m), anx_replica_of(m, 0), vocab, sa, sg, n, *p, secs, sec_rows, out, pairs, err);
-  release();
+  const int rc = anx::evaluate_chunk(anx_learn_host(m), anx_replica_of(m, 0), vocab, sa, sg, n, *p, rows.secs, rows.sec_rows, out, pairs, err);
   return rc ? anx_fail(rc, err) : ANX_OK;
 }
 

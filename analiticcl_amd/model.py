@@ -873,6 +873,71 @@ class VariantModel:
                 "mrr": float(rr.sum()) / n if n else 0.0,
                 "reasons": {name: int(counts[i]) for i, name in enumerate(L.GOLD_REASONS)}}
 
+    # -- parameter sweep ---------------------------------------------------------------------------------
+    SUMMARY_DTYPE = [("n", "<u8"), ("gold_known", "<u8"), ("reasons", "<u8", (8,)), ("rank_hist", "<u8", (L.GOLD_RANK_BINS,)),
+                     ("rr_fixed", "<u8"), ("n_results", "<u8"), ("gained_at_1", "<u8"), ("lost_at_1", "<u8")]
+
+    def evaluate_sweep_arrays(self, inputs: Sequence[str], gold: Sequence[str], params_list: Sequence[SearchParameters],
+                              with_records: bool = False, with_pairs: bool = False, packed: bool = True, chunk: Optional[int] = None):
+        """anx_evaluate_sweep: evaluate_arrays' question for every parameter set of params_list over the same pairs, answered per
+        set as a summary the device reduced -- a numpy structured array (SUMMARY_DTYPE = anx_gold_summary: n, gold_known, reasons[8],
+        rank_hist[64] with every rank >= 63 in the last bin, rr_fixed = sum of floor(2^32 / (rank + 1)), n_results, gained_at_1 /
+        lost_at_1 against params_list[0]) with one element per set.  What does not depend on the set (upload, encoder, pair
+        measures, gold lookup) runs once per chunk.  with_records: also the (P, n) array of the records evaluate_arrays returns per
+        set; with_pairs: also the anx_pair_score records.  Returns the summaries alone, or a tuple (summaries[, records][, pairs]).
+        packed = False: the pointer form of the call; chunk: the test hook with a caller-chosen chunk size (pointer form)."""
+        import numpy as np
+        n, P = len(inputs), len(params_list)
+        if len(gold) != n:
+            raise ValueError("evaluate_sweep: inputs and gold differ in length")
+        dt = np.dtype(self.SUMMARY_DTYPE)
+        assert dt.itemsize == C.sizeof(L.GoldSummary)
+        sums = np.zeros(max(P, 1), dtype=dt)
+        sptr = sums.ctypes.data_as(C.POINTER(L.GoldSummary))
+        sets = (L.Params * max(P, 1))(*[p._c() for p in params_list])
+        rec = np.zeros((max(P, 1), max(n, 1)), dtype=np.dtype(self.GOLD_DTYPE)) if with_records else None   # [P][n] set-major (n == 0: untouched)
+        optr = rec.ctypes.data_as(C.POINTER(L.GoldEval)) if with_records else None
+        pairs = np.zeros(max(n, 1), dtype=np.dtype(self.PAIR_DTYPE)) if with_pairs else None
+        pptr = pairs.ctypes.data_as(C.POINTER(L.PairScore)) if with_pairs else None
+        if packed and chunk is None:
+            ba, bg = _pack(inputs), _pack(gold)
+            L.check(L.lib().anx_evaluate_sweep_packed(self.h, ba, len(ba), bg, len(bg), n, sets, P, sptr, optr, pptr))
+        else:
+            aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
+            ag = (C.c_char_p * max(n, 1))(*[_b(t) for t in gold])
+            if chunk is None:
+                L.check(L.lib().anx_evaluate_sweep(self.h, aa, ag, n, sets, P, sptr, optr, pptr))
+            else:
+                L.check(L.lib().anx_debug_evaluate_sweep_chunk(self.h, aa, ag, n, sets, P, sptr, optr, pptr, int(chunk)))
+        res = (sums[:P],) + ((rec[:P, :n],) if with_records else ()) + ((pairs[:n],) if with_pairs else ())
+        return res if len(res) > 1 else res[0]
+
+    @staticmethod
+    def sweep_summary(s) -> dict:
+        """One element of evaluate_sweep_arrays' summaries as a dict: evaluate_summary's keys (accuracy_at_1 = rank_hist[0] / n,
+        ranked_share = reasons[RANKED] / n, mrr = rr_fixed / 2^32 / n) plus rank_hist, n_results, gained_at_1 and lost_at_1."""
+        n = int(s["n"])
+        reasons = [int(x) for x in s["reasons"]]
+        hist = [int(x) for x in s["rank_hist"]]
+        return {"n": n, "gold_known": int(s["gold_known"]),
+                "accuracy_at_1": hist[0] / n if n else 0.0,
+                "ranked_share": reasons[L.ANX_GOLD_RANKED] / n if n else 0.0,
+                "mrr": int(s["rr_fixed"]) / 4294967296.0 / n if n else 0.0,
+                "reasons": {name: reasons[i] for i, name in enumerate(L.GOLD_REASONS)},
+                "rank_hist": hist, "n_results": int(s["n_results"]), "gained_at_1": int(s["gained_at_1"]), "lost_at_1": int(s["lost_at_1"])}
+
+    def evaluate_sweep(self, inputs: Sequence[str], gold: Sequence[str], params_list: Sequence[SearchParameters]) -> List[dict]:
+        """evaluate_sweep_arrays as one dict per parameter set (sweep_summary)."""
+        return [self.sweep_summary(s) for s in self.evaluate_sweep_arrays(inputs, gold, params_list)]
+
+    @staticmethod
+    def sweep_stats() -> dict:
+        """anx_debug_sweep_stats: running totals of the sweep calls since process start."""
+        keys = ("calls", "chunks", "sets", "pair_passes", "lookups", "batch_runs", "bytes_down")
+        out = (C.c_uint64 * len(keys))()
+        L.check(L.lib().anx_debug_sweep_stats(out, len(keys)))
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
     def query_output(self, inputs: Sequence[str], params: SearchParameters, json: bool = False,
                      output_lexmatch: bool = False, first_seqnr: int = 1) -> str:
         """One device batch + the text `analiticcl query` prints for it (anx_format_query_output: the TSV lines or JSON

@@ -45,7 +45,8 @@ extern "C" {
  *    the struct anx_row_measures: the measures behind every ranked row of a batch (additive, nothing else changed);
  *    anx_mine_confusables / _packed, anx_mine_result_free, anx_default_mine_params, anx_format_confusable_list, the structs
  *    anx_mine_params / anx_mine_site / anx_mine_result and the hooks anx_debug_mine_stats / anx_debug_mine_chunk: confusable patterns
- *    mined from string pairs (additive, nothing else changed). */
+ *    mined from string pairs (additive, nothing else changed); anx_evaluate_sweep / _packed, the struct anx_gold_summary and the hooks
+ *    anx_debug_evaluate_sweep_chunk / anx_debug_sweep_stats: several parameter sets over the same gold pairs (additive). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -737,6 +738,57 @@ int anx_evaluate_gold_packed(anx_model *, const char *blob_in, size_t len_in, co
 /* Test hook: the same contract with a caller-chosen chunk size (1 .. 2^20 pairs), so that chunk seams are reached with small calls. */
 int anx_debug_evaluate_gold_chunk(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const anx_params *,
                                   anx_gold_eval *out, anx_pair_score *pairs, size_t chunk);
+
+/* ---- parameter sweep: several parameter sets over the same gold pairs in one pass, the summary reduced on the device -------------------
+ * For every set s of sets[0 .. n_sets), summaries[s] holds the integers one gets by reducing the records that
+ * anx_evaluate_gold(model, inputs, gold, n, &sets[s], ...) writes for the same pairs -- every field equal, whatever the order in which
+ * the device's blocks arrive (the summary is integers only; nothing is summed in floating point):
+ *   n, gold_known   pairs; pairs whose gold_vocab_id != UINT32_MAX
+ *   reasons[r]      pairs whose reason is the ANX_GOLD_* value r
+ *   rank_hist[b]    ranked pairs by rank; the last bin holds every rank >= ANX_GOLD_RANK_BINS - 1
+ *   rr_fixed        sum over ranked pairs of floor(2^32 / (rank + 1)): the reciprocal ranks as 32.32 fixed point
+ *   n_results       sum of the records' n_results: how long the lists get under this set
+ *   gained_at_1, lost_at_1   pairs whose gold is at rank 0 under this set but not under sets[0], and the reverse (both 0 for sets[0])
+ * The host derives accuracy@1 = rank_hist[0] / n, ranked share = reasons[ANX_GOLD_RANKED] / n and mrr = rr_fixed / 2^32 / n.
+ * out (may be NULL): [n_sets][n], set-major; out[s * n .. (s + 1) * n) is byte for byte what anx_evaluate_gold writes under sets[s].
+ * pairs (may be NULL): [n], byte for byte what anx_score_pairs writes; it does not depend on the set.
+ * Per chunk of at most 2^20 pairs the work that does not depend on the set runs once and stays on replica 0's device (one upload of the
+ * 2 n strings, the encoder, the pair kernels, the vocabulary lookup of the gold strings, the vocabulary flags); per set the inputs go
+ * through the staged batch path with that set, the rows are gathered onto replica 0 as anx_evaluate_gold gathers them, and
+ * k_sweep_sections / k_sweep_rows / k_sweep_classify find the ranks, classify with the set's clamped k / d per input and reduce.  With
+ * out == NULL the pass downloads 624 bytes per set and chunk; the summaries of a call's chunks are added up.
+ * Errors and limits are anx_evaluate_gold's (the learn lock is held for the call; confusables weighted on the host are refused), and:
+ * ANX_EINVAL for n_sets == 0, n_sets > ANX_SWEEP_MAX_SETS, sets == NULL or summaries == NULL; n == 0 zeroes the summaries and returns
+ * ANX_OK without a build or a device.  The weights are the model's: a sweep over weights, confusable lists or variant lists is not
+ * built.  _packed: the blobs as anx_evaluate_gold_packed. */
+#define ANX_SWEEP_MAX_SETS 256
+#define ANX_GOLD_RANK_BINS 64
+typedef struct anx_gold_summary {
+  uint64_t n;
+  uint64_t gold_known;
+  uint64_t reasons[8];
+  uint64_t rank_hist[ANX_GOLD_RANK_BINS];
+  uint64_t rr_fixed;
+  uint64_t n_results;
+  uint64_t gained_at_1, lost_at_1;
+} anx_gold_summary; /* 624 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(anx_gold_summary) == 624, "anx_gold_summary is 624 bytes");
+#else
+_Static_assert(sizeof(anx_gold_summary) == 624, "anx_gold_summary is 624 bytes");
+#endif
+int anx_evaluate_sweep(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const anx_params *sets, size_t n_sets,
+                       anx_gold_summary *summaries, anx_gold_eval *out, anx_pair_score *pairs);
+int anx_evaluate_sweep_packed(anx_model *, const char *blob_in, size_t len_in, const char *blob_gold, size_t len_gold, size_t n,
+                              const anx_params *sets, size_t n_sets, anx_gold_summary *summaries, anx_gold_eval *out, anx_pair_score *pairs);
+/* Test hook: the pointer form with a caller-chosen chunk size (1 .. 2^20 pairs). */
+int anx_debug_evaluate_sweep_chunk(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const anx_params *sets,
+                                   size_t n_sets, anx_gold_summary *summaries, anx_gold_eval *out, anx_pair_score *pairs, size_t chunk);
+/* Running totals of the sweep calls since process start, the first min(n, 7) of: [0] calls, [1] chunks, [2] sets run (per chunk),
+ * [3] pair-side passes (upload, encoder, pair kernels: one per chunk), [4] gold lookups (one per chunk), [5] batch runs, [6] bytes the
+ * sweep's own pass downloaded (624 per set and chunk, + 32 per pair and set with `out`, + 24 per pair with `pairs`; the batch path's
+ * control reads inside anx_batch_run are not part of it). */
+int anx_debug_sweep_stats(uint64_t *out, int n);
 
 /* ---- anx_mine_confusables: confusable patterns from (observed, correct) string pairs ---------------------------------------------------
  * For every pair (a[i], b[i]) the change sites of shortest_edit_script(a[i], b[i]) -- a site is a maximal run of consecutive non-`=`
