@@ -53,6 +53,12 @@ class SearchParams(C.Structure):
                 ("variantmodel_weight", C.c_float), ("contextrules_weight", C.c_float), ("unicodeoffsets", C.c_int32)]
 
 
+class LatticeDebug(C.Structure):  # anx_lattice_debug
+    _fields_ = [("budget_nodes", C.c_uint64), ("launch_of", C.c_void_p), ("width_of", C.c_void_p), ("lds_of", C.c_void_p),
+                ("nodes", C.c_void_p), ("lm", C.c_void_p), ("marks", C.c_void_p), ("cnts", C.c_void_p), ("ctxval", C.c_void_p),
+                ("lds_limit", C.c_uint32), ("n_launches", C.c_uint32)]
+
+
 class Match(C.Structure):
     _fields_ = [("begin", C.c_size_t), ("end", C.c_size_t), ("n", C.c_uint32), ("selected", C.c_int32),
                 ("var_begin", C.c_size_t), ("var_end", C.c_size_t), ("tag_begin", C.c_uint32),
@@ -301,6 +307,9 @@ def lib():
         "anx_debug_rank_rows": (C.c_int, [C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_uint64, C.c_float, C.c_int,
                                           C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
         "anx_debug_score_slots": (C.c_int, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+        "anx_debug_lattice_decode": (C.c_int, [vp, C.POINTER(SearchParams), C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t,
+                                               vp, vp, vp, C.POINTER(LatticeDebug)]),
+        "anx_debug_portable_log": (C.c_int, [vp, C.c_size_t, vp]),
         "anx_batch_free": (None, [vp]),
         "anx_device_pool_trim": (None, [C.c_int]),
     }

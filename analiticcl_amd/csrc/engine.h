@@ -184,8 +184,28 @@ struct LatView {
 };
 // out_n[i] = symbols on the chosen path of stretch i (0xFFFFFFFF: not decoded here -> the host decoder), out_syms[st[i].out0 ..]
 // decodes the lattices [first, first + count) of the view on the replica `dl` (a multi-device model gives every replica a share)
+// The test record of anx_debug_lattice_decode (nullptr in production: nothing below happens).  budget_nodes replaces the driver's node
+// budget of a launch; the device pools start as 0xFF bytes and, per launch and before they are reused or freed, come back to the
+// caller's arrays.  Stretch j (relative to the decoded sub-range) owns the states [state_off(j), state_off(j) + nstates + 1) of those
+// arrays, state_off = the running sum of nstates + 1; a state owns K nodes / (K + 3 & ~3) mark bytes / one count; a stretch K ctxval.
+struct LatDebug {
+  uint64_t budget_nodes = 0;       // in: nodes per launch, 0 = the driver's own
+  uint32_t* launch_of = nullptr;   // [count]: the launch that took stretch j
+  uint32_t* width_of = nullptr;    // [count]: lanes per stretch of its kernels (32 | 64)
+  uint32_t* lds_of = nullptr;      // [count]: dynamic LDS bytes per block of its k_lattice launch
+  uint32_t* nodes = nullptr;       // [states * K * 3]: (cost bits, parent, symbol)
+  uint32_t* lm = nullptr;          // [states * K * 3]: (lp bits, n, prev), written with an LM only
+  uint8_t* marks = nullptr;        // [states * (K + 3 & ~3)], written with an LM only
+  uint16_t* cnts = nullptr;        // [states]
+  double* ctxval = nullptr;        // [count * K], written with rules only
+  uint32_t lds_limit = 0;          // out: the device's dynamic LDS limit per block the routing used
+  uint32_t n_launches = 0;         // out
+};
 int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& in, size_t first, size_t count, const anx_search_params& p,
                    uint32_t* out_n, uint32_t* out_syms, std::string& err);
+// the same with the test record (lattice.hip only: anx_debug_lattice_decode lives there, so the host-only build needs no stub of it)
+int lattice_decode_dbg(const HostModel& m, const DeviceLexicon* dl, const LatView& in, size_t first, size_t count, const anx_search_params& p,
+                       uint32_t* out_n, uint32_t* out_syms, std::string& err, LatDebug* dbg);
 void batch_free(Batch*);
 
 // ---- caller-chosen string pairs (pairs.hip): anx_score_pairs ------------------------------------------------------------------------

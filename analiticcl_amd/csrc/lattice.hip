@@ -21,7 +21,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <ctime>
 #include <functional>
 #include <mutex>
@@ -686,7 +688,7 @@ static int lm_ensure(const HostModel& m, const DeviceLexicon* dl, std::string& e
 static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vector<LatStretch>& hst, const std::vector<uint32_t>& maxdeg, LatStretch* d_st,
                           const uint32_t* d_inoff, const LatArc* d_arcs, const LatSym* d_syms, size_t nsyms_cap, const uint32_t* d_boff, const int32_t* d_btok, uint32_t* d_outn,
                           uint32_t* d_outs, uint32_t* d_outcover, const anx_search_params& p, hipStream_t st, const std::function<int()>& after_stretch_upload, std::vector<void*>& owned,
-                          std::string& err) {
+                          std::string& err, LatDebug* dbg = nullptr) {
   const size_t n = hst.size();
   const DeviceLm* lm = dl->dlm;
   const uint32_t K = std::max<uint32_t>(1u, p.max_seq);
@@ -696,12 +698,25 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
   // node pool: (nstates + 1) * K nodes per stretch; launches of as many stretches as fit the budget
   // (with context rules a node also owns two words of the rules' scratch: the same bytes hold fewer nodes)
   const bool rules_on = lm->nrules > 0 && d_outcover;
-  const size_t budget_nodes = ((size_t)6 << 30) / (sizeof(LNode) + (rules_on ? 2 * sizeof(uint32_t) : 0));
+  const size_t budget_nodes = dbg && dbg->budget_nodes ? (size_t)dbg->budget_nodes : ((size_t)6 << 30) / (sizeof(LNode) + (rules_on ? 2 * sizeof(uint32_t) : 0));
   // Launch order: the stretches none of whose states has more than 64 incoming arcs (and whose cost ring fits half the LDS budget)
   // first, by decreasing number of states -- k_lattice<32> decodes them two per wave, neighbours of this order side by side --,
   // then the others (k_lattice<64>: one per wave, up to 128 incoming arcs).
-  const uint32_t ring_cap64 = (uint32_t)std::max<size_t>(3, ((size_t)48 << 10) / ((size_t)K * sizeof(float))) - 1u;  // one list of K words beside the rings
-  const uint32_t ring_cap32 = (uint32_t)std::max<size_t>(3, ((size_t)24 << 10) / ((size_t)K * sizeof(float))) - 1u;
+  uint32_t ring_cap64 = (uint32_t)std::max<size_t>(3, ((size_t)48 << 10) / ((size_t)K * sizeof(float))) - 1u;  // one list of K words beside the rings
+  uint32_t ring_cap32 = (uint32_t)std::max<size_t>(3, ((size_t)24 << 10) / ((size_t)K * sizeof(float))) - 1u;
+  // The floor of 3 lists is more than 24 KB per stretch once K passes 2048 (two stretches of a narrow block: ~100 KB at K = 4096):
+  // both caps shrink to what the device takes as a block's dynamic LDS with the longest count array.  A stretch whose ring no longer
+  // fits the narrow kernel goes to the wide one; with a cap of 0 a kernel takes nothing (a ring is at least 1) and k_lattice hands
+  // back whatever it is sent -- a launch the device would refuse is never made.
+  int lds_attr = 0;
+  HIP_TRY(hipDeviceGetAttribute(&lds_attr, hipDeviceAttributeMaxSharedMemoryPerBlock, dl->device));
+  const size_t lds_limit = (size_t)std::max(lds_attr, 0);
+  auto lds_bytes = [&](uint32_t lanes, uint32_t ring_max, uint32_t cnt_cap) {  // cost rings + the merged state's (arc, rank) list + the per-state node counts
+    return (size_t)(64u / lanes) * (((size_t)ring_max + 1u) * K * sizeof(float) + (size_t)cnt_cap * sizeof(uint16_t));
+  };
+  while (ring_cap64 > 0u && lds_bytes(64u, ring_cap64, LAT_MAX_STATES) > lds_limit) --ring_cap64;
+  while (ring_cap32 > 0u && lds_bytes(32u, ring_cap32, LAT_MAX_STATES) > lds_limit) --ring_cap32;
+  if (dbg) dbg->lds_limit = (uint32_t)std::min<size_t>(lds_limit, 0xFFFFFFFFu);
   std::vector<uint32_t> order;
   order.reserve(n);
   std::vector<uint32_t> wide;
@@ -757,6 +772,15 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
   a.nrules = rules_on ? lm->nrules : 0u;
   a.ctxseq = d_ctxseq; a.ctxval = d_ctxval; a.out_cover = rules_on ? d_outcover : nullptr;
   a.index = d_index;
+  // the test record: where stretch j's states lie in the caller's arrays
+  std::vector<size_t> dbg_state0;
+  if (dbg) {
+    dbg_state0.assign(n + 1, 0);
+    for (size_t j = 0; j < n; ++j) dbg_state0[j + 1] = dbg_state0[j] + hst[j].nstates + 1u;
+    dbg->n_launches = (uint32_t)launches.size();
+  }
+  const size_t MKb = (K + 3u) & ~3u;
+  uint32_t launch_no = 0;
   // LDS ring of cost lists: as many states as the widest arc of the launch's stretches spans (+ 1), capped by 48 KB per wave
   for (const Launch& l : launches) {
     uint32_t ring_need = 2;
@@ -765,9 +789,17 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
     uint32_t cnt_cap = 2;
     for (uint32_t i = 0; i < l.count; ++i) cnt_cap = std::max(cnt_cap, std::min(hst[order[l.first + i]].nstates + 1u, LAT_MAX_STATES));
     a.cnt_cap = (cnt_cap + 1u) & ~1u;
-    // cost rings + the merged state's (arc, rank) list + the per-state node counts
-    const size_t lds = (size_t)(64u / l.lanes) * (((size_t)a.ring_max + 1u) * K * sizeof(float) + (size_t)a.cnt_cap * sizeof(uint16_t));
+    const size_t lds = lds_bytes(l.lanes, a.ring_max, a.cnt_cap);
     a.first = l.first; a.count = l.count;
+    size_t used = 0;  // nodes of this launch
+    if (dbg) {        // what the kernels do not write stays visible
+      for (uint32_t i = 0; i < l.count; ++i) used += (size_t)(hst[order[l.first + i]].nstates + 1u) * K;
+      HIP_TRY(hipMemsetAsync(d_nodes, 0xFF, used * sizeof(LNode), st));
+      if (d_lm) HIP_TRY(hipMemsetAsync(d_lm, 0xFF, used * sizeof(LmNode), st));
+      if (d_marks) HIP_TRY(hipMemsetAsync(d_marks, 0xFF, used / K * MKb, st));
+      HIP_TRY(hipMemsetAsync(d_cnts, 0xFF, (used / K + 1) * sizeof(uint16_t), st));
+      if (d_ctxval) HIP_TRY(hipMemsetAsync(d_ctxval, 0xFF, (used / 2 + 1) * sizeof(double), st));
+    }
     const int kt = ktimer_begin("k_lattice", st);
     if (l.lanes == 32u) hipLaunchKernelGGL(k_lattice<32>, dim3((l.count + 1u) / 2u), dim3(64), lds, st, a);
     else hipLaunchKernelGGL(k_lattice<64>, dim3(l.count), dim3(64), lds, st, a);
@@ -782,6 +814,23 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
     if (l.lanes == 32u) hipLaunchKernelGGL(k_lattice_lm<32>, dim3((l.count + 1u) / 2u), dim3(64), 0, st, a);
     else hipLaunchKernelGGL(k_lattice_lm<64>, dim3(l.count), dim3(64), 0, st, a);
     ktimer_end(kt2, st);
+    if (dbg) {  // the pools of this launch, before the next launch reuses them
+      HIP_TRY(hipStreamSynchronize(st));
+      HIP_TRY(hipGetLastError());
+      for (uint32_t i = 0; i < l.count; ++i) {
+        const uint32_t j = order[l.first + i];
+        const size_t s0 = dbg_state0[j], nst_j = (size_t)hst[j].nstates + 1u, node0 = (size_t)hst[j].node0;
+        if (dbg->launch_of) dbg->launch_of[j] = launch_no;
+        if (dbg->width_of) dbg->width_of[j] = l.lanes;
+        if (dbg->lds_of) dbg->lds_of[j] = (uint32_t)lds;
+        if (dbg->nodes) HIP_TRY(hipMemcpy(dbg->nodes + s0 * K * 3u, d_nodes + node0, nst_j * K * sizeof(LNode), hipMemcpyDeviceToHost));
+        if (dbg->lm && d_lm) HIP_TRY(hipMemcpy(dbg->lm + s0 * K * 3u, d_lm + node0, nst_j * K * sizeof(LmNode), hipMemcpyDeviceToHost));
+        if (dbg->marks && d_marks) HIP_TRY(hipMemcpy(dbg->marks + s0 * MKb, d_marks + node0 / K * MKb, nst_j * MKb, hipMemcpyDeviceToHost));
+        if (dbg->cnts) HIP_TRY(hipMemcpy(dbg->cnts + s0, d_cnts + node0 / K, nst_j * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        if (dbg->ctxval && d_ctxval) HIP_TRY(hipMemcpy(dbg->ctxval + (size_t)j * K, d_ctxval + node0 / 2u, (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
+      }
+    }
+    ++launch_no;
   }
   HIP_TRY(hipGetLastError());
   return ANX_OK;
@@ -789,8 +838,8 @@ static int lattice_launch(const HostModel& m, const DeviceLexicon* dl, std::vect
 
 // Decodes the stretches of `in` on the replica `dl`.  out_n[i] = symbols of the chosen path of stretch i (0xFFFFFFFF: not decoded,
 // the caller's host decoder takes it), out_syms[st[i].out0 ..] = their local symbol ids in path order.
-int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& whole, size_t first, size_t count, const anx_search_params& p,
-                   uint32_t* out_n, uint32_t* out_syms, std::string& err) {
+int lattice_decode_dbg(const HostModel& m, const DeviceLexicon* dl, const LatView& whole, size_t first, size_t count, const anx_search_params& p,
+                              uint32_t* out_n, uint32_t* out_syms, std::string& err, LatDebug* dbg) {
   if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
   HIP_TRY(hipSetDevice(dl->device));
   if (!count) return ANX_OK;
@@ -836,6 +885,11 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& w
     return rc;
   uint32_t* d_outcover = nullptr;
   if (rules && (rc = dalloc_((void**)&d_outcover, nout * 4))) return rc;
+  if (dbg) {  // the words no kernel writes come back as the fill
+    HIP_TRY(hipMemsetAsync(d_outn, 0xFF, std::max<size_t>(n * 4, 16), st));
+    HIP_TRY(hipMemsetAsync(d_outs, 0xFF, std::max<size_t>(nout * 4, 16), st));
+    if (d_outcover) HIP_TRY(hipMemsetAsync(d_outcover, 0xFF, std::max<size_t>(nout * 4, 16), st));
+  }
   std::vector<LatStretch> hst(in.st, in.st + n);
   std::vector<uint32_t> maxdeg(n, 0u);
   for (size_t j = 0; j < n; ++j) {  // indices relative to the uploaded parts
@@ -846,13 +900,13 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& w
   }
   auto uploads = [&]() -> int {
     HIP_TRY(hipMemcpyAsync(d_inoff, in.in_off, in.nin * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_arcs, in.arcs, in.narcs * sizeof(LatArc), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_syms, in.syms, in.nsyms * sizeof(LatSym), hipMemcpyHostToDevice, st));
+    if (in.narcs) HIP_TRY(hipMemcpyAsync(d_arcs, in.arcs, in.narcs * sizeof(LatArc), hipMemcpyHostToDevice, st));
+    if (in.nsyms) HIP_TRY(hipMemcpyAsync(d_syms, in.syms, in.nsyms * sizeof(LatSym), hipMemcpyHostToDevice, st));  // (the test hook's lattices may have none)
     HIP_TRY(hipMemcpyAsync(d_boff, in.btok_off, in.nboff * 4, hipMemcpyHostToDevice, st));
     if (in.nbtok) HIP_TRY(hipMemcpyAsync(d_btok, in.btok, in.nbtok * 4, hipMemcpyHostToDevice, st));
     return ANX_OK;
   };
-  if ((rc = lattice_launch(m, dl, hst, maxdeg, d_st, d_inoff, d_arcs, d_syms, in.nsyms, d_boff, d_btok, d_outn, d_outs, d_outcover, p, st, uploads, owned, err))) return rc;
+  if ((rc = lattice_launch(m, dl, hst, maxdeg, d_st, d_inoff, d_arcs, d_syms, in.nsyms, d_boff, d_btok, d_outn, d_outs, d_outcover, p, st, uploads, owned, err, dbg))) return rc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_n, d_outn, n * 4, hipMemcpyDeviceToHost, st));
   if (nout) HIP_TRY(hipMemcpyAsync(out_syms, d_outs, nout * 4, hipMemcpyDeviceToHost, st));
@@ -860,7 +914,10 @@ int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& w
   HIP_TRY(hipStreamSynchronize(st));
   return ANX_OK;
 }
-
+int lattice_decode(const HostModel& m, const DeviceLexicon* dl, const LatView& whole, size_t first, size_t count, const anx_search_params& p,
+                   uint32_t* out_n, uint32_t* out_syms, std::string& err) {
+  return lattice_decode_dbg(m, dl, whole, first, count, p, out_n, out_syms, err, nullptr);
+}
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // Search mode in ONE device pass (round 5).  Until round 4 a part of a find_all_matches call downloaded every ranked row of every
@@ -1244,3 +1301,114 @@ int search_onepass_rows_wait(OnePassState* S, std::string& err) {
 }
 
 }  // namespace anx
+
+const anx::HostModel& anx_host_of(const anx_model* m);  // capi.cpp
+const anx::DeviceLexicon* anx_replica_of(const anx_model* m, size_t i);
+int anx_fail(int code, const std::string& msg);
+extern "C" {
+// test hook: the device lattice decoder alone on the caller's lattices (include/anx.h; tests/test_gpu_lattice_door.py).  Everything is
+// validated here, on the host, before lattice_decode sees it: the kernels index with these words.  (In this file, beside lattice_decode:
+// the host-only build of the library, which stubs the engine, has no use for it.)
+int anx_debug_lattice_decode(const anx_model* model, const anx_search_params* sp, size_t nst, const uint32_t* nstates, const uint32_t* in_off,
+                             const uint32_t* arcs, const uint32_t* nsyms, const uint32_t* syms, const uint32_t* btok_off, const int32_t* btok,
+                             const float* best_cost_init, size_t first, size_t count, uint32_t* out_n, uint32_t* out_syms, uint32_t* out_cover,
+                             anx_lattice_debug* dbg) {
+  if (!model || !sp || !nstates || !in_off || !nsyms || !btok_off || !best_cost_init || !out_n || !out_syms) return anx_fail(ANX_EINVAL, "NULL argument");
+  if (nst == 0 || nst > (1u << 20)) return anx_fail(ANX_EINVAL, "lattice door: 1 .. 2^20 stretches");
+  auto refuse = [&](size_t s, const char* what) { return anx_fail(ANX_EINVAL, "lattice door: stretch " + std::to_string(s) + ": " + what); };
+  // sizes first: they place every output, and the outputs start as the fill whatever happens next
+  size_t out_total = 0;
+  for (size_t s = 0; s < nst; ++s) {
+    if (nstates[s] < 1u || nstates[s] > 65535u) return refuse(s, "nstates outside 1 .. 65535");
+    out_total += nstates[s];
+  }
+  memset(out_n, 0xFF, nst * sizeof(uint32_t));
+  memset(out_syms, 0xFF, out_total * sizeof(uint32_t));
+  if (out_cover) memset(out_cover, 0xFF, out_total * sizeof(uint32_t));
+  const anx::HostModel& m = anx_host_of(model);
+  const bool rules = !m.context_rules.empty();
+  if (rules && !out_cover) return anx_fail(ANX_EINVAL, "lattice door: a model with context rules needs out_cover");
+  if (first > nst || count > nst - first) return anx_fail(ANX_EINVAL, "lattice door: the sub-range lies outside the view");
+  const uint32_t K = std::max<uint32_t>(1u, sp->max_seq);
+  if (!std::isfinite(sp->lm_weight) || !std::isfinite(sp->variantmodel_weight) || !std::isfinite(sp->contextrules_weight))
+    return anx_fail(ANX_EINVAL, "lattice door: a weight is not finite");
+  auto cost_ok = [](uint32_t bits) { float f; memcpy(&f, &bits, 4); return !(bits >> 31) && std::isfinite(f) && f <= 1e6f; };
+  const size_t nvocab = m.decoder.size();
+  std::vector<anx::LatStretch> st(nst);
+  size_t in_pos = 0, arc_pos = 0, sym_pos = 0, boff_pos = 0, btok_pos = 0, out_pos = 0, nodes = 0;
+  for (size_t s = 0; s < nst; ++s) {
+    const uint32_t ns = nstates[s];
+    const uint32_t* io = in_off + in_pos;
+    if (io[0] != 0u || io[1] != 0u) return refuse(s, "state 0 has an incoming arc (in_off[0], in_off[1] must be 0)");
+    for (uint32_t d = 1; d <= ns; ++d)
+      if (io[d + 1] < io[d]) return refuse(s, "in_off is not monotone");
+    const size_t na = io[ns + 1];
+    if (arc_pos + na >= ((size_t)1 << 31)) return refuse(s, "too many arcs");
+    if (na && !arcs) return anx_fail(ANX_EINVAL, "NULL argument");
+    if (nsyms[s] && !syms) return anx_fail(ANX_EINVAL, "NULL argument");
+    uint32_t span = 0;
+    for (uint32_t d = 1; d <= ns; ++d) {
+      uint32_t prev_src = 0;
+      for (size_t k = io[d]; k < io[d + 1]; ++k) {
+        const uint32_t* a = arcs + (arc_pos + k) * 3;
+        if (!cost_ok(a[0])) return refuse(s, "an arc cost is negative, not finite or above 1e6");
+        if (a[1] >= d) return refuse(s, "an arc's source is not below its destination");
+        if (a[1] < prev_src) return refuse(s, "the sources of a state's arcs decrease");
+        if (a[2] != 0xFFFFFFFFu && a[2] >= nsyms[s]) return refuse(s, "an arc's symbol is beyond the stretch's symbols");
+        prev_src = a[1];
+        span = std::max(span, d - a[1]);
+      }
+    }
+    for (size_t k = 0; k < nsyms[s]; ++k) {
+      const uint32_t* y = syms + (sym_pos + k) * 2;
+      if (y[0] >= nvocab) return refuse(s, "a symbol's vocab_id is beyond the vocabulary");
+      if (y[1] >= ns - 1u) return refuse(s, "a symbol's boundary is not below nstates - 1");
+    }
+    const uint32_t* bo = btok_off + boff_pos;
+    if (bo[0] != 0u) return refuse(s, "btok_off does not start at 0");
+    for (uint32_t b = 1; b < ns; ++b)
+      if (bo[b] < bo[b - 1]) return refuse(s, "btok_off is not monotone");
+    const size_t nbt = bo[ns - 1];
+    if (btok_pos + nbt >= ((size_t)1 << 31)) return refuse(s, "too many boundary tokens");
+    if (nbt && !btok) return anx_fail(ANX_EINVAL, "NULL argument");
+    for (size_t k = 0; k < nbt; ++k)
+      if (btok[btok_pos + k] < -1 || (btok[btok_pos + k] >= 0 && (size_t)btok[btok_pos + k] >= nvocab)) return refuse(s, "a boundary token is neither -1 nor a vocabulary id");
+    uint32_t cb; memcpy(&cb, &best_cost_init[s], 4);
+    if (!cost_ok(cb)) return refuse(s, "best_cost_init is negative, not finite or above 1e6");
+    anx::LatStretch& S = st[s];
+    S.nstates = ns; S.in_off0 = (uint32_t)in_pos; S.arc0 = (uint32_t)arc_pos; S.sym0 = (uint32_t)sym_pos;
+    S.btok_off0 = (uint32_t)boff_pos; S.btok0 = (uint32_t)btok_pos; S.out0 = (uint32_t)out_pos;
+    S.best_cost_init = best_cost_init[s]; S.ring = span + 1u; S.node0 = 0;
+    in_pos += (size_t)ns + 2; arc_pos += na; sym_pos += nsyms[s]; boff_pos += ns; btok_pos += nbt; out_pos += ns;
+    if (s >= first && s < first + count) nodes += ((size_t)ns + 1) * K;
+    if (nodes > ((size_t)1 << 24)) return refuse(s, "more than 2^24 nodes in one call");
+  }
+  const anx::DeviceLexicon* dl = anx_replica_of(model, 0);
+  if (!dl) return anx_fail(ANX_ENODEVICE, "model is not resident on a device");
+  // the arrays in the product's own element types (same words)
+  static_assert(sizeof(anx::LatArc) == 12 && sizeof(anx::LatSym) == 8, "the door's arrays are the lattice's words");
+  std::vector<anx::LatArc> varcs(arc_pos);
+  if (arc_pos) memcpy(varcs.data(), arcs, arc_pos * sizeof(anx::LatArc));
+  std::vector<anx::LatSym> vsyms(sym_pos);
+  if (sym_pos) memcpy(vsyms.data(), syms, sym_pos * sizeof(anx::LatSym));
+  anx::LatView L;
+  L.st = st.data(); L.nst = nst;
+  L.in_off = in_off; L.nin = in_pos;
+  L.arcs = varcs.data(); L.narcs = arc_pos;
+  L.syms = vsyms.data(); L.nsyms = sym_pos;
+  L.btok_off = btok_off; L.nboff = boff_pos;
+  L.btok = btok; L.nbtok = btok_pos;
+  L.out_total = out_pos;
+  L.out_cover = out_cover;
+  anx::LatDebug D;
+  if (dbg) {
+    D.budget_nodes = dbg->budget_nodes;
+    D.launch_of = dbg->launch_of; D.width_of = dbg->width_of; D.lds_of = dbg->lds_of;
+    D.nodes = dbg->nodes; D.lm = dbg->lm; D.marks = dbg->marks; D.cnts = dbg->cnts; D.ctxval = dbg->ctxval;
+  }
+  std::string err;
+  const int rc = anx::lattice_decode_dbg(m, dl, L, first, count, *sp, out_n, out_syms, err, dbg ? &D : nullptr);
+  if (dbg) { dbg->lds_limit = D.lds_limit; dbg->n_launches = D.n_launches; }
+  return rc ? anx_fail(rc, err) : ANX_OK;
+}
+}  // extern "C"

@@ -920,6 +920,12 @@ int anx_debug_contextrule_match(const anx_model* model, size_t rule, size_t posi
   *out = anx::flat_elem_matches(fr.elems[fr.rules[rule].elem0 + position], fr.atoms.data(), (uint32_t)vocab_id, lexindex) ? 1 : 0;
   return ANX_OK;
 }
+// test hook: the host build of the library's logarithm
+int anx_debug_portable_log(const double* x, size_t n, double* out) {
+  if ((!x || !out) && n) return anx_fail(ANX_EINVAL, "NULL argument");
+  for (size_t i = 0; i < n; ++i) out[i] = anx::portable_log(x[i]);
+  return ANX_OK;
+}
 int anx_find_all_matches_batch(const anx_model* model, const char* const* texts, size_t n, const anx_search_params* sp,
                                anx_match** out_matches, size_t** out_offsets, anx_result** out_rows, size_t* out_n_rows,
                                anx_match_tag** out_tags) {

@@ -1249,6 +1249,85 @@ class VariantModel:
         L.check(L.lib().anx_debug_search_lattice_stats(out))
         return {"device": out[0], "host": out[1], "device_rules": out[2], "onepass_parts": out[3]}
 
+    @staticmethod
+    def portable_log(x):
+        """Test hook (anx_debug_portable_log): the host build of the library's logarithm over a float64 array."""
+        import numpy as np
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.empty_like(x)
+        L.check(L.lib().anx_debug_portable_log(x.ctypes.data, x.size, out.ctypes.data))
+        return out
+
+    def debug_lattice_decode(self, params: SearchParameters, lattices: Sequence[dict], first: int = 0, count: Optional[int] = None,
+                             budget_nodes: int = 0, pools: bool = True) -> dict:
+        """Test hook (anx_debug_lattice_decode): the device lattice decoder alone on the caller's lattices, through the product's
+        lattice_decode.  A lattice is a dict of nstates, in_off [nstates + 2], arcs [(cost, src, sym)] (sym 0xFFFFFFFF = epsilon),
+        syms [(vocab_id, boundary)], btok_off [nstates], btok, best_cost_init.  Returns out_n / out_syms / out_cover (per lattice
+        of the view; out_cover stays the fill without rules) and, with pools, the device pools of the sub-range's stretches over a 0xFF
+        fill: per stretch cnts [states], nodes [states, K, 3], lm [states, K, 3], marks [states, MK], ctxval [K], launch, width,
+        lds; plus lds_limit and n_launches.  A refusal raises AnxError before anything is launched."""
+        import numpy as np
+        n = len(lattices)
+        count = n - first if count is None else count
+        K = max(1, int(params.max_seq))
+        ns = np.array([int(l["nstates"]) for l in lattices], dtype=np.uint32)
+        for l in lattices:  # the lengths the C side cannot see
+            if len(l["in_off"]) != int(l["nstates"]) + 2 or len(l["btok_off"]) != max(int(l["nstates"]), 1):
+                raise ValueError("in_off needs nstates + 2 entries and btok_off nstates")
+            if int(l["in_off"][-1]) != len(l["arcs"]) or int(l["btok_off"][-1]) != len(l["btok"]):
+                raise ValueError("the last offset is not the length of its array")
+        cat = lambda key, dt: np.ascontiguousarray(np.concatenate([np.asarray(l[key], dtype=dt).reshape(-1) for l in lattices] + [np.zeros(0, dt)]))
+        in_off, btok_off, btok = cat("in_off", np.uint32), cat("btok_off", np.uint32), cat("btok", np.int32)
+        arcs = np.zeros((sum(len(l["arcs"]) for l in lattices), 3), dtype=np.uint32)
+        syms = np.zeros((sum(len(l["syms"]) for l in lattices), 2), dtype=np.uint32)
+        ai = si = 0
+        for l in lattices:
+            if len(l["arcs"]):
+                a = l["arcs"]
+                arcs[ai:ai + len(a), 0] = np.array([x[0] for x in a], dtype=np.float32).view(np.uint32)
+                arcs[ai:ai + len(a), 1] = [x[1] for x in a]
+                arcs[ai:ai + len(a), 2] = [x[2] for x in a]
+                ai += len(a)
+            if len(l["syms"]):
+                syms[si:si + len(l["syms"])] = np.asarray(l["syms"], dtype=np.uint32).reshape(-1, 2)
+                si += len(l["syms"])
+        nsyms = np.array([len(l["syms"]) for l in lattices], dtype=np.uint32)
+        bci = np.array([l["best_cost_init"] for l in lattices], dtype=np.float32)
+        out_total = int(ns.sum())
+        out_n = np.zeros(n, dtype=np.uint32)
+        out_syms = np.zeros(max(out_total, 1), dtype=np.uint32)
+        out_cover = np.zeros(max(out_total, 1), dtype=np.uint32)  # (stays the fill for a model without rules)
+        dbg = L.LatticeDebug()
+        dbg.budget_nodes = int(budget_nodes)
+        sub = ns[first:first + count].astype(np.int64) + 1 if 0 <= first <= n and 0 <= count <= n - first else np.zeros(0, np.int64)
+        states = int(sub.sum())
+        MK = (K + 3) & ~3
+        arrs = {}
+        if pools and states * K <= 1 << 24:
+            arrs = dict(launch_of=np.full(max(len(sub), 1), 0xFFFFFFFF, np.uint32), width_of=np.full(max(len(sub), 1), 0xFFFFFFFF, np.uint32),
+                        lds_of=np.full(max(len(sub), 1), 0xFFFFFFFF, np.uint32), nodes=np.full((max(states, 1), K, 3), 0xFFFFFFFF, np.uint32),
+                        lm=np.full((max(states, 1), K, 3), 0xFFFFFFFF, np.uint32), marks=np.full((max(states, 1), MK), 0xFF, np.uint8),
+                        cnts=np.full(max(states, 1), 0xFFFF, np.uint16), ctxval=np.full((max(len(sub), 1), K), 0xFFFFFFFFFFFFFFFF, np.uint64))
+            for k, v in arrs.items():
+                setattr(dbg, k, v.ctypes.data)
+        cs = params._c_search()
+        L.check(L.lib().anx_debug_lattice_decode(self.h, C.byref(cs), n, ns.ctypes.data, in_off.ctypes.data, arcs.ctypes.data, nsyms.ctypes.data,
+                                                 syms.ctypes.data, btok_off.ctypes.data, btok.ctypes.data, bci.ctypes.data, first, count,
+                                                 out_n.ctypes.data, out_syms.ctypes.data, out_cover.ctypes.data,
+                                                 C.byref(dbg)))
+        o0 = np.concatenate([[0], np.cumsum(ns.astype(np.int64))])
+        res = {"out_n": out_n, "out_syms": [out_syms[o0[i]:o0[i + 1]] for i in range(n)],
+               "out_cover": [out_cover[o0[i]:o0[i + 1]] for i in range(n)],
+               "lds_limit": int(dbg.lds_limit), "n_launches": int(dbg.n_launches), "stretches": []}
+        if arrs:
+            s0 = np.concatenate([[0], np.cumsum(sub)])
+            for j in range(len(sub)):
+                a, b = int(s0[j]), int(s0[j + 1])
+                res["stretches"].append(dict(cnts=arrs["cnts"][a:b], nodes=arrs["nodes"][a:b], lm=arrs["lm"][a:b], marks=arrs["marks"][a:b],
+                                             ctxval=arrs["ctxval"][j], launch=int(arrs["launch_of"][j]), width=int(arrs["width_of"][j]),
+                                             lds=int(arrs["lds_of"][j])))
+        return res
+
     def contextrule_element_matches(self, rule: int, position: int, vocab_id: int, lexindex: int, flat: bool = False) -> bool:
         """Test hook (anx_debug_contextrule_match): element `position` of context rule `rule` on (vocab_id, lexindex), evaluated as
         the parsed pattern (flat=False) or as the flattened element the device decoder reads (flat=True)."""

@@ -46,7 +46,8 @@ extern "C" {
  *    anx_mine_confusables / _packed, anx_mine_result_free, anx_default_mine_params, anx_format_confusable_list, the structs
  *    anx_mine_params / anx_mine_site / anx_mine_result and the hooks anx_debug_mine_stats / anx_debug_mine_chunk: confusable patterns
  *    mined from string pairs (additive, nothing else changed); anx_evaluate_sweep / _packed, the struct anx_gold_summary and the hooks
- *    anx_debug_evaluate_sweep_chunk / anx_debug_sweep_stats: several parameter sets over the same gold pairs (additive). */
+ *    anx_debug_evaluate_sweep_chunk / anx_debug_sweep_stats: several parameter sets over the same gold pairs (additive); the test hooks
+ *    anx_debug_lattice_decode (with the struct anx_lattice_debug) and anx_debug_portable_log (additive). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -621,6 +622,45 @@ typedef struct anx_match_tag {
   uint8_t pad_;
 } anx_match_tag;
 void anx_default_search_params(anx_search_params *);
+/* Test hook: search mode's lattice decoder (k_lattice<32|64>, k_ctx_rules, k_lattice_lm and their driver) alone, on lattices the caller
+ * laid out, through the product's own lattice_decode / lattice_launch: launch order, pairing, pools and kernel instances are the run's.
+ * `model` (resident) gives the LM tables, the n-gram token lists, the lexicon masks and the flat context rules; `params` max_seq (K)
+ * and the three rerank weights.  The lattices, stretch after stretch: nstates[s] (without the virtual end state; >= 1); in_off = per
+ * stretch nstates + 2 offsets into ITS arcs (entry d = first incoming arc of state d, the virtual end state is state nstates, the last
+ * entry is the stretch's arc count); arcs = 3 words each (cost as float bits, source state, symbol | UINT32_MAX = epsilon), per
+ * destination in (source state, arc number) order; nsyms[s] and syms = 2 words each (vocab_id, boundary); btok_off = per stretch nstates
+ * offsets (nstates - 1 boundaries + 1) into ITS boundary tokens, btok = LM tokens (-1 = not in the vocabulary); best_cost_init[s].  The
+ * hook computes the ring (1 + the widest span, end arcs included) as the lattice builder does.  Only the stretches [first, first + count)
+ * are decoded (a replica's share).
+ * Everything is validated on the host BEFORE anything is launched, ANX_EINVAL otherwise: offsets monotone and in range, state 0 without
+ * an incoming arc, every arc's source below its destination and non-decreasing within a state, symbols below nsyms[s], boundary <
+ * nstates - 1, vocab_id below the vocabulary size, tokens -1 or a vocabulary id, every cost (and best_cost_init) finite, sign bit clear,
+ * at most 1e6 (the merge orders costs by bit pattern), nstates <= 65535 and the nodes of the call ((nstates + 1) * K per stretch) at
+ * most 2^24.  States nothing reaches, and an end state nothing reaches, are accepted.
+ * Outputs start as 0xFF bytes (also after a refusal): out_n[nst] (UINT32_MAX = handed back; the hook runs no host decoder), out_syms and
+ * out_cover (NULL only for a model without rules) with nstates[s] slots per stretch, all stretches of the view back to back.  `dbg` may
+ * be NULL; else budget_nodes (0 = the driver's own) cuts the launches and the arrays that are not NULL receive, per launch and before
+ * the pools are reused, the device pools over a 0xFF fill: stretch j of the sub-range owns the states [sum of nstates + 1 before it ..)
+ * of nodes (K nodes of 3 words (cost bits, parent, symbol) per state), lm (3 words (lp bits, n, prev) per node, LM only), marks ((K + 3
+ * & ~3) bytes per state, LM only), cnts (one per state), and ctxval[j * K ..] (rules only); launch_of / width_of / lds_of [count].
+ * tests/test_gpu_lattice_door.py compares all of it exactly with oracle/twin.py decode_lattice on the cases of tests/lattice_cases.py. */
+typedef struct anx_lattice_debug {
+  uint64_t budget_nodes;
+  uint32_t *launch_of, *width_of, *lds_of;
+  uint32_t *nodes, *lm;
+  uint8_t *marks;
+  uint16_t *cnts;
+  double *ctxval;
+  uint32_t lds_limit;   /* out: the device's dynamic LDS limit per block */
+  uint32_t n_launches;  /* out */
+} anx_lattice_debug;
+int anx_debug_lattice_decode(const anx_model *model, const anx_search_params *params, size_t nst, const uint32_t *nstates,
+                             const uint32_t *in_off, const uint32_t *arcs, const uint32_t *nsyms, const uint32_t *syms,
+                             const uint32_t *btok_off, const int32_t *btok, const float *best_cost_init, size_t first, size_t count,
+                             uint32_t *out_n, uint32_t *out_syms, uint32_t *out_cover, anx_lattice_debug *dbg);
+/* Test hook: out[i] = the host build of the library's own logarithm (portable_log.hpp) of x[i]: a reference of the rerank computes
+ * with the product's bits. */
+int anx_debug_portable_log(const double *x, size_t n, double *out);
 /* matches of text i are (*out_matches)[(*out_offsets)[i] .. (*out_offsets)[i+1]); out_tags may be NULL (tags are then
  * not reported); release with anx_matches_free */
 int anx_find_all_matches_batch(const anx_model *, const char *const *utf8_texts, size_t n, const anx_search_params *,

@@ -836,6 +836,7 @@ import numpy as _np
 
 TRANSITION_SMOOTHING_LOGPROB = _np.float32(-13.815510557964274)  # src/search.rs:4
 BOS, EOS, UNK = 0, 1, 2  # src/vocab.rs:145-147
+LAT_EPS = 0xFFFFFFFF  # lattice arrays: no symbol (an epsilon arc) / no parent (the start node)
 
 
 @dataclass
@@ -1148,10 +1149,17 @@ class SearchModel(VariantModel):
     def test_context_rules(self, sequence: List[Tuple[int, int]]):
         """src/lib.rs:2501-2578 with ContextRule::matches (src/search.rs:472-524): (context score, per position
         [(score, tag | None, seqnr)])."""
+        score, results, _cover = self.test_context_rules_cover(sequence)
+        return score, results
+
+    def test_context_rules_cover(self, sequence: List[Tuple[int, int]]):
+        """test_context_rules plus, per position, what covers it: rule index << 8 | position in the rule, None = uncovered
+        (a position a rule matched but none of its tag offsets reaches stays uncovered: results[] is empty there)."""
         results: List[list] = [[] for _ in sequence]
+        cover: List[Optional[int]] = [None for _ in sequence]
         found = False
         for begin in range(len(sequence)):
-            for rule in self.context_rules:
+            for ri, rule in enumerate(self.context_rules):
                 n = len(rule.pattern)
                 if begin + n > len(sequence):
                     continue
@@ -1164,12 +1172,14 @@ class SearchModel(VariantModel):
                     else:
                         results[begin + c] = [(rule.score, t, c - b) for t, (b, l) in zip(rule.tag, rule.tagoffset)
                                               if b <= c < b + l]
+                    if results[begin + c]:
+                        cover[begin + c] = ri << 8 | c
         if not found:
-            return 1.0, results
+            return 1.0, results, cover
         total = _np.float32(0.0)
         for r in results:
             total = _np.float32(total + _np.float32(r[0][0] if r else 1.0))
-        return float(total) / float(len(sequence)), results
+        return float(total) / float(len(sequence)), results, cover
 
     # -- LM ------------------------------------------------------------------------------------------------
     def lm_score_tokens(self, tokens: List[Optional[int]]) -> Tuple[float, float]:
@@ -1217,17 +1227,58 @@ class SearchModel(VariantModel):
         return self.lm_score_tokens(tokens)
 
     # -- lattice -------------------------------------------------------------------------------------------
-    def most_likely_sequence(self, matches: List[Match], boundaries: List[Match], begin_offset: int,
-                             end_offset: int, params: "SearchParams") -> List[Match]:
-        """src/lib.rs:2088-2495 without context rules.  The reference decodes with rustfst
-        shortest_path(nshortest = max_seq); here: exact k-best over the boundary DAG.  Order among equal-cost
-        paths is rustfst-internal in the reference and NOT pinned (documented)."""
+    def lm_term(self, a: Optional[int], b: Optional[int], logf=None):
+        """One bigram term of lm_score_tokens (src/lib.rs:2632-2674), f32.  logf: the f32 logarithm (default numpy's)."""
+        if a is None or b is None:
+            return TRANSITION_SMOOTHING_LOGPROB
+        joint = self.ngrams.get((a, b))
+        if joint is None:
+            return TRANSITION_SMOOTHING_LOGPROB
+        priorcount = self.ngrams.get((a,), 1)
+        logf = logf or _np.log
+        if priorcount < joint:
+            return _np.float32(logf(_np.float32(joint)))
+        return _np.float32(logf(_np.float32(joint) / _np.float32(priorcount)))
+
+    def symbol_tokens(self, vocab_id: int, btoks: Sequence[Optional[int]]) -> List[Optional[int]]:
+        """The LM tokens of an output symbol (src/lib.rs:2580-2629): its n-gram parts (one out-of-vocabulary token for vocab id
+        0, nothing for an entry of more than 5 parts), then the tokens of the boundary text behind it."""
+        toks: List[Optional[int]] = []
+        if vocab_id == 0:
+            toks.append(None)
+        elif vocab_id < len(self.decoder):
+            ng = self._into_ngram(vocab_id)
+            if ng is not None:
+                toks.extend(ng)
+        toks.extend(btoks)
+        return toks
+
+    def boundary_tokens(self, b: Match) -> List[Optional[int]]:
+        """The LM tokens of a boundary's text (src/lib.rs:2606-2629)."""
+        bt = rust_trim(b.text)
+        if bt == "":
+            return []
+        bid = self.encoder.get(bt)
+        if bid is None:
+            return [None]
+        ng = self._into_ngram(bid)
+        return list(ng) if ng is not None else []
+
+    def build_lattice_view(self, matches: List[Match], boundaries: List[Match], end_offset: int, params: "SearchParams"):
+        """The lattice of a stretch as plain arrays, in the layout the device decoder reads (one state per boundary + the start,
+        a virtual end state behind the final states): nstates (without the end state), in_off [nstates + 2] (entry d = first
+        incoming arc of state d), arcs [(f32 cost, source state, symbol | EPS)] per destination in (source state, arc number)
+        order, syms [(vocab_id, boundary)], refs [(match index, variant index | None)] beside syms, btok_off [nstates] / btok
+        (LM tokens of the boundary texts, -1 = not in the vocabulary), best_cost_init, ring (1 + the widest span).
+        None when the stretch needs no decoding (no symbol; src/lib.rs:2277-2290)."""
         f32 = _np.float32
-        nstates = len(boundaries) + 1  # state 0 = start, state i+1 = boundary i
+        nb = len(boundaries)
+        nstates = nb + 1  # state 0 = start, state i+1 = boundary i
         finals = [i + 1 for i, b in enumerate(boundaries) if b.begin == end_offset or b.end == end_offset]
         assert finals, "no final state found"
-        arcs: List[List[tuple]] = [[] for _ in range(nstates)]  # per source state: (cost, dst, symbol or None)
-        symbols = [None]  # output symbols: (vocab_id, match_index, variant_index, boundary_index)
+        out: List[List[tuple]] = [[] for _ in range(nstates)]  # per source state: (cost, dst, symbol)
+        syms: List[tuple] = []
+        refs: List[tuple] = []
         for mi, m in enumerate(matches):
             prevb = nextb = None
             for i, b in enumerate(boundaries):
@@ -1241,72 +1292,173 @@ class SearchModel(VariantModel):
             dst = nextb + 1
             if m.variants:
                 for vi, vr in enumerate(m.variants):
-                    symbols.append((vr.vocab_id, mi, vi, nextb))
                     cost = f32(f32(n) + f32(f32(1.0) - f32(vr.score(params.freq_weight))))
-                    arcs[src].append((cost, dst, len(symbols) - 1))
+                    out[src].append((cost, dst, len(syms)))
+                    syms.append((vr.vocab_id, nextb))
+                    refs.append((mi, vi))
             elif n == 1:
-                symbols.append((0, mi, None, nextb))
-                arcs[src].append((f32(f32(n) + f32(1.0)), dst, len(symbols) - 1))
-        for i in range(len(boundaries)):  # failsafe epsilon transitions
-            arcs[i].append((f32(100.0), i + 1, None))
-        if len(symbols) == 1:
-            return matches
-        # k-best paths into every state (states are topologically ordered by index)
-        K = params.max_seq
-        best: List[List[tuple]] = [[] for _ in range(nstates)]  # (cost, symbol list)
-        best[0] = [(f32(0.0), ())]
+                out[src].append((f32(f32(n) + f32(1.0)), dst, len(syms)))
+                syms.append((0, nextb))
+                refs.append((mi, None))
+        if not syms:
+            return None
+        for i in range(nb):  # failsafe epsilon transitions
+            out[i].append((f32(100.0), i + 1, LAT_EPS))
+        incoming: List[List[tuple]] = [[] for _ in range(nstates + 1)]
+        span = 1
         for s in range(nstates):
-            if not best[s]:
-                continue
-            best[s].sort(key=lambda t: float(t[0]))
-            best[s] = best[s][:K]
-            for cost, dst, sym in arcs[s]:
-                for c0, syms in best[s]:
-                    best[dst].append((f32(c0 + cost), syms + ((sym,) if sym is not None else ())))
-        paths: List[tuple] = []
+            for cost, dst, sym in out[s]:
+                incoming[dst].append((cost, s, sym))
+                span = max(span, dst - s)
         for fstate in finals:
-            paths.extend(best[fstate])
-        paths.sort(key=lambda t: float(t[0]))
-        paths = paths[:K]
-        # rerank (src/lib.rs:2318-2425)
-        seqs = []
-        best_ppl, best_cost, best_ctx = 999999.0, f32((len(boundaries) - 1) * 2.0), 0.0
+            incoming[nstates].append((f32(0.0), fstate, LAT_EPS))
+            span = max(span, nstates - fstate)
+        in_off = [0]
+        arcs: List[tuple] = []
+        for d in range(nstates + 1):
+            arcs.extend(incoming[d])
+            in_off.append(len(arcs))
+        btok_off, btok = [], []
+        for b in boundaries:
+            btok_off.append(len(btok))
+            if self.have_lm:
+                btok.extend(-1 if t is None else t for t in self.boundary_tokens(b))
+        btok_off.append(len(btok))
+        return dict(nstates=nstates, in_off=in_off, arcs=arcs, syms=syms, refs=refs, btok_off=btok_off, btok=btok,
+                    best_cost_init=f32((nb - 1) * 2.0), ring=span + 1)
+
+    def decode_lattice(self, view: dict, K: int, params: "SearchParams", ln=None, logf=None) -> dict:
+        """The decoder over the arrays of build_lattice_view, restated from the device kernels' contract (src/lib.rs:2088-2495
+        for what they compute): the K best paths into every state under (f32 cost, source state, arc number, rank at the
+        source) with cost = f32(source node's cost + arc cost); the LM sums of the nodes on final paths token by token in f32;
+        test_context_rules per final path; the rerank with first-maximum and NaN behaviour.  ln: the f64 logarithm of the
+        rerank (default _ln), logf: the f32 logarithm of the bigram terms (default numpy's).
+        Returns nodes[state] = [(cost, parent, symbol)] (parent = source state << 16 | rank, LAT_EPS for the start node),
+        marked = {(state, rank)} of the nodes on final paths, lm[(state, rank)] = (f32 sum, tokens, last token | None),
+        ctxval[path] = ln(ctx / best ctx) (None without rules), scores[path], chosen (path index; None: the end state has no
+        path), out_syms (local symbol ids of the chosen path), out_cover (rule << 8 | position, None = uncovered) and covers (the
+        same for every final path, with rules)."""
+        f32 = _np.float32
+        ln = ln or _ln
+        K = max(1, int(K))
+        nstates, in_off, arcs, syms = view["nstates"], view["in_off"], view["arcs"], view["syms"]
+        end = nstates
+        nodes: List[List[tuple]] = [[] for _ in range(nstates + 1)]
+        nodes[0] = [(f32(0.0), LAT_EPS, LAT_EPS)]
+        for d in range(1, nstates + 1):
+            cands = []
+            for ai in range(in_off[d], in_off[d + 1]):
+                cost, src, sym = arcs[ai]
+                cost = f32(cost)
+                for r, nd in enumerate(nodes[src]):
+                    cands.append((float(f32(nd[0] + cost)), ai, r, src, sym))
+            cands.sort(key=lambda t: t[:3])
+            nodes[d] = [(f32(c), src << 16 | r, sym) for c, _ai, r, src, sym in cands[:K]]
+        npaths = len(nodes[end])
+        res = dict(nodes=nodes, marked=set(), lm={}, ctxval=None, scores=[], chosen=None, out_syms=[], out_cover=[], covers=[])
+        if npaths == 0:
+            return res
+
+        def walk(i):  # the local symbols of final path i, in path order
+            st, r, out = end, i, []
+            while True:
+                _c, par, sym = nodes[st][r]
+                if par == LAT_EPS:
+                    break
+                if sym != LAT_EPS:
+                    out.append(sym)
+                st, r = par >> 16, par & 0xFFFF
+            return out[::-1]
         use_lm = self.have_lm and params.lm_weight > 0.0
-        for cost, syms in paths:
-            osyms = [symbols[s] for s in syms]
-            logprob, ppl = (0.0, 0.0)
-            ctx, tags = 1.0, []
+        marked = res["marked"]
+        if use_lm:
+            for i in range(npaths):
+                st, r = end, i
+                while (st, r) not in marked:
+                    marked.add((st, r))
+                    par = nodes[st][r][1]
+                    if par == LAT_EPS:
+                        break
+                    st, r = par >> 16, par & 0xFFFF
+            lm = res["lm"]
+            btok_off, btok = view["btok_off"], view["btok"]
+            for st, r in sorted(marked):
+                _c, par, sym = nodes[st][r]
+                if par == LAT_EPS:
+                    lm[(st, r)] = (f32(0.0), 0, BOS)
+                    continue
+                lp, n, prev = lm[(par >> 16, par & 0xFFFF)]
+                if sym != LAT_EPS:
+                    vid, bidx = syms[sym]
+                    for t in self.symbol_tokens(vid, [None if t < 0 else t for t in btok[btok_off[bidx]:btok_off[bidx + 1]]]):
+                        lp = f32(lp + self.lm_term(prev, t, logf))
+                        n += 1
+                        prev = t
+                lm[(st, r)] = (lp, n, prev)
+        best_ppl, best_cost, best_ctx = 999999.0, f32(view["best_cost_init"]), 0.0
+        rules = bool(self.context_rules)
+        ppls, ctxs, covers = [], [], []
+        for i in range(npaths):
+            cost = nodes[end][i][0]
+            ppl, ctx, cover = 0.0, 1.0, None
             if use_lm:
-                logprob, ppl = self.lm_score(osyms, boundaries)
-                best_ppl = min(best_ppl, ppl)
-            if self.context_rules:  # src/lib.rs:2345-2363
-                ctx, results = self.test_context_rules(
-                    [(vid, self.decoder[vid].lexindex if vid != 0 else 0) for vid, _mi, _vi, _b in osyms])
-                tags = [[(t, nr) for _sc, t, nr in r if t is not None] for r in results]
+                lp, n, prev = res["lm"][(end, i)]
+                logprob = f32(lp + self.lm_term(prev, EOS, logf))
+                ppl = -1.0 / float(n + 1) * float(logprob)
+                if ppl < best_ppl:
+                    best_ppl = ppl
+            if rules:  # src/lib.rs:2345-2363
+                ctx, _results, cover = self.test_context_rules_cover(
+                    [(syms[s][0], self.decoder[syms[s][0]].lexindex if syms[s][0] != 0 else 0) for s in walk(i)])
+                if ctx > best_ctx:
+                    best_ctx = ctx
             if cost < best_cost:
                 best_cost = cost
-            if ctx > best_ctx:
-                best_ctx = ctx
-            seqs.append((cost, osyms, ppl, ctx, tags))
-        best_score, best_seq, best_tags = -99999999.0, None, []
+            ppls.append(ppl)
+            ctxs.append(ctx)
+            covers.append(cover)
+        if rules:
+            res["ctxval"] = [ln(_div(c, best_ctx)) for c in ctxs]
         lw, vw, cw = float(f32(params.lm_weight)), float(f32(params.variantmodel_weight)), float(f32(params.contextrules_weight))
-        shortcut = (not self.have_lm or lw == 0.0) and (not self.context_rules or cw == 0.0)
-        for cost, osyms, ppl, ctx, tags in seqs:
-            norm_lm = _ln(_div(best_ppl, ppl)) if use_lm else 0.0
+        shortcut = not use_lm and (not rules or cw == 0.0)
+        best_score, chosen = None, None
+        for i in range(npaths):
+            norm_lm = ln(_div(best_ppl, ppls[i])) if use_lm else 0.0
             # a stretch with ONE boundary leaves best_cost at 0.0 (src/lib.rs:2320): ln(0) = -inf for every path, and
-            # the first path the FST yields wins (src/lib.rs:2419); here that is the cheapest one
-            norm_var = _ln(_div(float(best_cost), float(cost)))
-            norm_ctx = _ln(_div(ctx, best_ctx))
+            # the first path wins (src/lib.rs:2419)
+            norm_var = ln(_div(float(best_cost), float(nodes[end][i][0])))
+            norm_ctx = res["ctxval"][i] if rules else ln(1.0)
             if shortcut:
                 score = norm_var
             else:
                 with _np.errstate(all="ignore"):
                     score = float((_np.float64(lw) * norm_lm + _np.float64(vw) * norm_var + _np.float64(cw) * norm_ctx)
-                                  / _np.float64(lw + vw + cw))
-            if score > best_score or best_seq is None:
-                best_score, best_seq, best_tags = score, osyms, tags
+                                  / (_np.float64(lw) + _np.float64(vw) + _np.float64(cw)))
+            res["scores"].append(score)
+            if chosen is None or score > best_score:  # a NaN never wins, and a NaN on path 0 stands
+                best_score, chosen = score, i
+        res["chosen"] = chosen
+        res["out_syms"] = walk(chosen)
+        res["out_cover"] = covers[chosen] if rules else [None] * len(res["out_syms"])
+        res["covers"] = covers if rules else []
+        return res
+
+    def most_likely_sequence(self, matches: List[Match], boundaries: List[Match], begin_offset: int,
+                             end_offset: int, params: "SearchParams") -> List[Match]:
+        """src/lib.rs:2088-2495.  The reference decodes with rustfst shortest_path(nshortest = max_seq); here: the
+        lattice arrays of build_lattice_view, decoded by decode_lattice (exact k-best over the boundary DAG).  Order among
+        equal-cost paths is rustfst-internal in the reference and NOT pinned (documented)."""
+        view = self.build_lattice_view(matches, boundaries, end_offset, params)
+        if view is None:
+            return matches
+        res = self.decode_lattice(view, params.max_seq, params)
+        osyms = [(view["syms"][s][0],) + view["refs"][s] for s in res["out_syms"]]
+        best_tags = []
+        if self.context_rules:
+            _ctx, results = self.test_context_rules([(vid, self.decoder[vid].lexindex if vid != 0 else 0) for vid, _mi, _vi in osyms])
+            best_tags = [[(t, nr) for _sc, t, nr in r if t is not None] for r in results]
         out = []
-        for i, (vocab_id, mi, vi, _b) in enumerate(best_seq):
+        for i, (vocab_id, mi, vi) in enumerate(osyms):
             m = matches[mi]
             r = Match(m.text, m.begin, m.end, m.variants, vi, m.n)
             if best_tags:
