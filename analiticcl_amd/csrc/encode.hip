@@ -7,7 +7,7 @@
 // src/lib.rs:1164-1173) the exact anagram class of every query.  The host only hands over the input bytes and their offsets.
 //   k_enc_strings : one lane per input string: greedy first-match alphabet walk (class order, member order; multi-character
 //                   members consume their characters), codes, count vector, planes, signature, clamps, first-char case
-//   sort          : one packed key (scan kernel, length, signature, kind) -- rocPRIM device radix sort (plumbing)
+//   sort          : one packed key (scan kernel, length, signature, kind, hash of the planes) -- rocPRIM device radix sort (plumbing)
 //   k_enc_gather  : sorted position -> query records, rows, planes, count vectors, exact class
 //   k_tile_*      : segment heads -> tiles of <= SCAN_TQ queries -> LPT order (one more radix sort)
 // The threaded host encoder in engine.hip (ANX_ENCODE=host) produces the same arrays and is kept as the A/B reference.
@@ -23,6 +23,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "engine_internal.h"
+#include "scan_twins.hpp"
 
 namespace anx {
 
@@ -52,7 +53,7 @@ struct EncArgs {
   unsigned long long* sig;  // [n]
   uint32_t* kind;           // [n]
   uint32_t* cv;             // [n][NP]; zero-initialised when !bits_ok; with planes only rows of kind 0 are written
-  unsigned long long* key;  // [n] sort key: (scan kernel, length) << (3 + 5 ngroups) | signature, 5 bits per group, << 3 | kind; the bit above = not
+  unsigned long long* key;  // [n] sort key: (scan kernel, length) << (3 + 5 ngroups) | signature, 5 bits per group, << 3 | kind, << 10 | twin_hash of the planes (scan_twins.hpp); the bit above = not
                             // encodable (sorts last).  The order has to bring equal (scan kernel, length, signature) together, kinds
                             // ascending, and keeps neighbouring signatures together (tiles of equal cost run side by side: their
                             // table probes share cache lines -- a hashed signature cost 0.1 ms per step in the scan).  Group counts
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256) void k_enc_strings(EncArgs a) {
       }
     }
     uint32_t meta = 0, kind = 0;
-    unsigned long long key = 1ull << (12 + 5 * a.ngroups);
+    unsigned long long key = 1ull << (12 + 5 * a.ngroups + kTwinHashBits);
     if (!too_long && n > 0) {
       int fl;
       {  // char::is_lowercase on the first character of the ORIGINAL string (src/lib.rs:1367-1377)
@@ -233,7 +234,9 @@ __global__ __launch_bounds__(256) void k_enc_strings(EncArgs a) {
       kind = (a.bits_ok && !over) ? (p4 ? 4u : p3 ? 3u : p2 ? 2u : 1u) : 0u;
       unsigned long long sc = 0;  // group ngroups - 1 is the most significant byte in use: numeric order of the signature
       for (int g = a.ngroups - 1; g >= 0; --g) sc = sc << 5 | min((uint32_t)(sig >> (8 * g)) & 0xFFu, 31u);
-      key = ((unsigned long long)((kind ? 256u : 0u) + n) << (5 * a.ngroups) | sc) << 3 | kind;
+      // equal planes next to each other inside a (scan kernel, length, signature, kind) run: the scan tests such a run once (scan_twins.hpp)
+      const uint32_t th = kind ? twin_hash(p1, p2, p3, p4) : 0u;
+      key = (((unsigned long long)((kind ? 256u : 0u) + n) << (5 * a.ngroups) | sc) << 3 | kind) << kTwinHashBits | th;
       len = n; d = (uint32_t)dd; ok = 1;
     }
     if (ANX_DBG(a.dbg) & 8) return;
@@ -810,7 +813,7 @@ int batch_encode_device(const HostModel& m, const DeviceLexicon* dl, Batch* b, c
   unsigned long long* k64_b = nullptr;
   if ((rc = sc.get(&perm_a, n, err)) || (rc = sc.get(&perm_b, n, err)) || (rc = sc.get(&k64_b, n, err))) return rc;
   hipLaunchKernelGGL(k_iota, gn, dim3(256), 0, st, perm_a, n32);
-  if ((rc = sort_pairs(d_key, k64_b, perm_a, perm_b, n, 0, 13 + 5 * ea.ngroups, sc, st, err))) return rc;  // 9 + 5 ngroups + 3 bits, and "not encodable"
+  if ((rc = sort_pairs(d_key, k64_b, perm_a, perm_b, n, 0, 13 + 5 * ea.ngroups + kTwinHashBits, sc, st, err))) return rc;  // 9 + 5 ngroups + 3 bits, the twin hash below them, and "not encodable"
   const uint32_t* perm = perm_b;
   uint32_t h_ctr[8];
   HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr, sizeof h_ctr, hipMemcpyDeviceToHost, st));

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "engine_internal.h"
+#include "scan_twins.hpp"
 
 namespace anx {
 
@@ -658,6 +659,7 @@ static int encode_host(const HostModel& m, const DeviceLexicon* dl, Batch* b, co
     uint32_t kind;   // 0 = count-vector (SAD) scan, 1..NBITPLANES = planes the bit-plane scan compares for this query
     uint32_t off;    // offset of the norm string in its thread's arena
     uint16_t thread;
+    uint16_t twin;   // twin_hash of the planes (scan_twins.hpp; kind 0: 0): the last sort key, as in the device encoder
     uint64_t sig;    // per-group symbol counts (LexiconImage::sym_group)
   };
   HostBuf<Enc> enc(n);
@@ -673,7 +675,7 @@ static int encode_host(const HostModel& m, const DeviceLexicon* dl, Batch* b, co
     int16_t codes[kMaxSymbols];
     for (size_t i = lo; i < hi; ++i) {
       Enc& e = enc[i];
-      e.meta = 0; e.key = 0; e.kind = 0; e.off = 0; e.thread = (uint16_t)tid; e.sig = 0;
+      e.meta = 0; e.key = 0; e.kind = 0; e.off = 0; e.thread = (uint16_t)tid; e.twin = 0; e.sig = 0;
       memset(&cv_all[i * cvbytes], 0, cvbytes);
       const int len = utf8[i] ? m.alphabet.scan_into(utf8[i], strlen(utf8[i]), codes, kMaxSymbols) : -1;
       if (len < 0) { b->status[i] = ANX_ELIMIT; continue; }
@@ -692,6 +694,13 @@ static int encode_host(const HostModel& m, const DeviceLexicon* dl, Batch* b, co
                (first_char_is_lowercase(utf8[i]) ? 1u << 24 : 0u);
       const uint32_t kind = (bits_ok && maxcount <= (uint32_t)NBITPLANES) ? maxcount : 0;
       e.kind = kind;
+      if (kind) {  // the thermometer planes fill_range builds below, here only for their hash
+        uint32_t pl[NBITPLANES] = {};
+        for (size_t sym = 0; sym < cvbytes && sym < 32; ++sym)
+          for (uint32_t tp = 0; tp < cv[sym] && tp < (uint32_t)NBITPLANES; ++tp) pl[tp] |= 1u << sym;
+        static_assert(NBITPLANES == 4, "twin_hash takes four planes");
+        e.twin = (uint16_t)twin_hash(pl[0], pl[1], pl[2], pl[3]);
+      }
       e.key = (kind ? 256u : 0u) + (uint32_t)len;
       e.sig = signature_of(cv, cvbytes, m.lex.sym_group);
     }
@@ -766,13 +775,15 @@ static int encode_host(const HostModel& m, const DeviceLexicon* dl, Batch* b, co
       if (enc[i].meta) b->order[cursor[enc[i].key]++] = (uint32_t)i;
   }, n);
   lap("counting sort");
-  {  // inside a (scan kernel, length) bucket: by (signature, kind), stable; buckets are independent -> threads take them
-     // round-robin.  LSD radix sort (8-bit digits, digits on which the whole bucket agrees are skipped; the kind is the
-     // least significant digit) over (signature, kind, input index) records: contiguous keys instead of a comparison sort
+  {  // inside a (scan kernel, length) bucket: by (signature, kind, hash of the planes), stable -- the order of the device encoder's
+     // key; equal planes end up next to each other (scan_twins.hpp); buckets are independent -> threads take them
+     // round-robin.  LSD radix sort (8-bit digits, digits on which the whole bucket agrees are skipped; kind and hash are the
+     // least significant digit) over (signature, kind and hash, input index) records: contiguous keys instead of a comparison sort
      // through enc[] (23 -> 8 ms per million queries)
-    struct SigIdx { uint64_t sig; uint32_t idx; uint32_t kind; };
+    struct SigIdx { uint64_t sig; uint32_t idx; uint32_t kind; };  // kind: kind << kTwinHashBits | hash
     auto sort_buckets = [&](unsigned tid) {
       std::vector<SigIdx> a, t2;
+      std::vector<size_t> kcnts;
       for (uint32_t kx = tid; kx < NKEYS; kx += nthreads) {
         const size_t b0 = kstart[kx], cnt = kstart[kx + 1] - b0;
         if (cnt < 2) continue;
@@ -782,7 +793,7 @@ static int encode_host(const HostModel& m, const DeviceLexicon* dl, Batch* b, co
         uint32_t kind_or = 0, kind_and = ~0u;
         for (size_t i = 0; i < cnt; ++i) {
           const uint32_t x = b->order[b0 + i];
-          a[i] = SigIdx{enc[x].sig, x, enc[x].kind};
+          a[i] = SigIdx{enc[x].sig, x, enc[x].kind << kTwinHashBits | enc[x].twin};
           all_or |= a[i].sig;
           all_and &= a[i].sig;
           kind_or |= a[i].kind;
@@ -790,11 +801,12 @@ static int encode_host(const HostModel& m, const DeviceLexicon* dl, Batch* b, co
         }
         const uint64_t varying = all_or ^ all_and;  // bits on which some keys differ
         SigIdx *src = a.data(), *dst = t2.data();
-        if (kind_or != kind_and) {  // least significant digit: the kind (0..NBITPLANES)
-          size_t cnts[NBITPLANES + 2] = {0};
-          for (size_t i = 0; i < cnt; ++i) cnts[src[i].kind + 1]++;
-          for (int v = 0; v <= NBITPLANES; ++v) cnts[v + 1] += cnts[v];
-          for (size_t i = 0; i < cnt; ++i) dst[cnts[src[i].kind]++] = src[i];
+        if (kind_or != kind_and) {  // least significant digit: the kind (0..NBITPLANES) above the hash of the planes
+          constexpr int NV = (NBITPLANES + 1) << kTwinHashBits;
+          kcnts.assign(NV + 1, 0);
+          for (size_t i = 0; i < cnt; ++i) kcnts[src[i].kind + 1]++;
+          for (int v = 0; v < NV; ++v) kcnts[v + 1] += kcnts[v];
+          for (size_t i = 0; i < cnt; ++i) dst[kcnts[src[i].kind]++] = src[i];
           std::swap(src, dst);
         }
         for (int byte = 0; byte < 8; ++byte) {

@@ -557,6 +557,7 @@ const SwitchDef kSwitches[] = {
     {"ANX_FS_SPLIT", [](Switches& s, const char* v) { s.fs_split = flag01(v, 1); }},
     {"ANX_FS_PLANES", [](Switches& s, const char* v) { s.fs_planes = flag01(v, 1); }},
     {"ANX_FS_B7", [](Switches& s, const char* v) { s.fs_b7 = flag01(v, 1); }},
+    {"ANX_SCAN_TWINS", [](Switches& s, const char* v) { s.scan_twins = flag01(v, 1); }},
     {"ANX_SCAN_FUSE", [](Switches& s, const char* v) { s.fuse_prefilter = flag01(v, 1); }},
     {"ANX_CAP_DIV", [](Switches& s, const char* v) { const long x = v ? atol(v) : 0; s.cap_div = x > 1 ? x : 1; }},
     {"ANX_MAX_BATCH", [](Switches& s, const char* v) { const long x = v ? atol(v) : 0; s.max_batch = x > 0 ? x : (4l << 20); }},

@@ -85,6 +85,7 @@ struct Switches {
   int fs_planes = 1;         // ANX_FS_PLANES=0: byte rows instead of symbol planes in k_filter_score (A/B; alphabets beyond 61 classes always take the rows)
   int fs_split = 1;          // ANX_FS_SPLIT=0: the 8-word prefilter of the wide pairs inline in k_filter_score (A/B; until round 6 what batches with long queries ran)
   int fs_b7 = 1;             // ANX_FS_B7=0: general zero test in the prefilter
+  int scan_twins = 1;        // ANX_SCAN_TWINS=0: the bit-plane scan tests every query of a tile itself, also those with the planes of their predecessor (scan_twins.hpp; A/B reference)
   int fuse_prefilter = 1;    // ANX_SCAN_FUSE=0: the scan's expansion does not apply the SWAR bound (k_filter_score's phase 1 does)
   long cap_div = 1;          // ANX_CAP_DIV=n: first-run capacity estimates divided by n (regrow-and-repeat path)
   long max_batch = 4l << 20; // ANX_MAX_BATCH: inputs per device batch of anx_find_variants_batch

@@ -16,7 +16,8 @@
 //   and, whenever 64*CPL classes are staged, compares them (lane = class, gathered planes in registers) with
 //   every query of the tile (query planes broadcast from LDS).  On eng.aspell k<=3 this leaves 4.6 k of the
 //   68 k class tests per query that the plain charcount window needs.
-//   The query loop is branch-free: every lane keeps one hit bit per (class, query) in registers; after the loop
+//   The query loop keeps one hit bit per (class, query) in every lane's registers, with no vector branch (production bit-plane
+//   instances: a scalar loop over the queries whose planes differ from their predecessor's, scan_twins.hpp); after the loop
 //   the hits of the chunk (1-2 % of the remaining tests) go to the wave's LDS hit list -- rows of an adjacency list whose
 //   record length fails the DL's length test are only counted (production instance) -- and the list is expanded, when
 //   another chunk could overflow it, through the class -> entries CSR (bit-plane tiles: the entry id is in the list) into
@@ -145,6 +146,8 @@ struct ScanArgs {
                             // counted as scored pairs and never written; survivors carry RAW_PREFILTERED
   uint32_t* qpairs;         // per query: scored pairs of THIS run, counted where they are produced (materialised or only counted);
                             // nullptr in normal runs (anx_batch_pair_counts: the per-query check of the production pair list)
+  int twins;                // ANX_SCAN_TWINS (default 1): a run of queries with equal planes inside a pass is tested once (scan_twins.hpp); 0 = every
+                            // query is its own leader.  Production bit-plane instances only (BITS && !GEN).
   int dbg;  // ANX_SCAN_DBG (timing experiments only; results are wrong when set): 1 one query per pass, 2 skip process(), 4 no run staging,
             // 8 no hit expansion, 16 pairs dropped before the band filter, 32 filtered pairs not written; result-neutral A/B of HISTORY.md
             // section 19: 64 count-only rows take the hit list like any other, 128 the list is expanded after every chunk
@@ -212,6 +215,24 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
   {  // the tile's query words -> LDS: the comparison loop reads them back as broadcasts into VGPRs
     const uint32_t* __restrict__ src = (BITS ? A.q_bits : A.q_cv) + (size_t)t.q0 * QSTRIDE;
     for (uint32_t i = lane; i < t.nq * QSTRIDE; i += 64) qlds[i] = src[i];
+  }
+  // Twins (scan_twins.hpp): bit i of twin[i >> 5] = query i of the tile has the planes of query i - 1.  The class test sees a query
+  // only through its planes, so a run of equal planes is tested once (run_queries) and the leader's hit bit copied onto the run
+  // (twin_fill).  Bits 0 and 32 stay clear: a run never crosses a pass.  The first query of every kend range stays a leader too: the
+  // encoders give equal planes one kind, but search mode clears the planes of redundant queries after the encoder ran (lattice.hip
+  // k_op_skip), and two cleared neighbours may be of different kinds.  The encoders sort equal planes next to each other.
+  constexpr bool TWINS = BITS && !GEN;
+  uint32_t twin[2] = {0u, 0u};  // wave-uniform
+  if constexpr (TWINS) {
+    bool same = false;
+    if (A.twins && lane < t.nq && (lane & 31u) && lane != (t.kend & 0xFFu) && lane != ((t.kend >> 8) & 0xFFu) && lane != ((t.kend >> 16) & 0xFFu)) {
+      same = true;
+#pragma unroll
+      for (int p = 0; p < NBITPLANES; ++p) same = same && qlds[lane * QSTRIDE + p] == qlds[(lane - 1u) * QSTRIDE + p];
+    }
+    const unsigned long long tm = __ballot(same);
+    twin[0] = (uint32_t)tm;
+    twin[1] = (uint32_t)(tm >> 32);
   }
   // Fused prefilter (bit-plane tiles of queries <= 16 symbols with d <= 3): the first 16 symbols of the tile's queries sit in LDS,
   // the expansion below makes the pairs DENSE in an LDS buffer and tests 64 of them at a time against the band-match bound.
@@ -436,11 +457,12 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
       for (int j = 0; j < CPL; ++j) hm[j] = 0xFFFFFFFFu;  // miss bits
       // one query against the lane's CPL classes: shifts one bit into every hm[j].  TW = planes compared: the query's
       // kind (bit-plane tiles hold queries of every kind 1..NBITPLANES, sorted by kind) or NP count-vector dwords.
-      auto test_query = [&](auto tw, uint32_t qi) {
-        constexpr int TW = decltype(tw)::value;
-        uint32_t qreg[TW];
+      auto load_query = [&](auto tw, uint32_t qi, uint32_t (&qreg)[decltype(tw)::value]) {
 #pragma unroll
-        for (int p = 0; p < TW; ++p) qreg[p] = qlds[(qb + qi) * QSTRIDE + p];
+        for (int p = 0; p < decltype(tw)::value; ++p) qreg[p] = qlds[(qb + qi) * QSTRIDE + p];
+      };
+      auto test_regs = [&](auto tw, const uint32_t (&qreg)[decltype(tw)::value]) {
+        constexpr int TW = decltype(tw)::value;
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
           int32_t acc;
@@ -458,13 +480,53 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
           hm[j] = __builtin_amdgcn_alignbit(hm[j], (uint32_t)acc, 31);  // (hm << 1) | sign(acc)
         }
       };
-      auto run_queries = [&](auto tw, uint32_t lo, uint32_t hi) {  // queries [lo, hi) of the pass, in order
-        uint32_t qi = lo;
-        for (; qi + 2 <= hi; qi += 2) {  // two queries per trip: half the loop overhead, both LDS reads in flight
-          test_query(tw, qi);
-          test_query(tw, qi + 1);
+      auto test_query = [&](auto tw, uint32_t qi) {
+        uint32_t qreg[decltype(tw)::value];
+        load_query(tw, qi, qreg);
+        test_regs(tw, qreg);
+      };
+      // the pass's twin bits (wave-uniform; bit b = query b of the pass is a follower)
+      const uint32_t ptw = TWINS ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((qb ? twin[1] : twin[0]) & (npass >= 32u ? 0xFFFFFFFFu : ((1u << npass) - 1u)))) : 0u;
+      // r followers of the query just tested: their bits move in as misses (twin_fill copies the leader's bit after the pass), so bit
+      // positions stay query positions
+      auto skip_followers = [&](uint32_t r) {
+        if (r) {  // wave-uniform
+          const uint32_t back = 32u - r;  // 1 <= r <= 31
+#pragma unroll
+          for (int j = 0; j < CPL; ++j) hm[j] = __builtin_amdgcn_alignbit(hm[j], 0xFFFFFFFFu, back);  // hm << r | r ones: one instruction per mask
+
         }
-        if (qi < hi) test_query(tw, qi);
+      };
+      auto run_queries = [&](auto tw, uint32_t lo, uint32_t hi) {  // queries [lo, hi) of the pass, in order
+        if constexpr (TWINS) {
+          // the leaders of the range, a scalar bit loop; two per trip: half the loop overhead, both LDS reads in flight
+          if (lo >= hi) return;
+          uint32_t lead = ~ptw & (0xFFFFFFFFu << lo) & (hi >= 32u ? 0xFFFFFFFFu : ((1u << hi) - 1u));  // (bit lo is a leader: the twin mask is cut at the kend boundaries)
+          while (lead) {
+            const uint32_t q0 = (uint32_t)__builtin_ctz(lead);
+            lead &= lead - 1u;
+            const bool two = lead != 0u;
+            const uint32_t q1 = two ? (uint32_t)__builtin_ctz(lead) : hi;
+            lead &= lead - 1u;  // (0 stays 0)
+            const uint32_t q2 = lead ? (uint32_t)__builtin_ctz(lead) : hi;
+            uint32_t r0[decltype(tw)::value], r1[decltype(tw)::value];
+            load_query(tw, q0, r0);
+            load_query(tw, two ? q1 : q0, r1);  // (a lone last leader: read again, not tested)
+            test_regs(tw, r0);
+            skip_followers(q1 - q0 - 1u);
+            if (two) {
+              test_regs(tw, r1);
+              skip_followers(q2 - q1 - 1u);
+            }
+          }
+        } else {
+          uint32_t qi = lo;
+          for (; qi + 2 <= hi; qi += 2) {  // two queries per trip: half the loop overhead, both LDS reads in flight
+            test_query(tw, qi);
+            test_query(tw, qi + 1);
+          }
+          if (qi < hi) test_query(tw, qi);
+        }
       };
       if (BITS) {
         // the tile's queries are sorted by kind; ke[t] = end of the kind-t queries.  The four sub-ranges of the pass run
@@ -483,8 +545,13 @@ __device__ inline void scan_tile(const ScanArgs& AA, const Tile& t, uint32_t ite
       const uint32_t valid = npass >= 32u ? 0xFFFFFFFFu : ((1u << npass) - 1u);
       uint32_t any = 0;
 #pragma unroll
+      for (int j = 0; j < CPL; ++j) hm[j] = ~hm[j] & valid;
+      if constexpr (TWINS) {
+        // every leader's bit onto its followers (no step in a pass without twins); from here on the masks are what testing every query gives
+        if (ptw) twin_fill(hm, (uint32_t)__builtin_amdgcn_readfirstlane((int)(__brev(ptw) >> (32u - npass))));
+      }
+#pragma unroll
       for (int j = 0; j < CPL; ++j) {
-        hm[j] = ~hm[j] & valid;
         if (ADJ && conly[j]) {  // wave-uniform
           counted_only += (uint32_t)__popc(hm[j]);
           hm[j] = 0u;

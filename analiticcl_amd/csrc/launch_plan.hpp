@@ -16,6 +16,7 @@ static inline ScanArgs scan_args_of(const DeviceLexicon* dl) {
   A.cls_len = dl->cls_len; A.cls_off = dl->cls_off; A.sig = dl->sig; A.sig_e = dl->sig_e; A.sig_cbeg = dl->sig_cbeg; A.sighash = dl->sighash; A.sighash_e = dl->sighash_e; A.hash_mask = dl->hash_mask; A.ball = dl->ball;
   A.adj_hdr = dl->adj_hdr; A.adj_planes = dl->adj_planes; A.adj_ids = dl->adj_ids;
   A.e_rec = dl->e_rec;
+  A.twins = switches().scan_twins;
   return A;
 }
 // f(std::integral_constant<int, NP>) for the count-vector width the kernels of the SAD tiles are instantiated for (launch_scan<NP>, k_scan_small<NP>)
