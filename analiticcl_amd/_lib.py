@@ -59,6 +59,12 @@ class LatticeDebug(C.Structure):  # anx_lattice_debug
                 ("lds_limit", C.c_uint32), ("n_launches", C.c_uint32)]
 
 
+class ScanOpts(C.Structure):  # anx_debug_scan_opts
+    _fields_ = [("region_shift", C.c_uint32), ("chunk", C.c_uint32), ("chunk_fused", C.c_uint32), ("chunk_first", C.c_uint32),
+                ("fuse", C.c_int32), ("twins", C.c_int32), ("drop_len", C.c_int32), ("want_exact", C.c_int32), ("count_pairs", C.c_int32),
+                ("slots", C.c_uint32)]
+
+
 class Match(C.Structure):
     _fields_ = [("begin", C.c_size_t), ("end", C.c_size_t), ("n", C.c_uint32), ("selected", C.c_int32),
                 ("var_begin", C.c_size_t), ("var_end", C.c_size_t), ("tag_begin", C.c_uint32),
@@ -307,6 +313,8 @@ def lib():
         "anx_debug_rank_rows": (C.c_int, [C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_uint64, C.c_float, C.c_int,
                                           C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
         "anx_debug_score_slots": (C.c_int, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+        "anx_debug_scan_pairs": (C.c_int, [vp, vp, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(Params), C.POINTER(ScanOpts), vp,
+                                           C.POINTER(C.POINTER(C.c_uint32)), vp, vp, vp]),
         "anx_debug_lattice_decode": (C.c_int, [vp, C.POINTER(SearchParams), C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t,
                                                vp, vp, vp, C.POINTER(LatticeDebug)]),
         "anx_debug_portable_log": (C.c_int, [vp, C.c_size_t, vp]),

@@ -1534,6 +1534,22 @@ int anx_debug_score_slots(const anx_model* m, const anx_batch* b, uint32_t regio
     return anx::debug_score_slots(m->host, m->replicas[(size_t)s.replica].dev, s.b, in, out, err);
   });
 }
+int anx_debug_scan_pairs(const anx_model* m, const anx_batch* b, const char* const* utf8, size_t n, const anx_params* p, const anx_debug_scan_opts* o,
+                         uint32_t* out_counts, uint32_t** out_tiles, uint32_t* out_query, uint32_t* out_raw, uint32_t* out_rctr) {
+  if (!m || !o || !out_counts || !out_tiles || !out_query || !out_raw || !out_rctr || (!b && (!utf8 || !p))) return fail(ANX_EINVAL, "NULL argument");
+  if (b && b->model != m) return fail(ANX_EINVAL, "the batch was encoded with another model");
+  *out_tiles = nullptr;
+  memset(out_counts, 0xFF, 6 * sizeof(uint32_t));
+  if (!m->host.built) return fail(ANX_ENOTBUILT, "Model has not been built yet!");
+  if (check_resident(m)) return g_code;
+  if (m->replicas.size() != 1 || (b && (b->shards.size() != 1 || scattered(b)))) return fail(ANX_EINVAL, "scan pairs: a single-device model and a batch of one shard");
+  const size_t N = b ? b->n_input : n;
+  const anx::DebugScanIn in{o->region_shift, o->chunk, o->chunk_fused, o->chunk_first, o->fuse, o->twins, o->drop_len, o->want_exact, o->count_pairs, utf8, n, p, o->slots};
+  const anx::DebugScanOut out{out_counts, out_tiles, out_query, out_query + N, out_query + 2 * N, out_query + 3 * N, out_raw, out_rctr};
+  std::string err;
+  const int rc = anx::debug_scan_pairs(m->host, m->replicas[0].dev, b ? b->shards[0].b : nullptr, in, out, err);
+  return rc ? fail(rc, err) : ANX_OK;
+}
 int anx_batch_pair_counts(anx_batch* b, uint32_t** out) {
   if (!b || !out) return fail(ANX_EINVAL, "NULL argument");
   const size_t S = b->shards.size();

@@ -62,6 +62,27 @@ struct DebugScoreOut {
   uint32_t* skipped;
 };
 int debug_score_slots(const HostModel& m, const DeviceLexicon* dl, const Batch* b, const DebugScoreIn& in, const DebugScoreOut& out, std::string& err);
+// test hook: the scan stage alone (engine.hip debug_scan_pairs: k_scan_adj / k_scan_bits / k_scan_sad launched by the function a run launches
+// them with, or k_scan_small by the small call's) on tiles the product's own encoders made.  b != nullptr: the batch's tiles and queries (the
+// batch is left as it is); b == nullptr: the n strings are encoded by the small path's encoder with `slots` tile slots per query.  Everything
+// is validated on the host before the first launch (ANX_EINVAL).  Outputs: sizes in include/anx.h; *tiles is malloc'd.
+struct DebugScanIn {
+  uint32_t region_shift;           // log2(slots per region), 10 .. 25
+  uint32_t chunk, chunk_fused, chunk_first;  // 32 .. 1024
+  int fuse, twins, drop_len, want_exact, count_pairs;
+  const char* const* utf8;         // small form
+  size_t n;
+  const anx_params* params;
+  uint32_t slots;                  // 8, 16 or 32
+};
+struct DebugScanOut {
+  uint32_t* counts;                // [6]: tiles, of them in the adjacency / bit-plane / count-vector launch, queries, guard slots written
+  uint32_t** tiles;                // [tiles][15]
+  uint32_t *q_orig, *q_kind, *q_meta, *qpairs;  // [queries] in the sorted order the tiles refer to
+  uint32_t* raw;                   // [64 << region_shift][2]
+  uint32_t* rctr;                  // [64][32]
+};
+int debug_scan_pairs(const HostModel& m, const DeviceLexicon* dl, const Batch* b, const DebugScanIn& in, const DebugScanOut& out, std::string& err);
 void kernel_timer_enable(bool on);  // also clears the totals
 bool kernel_timer_read(const char* name, double* total_ms, uint64_t* launches);  // waits for the recorded launches
 void device_pool_trim(int device);  // hands the cached scratch blocks of the device (and the pinned result buffers) back to the driver

@@ -1182,11 +1182,12 @@ bool kernel_timer_read(const char* name, double* total_ms, uint64_t* launches) {
 
 #include "launch_plan.hpp"
 
+// ---- the scan stage: what Run::scan and the test hook debug_scan_pairs (below) both launch ------------------------------------------------
 template <int NP>
 static void launch_scan(ScanArgs A, uint32_t nadj, uint32_t nbits, uint32_t nsad, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   // tiles: [bit-plane tiles with an adjacency list | other bit-plane tiles | SAD kind]
   const int kt = ktimer_begin("k_scan", st);  // (off unless anx_debug_kernel_timer(1); its launch count = the runs of a batch, repeats after an overflow included)
-  (void)hipEventRecord(e0, st);  // e0 .. e1 = k_scan_adj + k_scan_bits (anx_batch_stats.ms_scan_kernel)
+  if (e0) (void)hipEventRecord(e0, st);  // e0 .. e1 = k_scan_adj + k_scan_bits (anx_batch_stats.ms_scan_kernel)
   const bool gen = A.want_exact || A.qpairs || !A.drop_len;
   if (nadj) {
     A.ntiles = nadj;
@@ -1201,13 +1202,19 @@ static void launch_scan(ScanArgs A, uint32_t nadj, uint32_t nbits, uint32_t nsad
     if (A.want_exact || A.qpairs || !A.drop_len) hipLaunchKernelGGL((k_scan_bits<true>), dim3((nbits + 3) / 4), dim3(256), 0, st, A);
     else hipLaunchKernelGGL((k_scan_bits<false>), dim3((nbits + 3) / 4), dim3(256), 0, st, A);
   }
-  (void)hipEventRecord(e1, st);
+  if (e1) (void)hipEventRecord(e1, st);
   if (nsad) {
     A.tiles += nbits;
     A.ntiles = nsad;
     hipLaunchKernelGGL((k_scan_sad<NP>), dim3((nsad + 3) / 4), dim3(256), 0, st, A);
   }
   ktimer_end(kt, st);
+}
+// the three launches [adj | bits | sad] of a stage with at least one tile (launch_plan.hpp ScanStage); e0 .. e1 (or nullptr) around the bit-plane kernels
+static void scan_stage_launch(const DeviceLexicon* dl, const ScanStage& S, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const ScanArgs A = scan_args_of(dl, S);
+  const uint32_t nsad = S.n_sad_tiles, nbits = S.ntiles - nsad, nadj = std::min(S.n_adj_tiles, nbits);
+  with_nplanes(dl->nplanes, [&](auto np) { launch_scan<decltype(np)::value>(A, nadj, nbits, nsad, st, e0, e1); });
 }
 
 static int ensure_raw(Batch* b, size_t slots_per_region, std::string& err) {
@@ -1383,32 +1390,32 @@ int Run::scan() {
   HIP_TRY(hipMemsetAsync(b->ctl, 0, HR_N * sizeof(uint32_t), st));
   if (b->ntiles == 0) { HIP_TRY(hipEventRecord(b->ev_scan0, st)); HIP_TRY(hipEventRecord(b->ev[5], st)); }
   if (b->ntiles) {
-    ScanArgs A = scan_args_of(dl);
-    A.tiles = b->d_tiles; A.ntiles = b->ntiles; A.q_bits = b->q_bits; A.q_cv = b->q_cv;
-    A.chunk = SCAN_CHUNK;  // (the small call: 64 / 32)
-    A.chunk_fused = switches().scan_chunk_fused ? (uint32_t)switches().scan_chunk_fused : SCAN_CHUNK_FUSED;
-    A.chunk_first = switches().scan_chunk_first ? (uint32_t)switches().scan_chunk_first : SCAN_CHUNK_FIRST;  // (the kernel caps it at the tile's chunk)
+    ScanStage S{};
+    S.tiles = b->d_tiles; S.ntiles = b->ntiles; S.n_adj_tiles = b->n_adj_tiles; S.n_sad_tiles = b->n_sad_tiles; S.q_bits = b->q_bits; S.q_cv = b->q_cv;
+    S.chunk = SCAN_CHUNK;  // (the small call: 64 / 32)
+    S.chunk_fused = switches().scan_chunk_fused ? (uint32_t)switches().scan_chunk_fused : SCAN_CHUNK_FUSED;
+    S.chunk_first = switches().scan_chunk_first ? (uint32_t)switches().scan_chunk_first : SCAN_CHUNK_FIRST;  // (the kernel caps it at the tile's chunk)
 #ifdef ANX_DEBUG_SWITCHES
-    { const char* e = getenv("ANX_SCAN_CHUNK"); const int v = e ? atoi(e) : 0; if (v >= 32 && v <= 1024) A.chunk = (uint32_t)v; }
+    { const char* e = getenv("ANX_SCAN_CHUNK"); const int v = e ? atoi(e) : 0; if (v >= 32 && v <= 1024) S.chunk = (uint32_t)v; }
 #endif
-    A.raw = b->raw; A.region_cap = region_cap; A.rctr = b->rctr; A.qexact = b->qexact; A.want_exact = stop;
-    A.drop_len = (!stop && !b->keep_all_pairs) ? 1 : 0;
-    A.q_rec = b->q_rec;
+    S.raw = b->raw; S.region_cap = region_cap; S.rctr = b->rctr; S.qexact = b->qexact; S.want_exact = stop;
+    S.drop_len = (!stop && !b->keep_all_pairs) ? 1 : 0;
+    S.q_rec = b->q_rec;
     // the band-match bound where the pair is born (not in the run that materialises every pair for the debug view, and not with
     // StopAtExactMatch, whose dropped pairs are counted by the scoring kernel from the materialised list)
-    A.fuse = (switches().fuse_prefilter && switches().prefilter && A.drop_len) ? 1 : 0;
-    A.qpairs = nullptr;
+    S.fuse = (switches().fuse_prefilter && switches().prefilter && S.drop_len) ? 1 : 0;
+    S.twins = switches().scan_twins;
+    S.qpairs = nullptr;
     if (b->count_pairs) {
       if (!b->qpairs && (rc = dalloc(&b->qpairs, nq, err))) return rc;
       HIP_TRY(hipMemsetAsync(b->qpairs, 0, nq * sizeof(uint32_t), st));
-      A.qpairs = b->qpairs;
+      S.qpairs = b->qpairs;
     }
-    A.dbg = 0;
+    S.dbg = 0;
 #ifdef ANX_DEBUG_SWITCHES
-    { const char* e = getenv("ANX_SCAN_DBG"); A.dbg = e ? atoi(e) : 0; }  // read per run: tools/scan_probe.py switches it between runs
+    { const char* e = getenv("ANX_SCAN_DBG"); S.dbg = e ? atoi(e) : 0; }  // read per run: tools/scan_probe.py switches it between runs
 #endif
-    const uint32_t nsad = b->n_sad_tiles, nbits = A.ntiles - nsad, nadj = std::min(b->n_adj_tiles, nbits);
-    with_nplanes(dl->nplanes, [&](auto np) { launch_scan<decltype(np)::value>(A, nadj, nbits, nsad, st, b->ev_scan0, b->ev[5]); });
+    scan_stage_launch(dl, S, st, b->ev_scan0, b->ev[5]);
   }
   HIP_TRY(hipEventRecord(b->ev[1], st));
   b->n_raw = (uint32_t)(SCAN_REGIONS << b->region_shift);  // slot space (regions are sparse)
@@ -2469,6 +2476,128 @@ int debug_score_slots(const HostModel& m, const DeviceLexicon* dl, const Batch* 
   }
   memcpy(out.surv, surv.data(), nsurv * sizeof(SurvRec));
   *out.skipped = ctl[HR_CTR + CTR_SKIPPED];
+  return ANX_OK;
+}
+
+// ---- test hook: the scan stage alone (anx_debug_scan_pairs; tests/test_gpu_scan_door.py) ------------------------------------------------
+// The tiles are the encoder's own, never the caller's: the batch's (batch form) or those small_encode_launch lays on a borrowed context of the
+// small path (small form, as small_find borrows one).  What is plain data in ScanArgs is the caller's and validated on the host before anything
+// is launched.  The pair list, its counters and the per-query counts are the hook's own buffers: the pair list (and SCAN_GUARD slots behind
+// it) starts as 0xFE bytes -- neither RAW_INVALID nor a pair -- the counters as 0.  The launch is scan_stage_launch / launch_scan_small.
+constexpr uint32_t SCAN_GUARD = 4096;  // slots behind the pair list that must keep the fill
+int debug_scan_pairs(const HostModel& m, const DeviceLexicon* dl, const Batch* b, const DebugScanIn& in, const DebugScanOut& out, std::string& err) {
+  if (!dl) { err = "scan pairs: the model is not resident on a device"; return ANX_ENODEVICE; }
+  auto refuse = [&](const std::string& msg) { err = "scan pairs: " + msg; return ANX_EINVAL; };
+  const bool small = b == nullptr;
+  if (in.region_shift < 10 || in.region_shift > 25) return refuse("region_shift outside 10 .. 25");
+  for (uint32_t c : {in.chunk, in.chunk_fused, in.chunk_first})
+    if (c < 32 || c > 1024) return refuse("a chunk size outside 32 .. 1024");
+  if (in.fuse && (!in.drop_len || in.want_exact)) return refuse("fuse without drop_len or with want_exact: the fused filter takes pairs that passed the length test (as a run sets it)");
+  uint32_t lens[SMALL_MAX];
+  uint32_t maxbytes = 0;
+  if (small) {
+    if (in.n == 0 || in.n > SMALL_MAX) return refuse("the small form takes 1 .. " + std::to_string(SMALL_MAX) + " strings");
+    if (in.slots != 8 && in.slots != 16 && in.slots != 32) return refuse("tile slots per query are 8, 16 or 32");
+    if ((size_t)in.slots * in.n > (size_t)8 * SMALL_MAX) return refuse("more tile slots than a context of the small path holds");
+    if (in.want_exact || in.count_pairs || !in.drop_len) return refuse("the small call's kernel has no instance for StopAtExactMatch, per-query counts or every pair");
+    if (dl->nplanes > 42) return refuse("the small path does not take this alphabet");
+    for (size_t i = 0; i < in.n; ++i) {
+      const size_t l = in.utf8[i] ? strlen(in.utf8[i]) : 0;
+      if (l > SMALL_MAX_BYTES) return refuse("a string of more than " + std::to_string(SMALL_MAX_BYTES) + " bytes");
+      lens[i] = (uint32_t)l;
+      maxbytes = std::max(maxbytes, (uint32_t)l);
+    }
+  } else {
+    if (b->nq >= ((size_t)1 << 26)) return refuse("more than 2^26 queries");
+    if (in.want_exact && (!b->params.stop_at_exact_match || !b->qexact)) return refuse("want_exact with a batch that was not encoded for StopAtExactMatch");
+  }
+  HIP_TRY(hipSetDevice(dl->device));
+  const size_t nq = small ? in.n : b->nq;
+  const uint32_t ntiles = small ? in.slots * (uint32_t)in.n : b->ntiles;
+  const size_t R = (size_t)SCAN_REGIONS << in.region_shift;
+  uint2* d_raw = nullptr;
+  uint32_t *d_rctr = nullptr, *d_qpairs = nullptr;
+  SmallCtx* c = nullptr;
+  auto cleanup = [&]() {
+    for (void* p : {(void*)d_raw, (void*)d_rctr, (void*)d_qpairs}) if (p) (void)hipFree(p);
+    if (c) { (void)hipStreamSynchronize(c->st); small_ctx_release(c); }
+  };
+  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
+  hipError_t e;
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e);  // (the encoder's streams: the tiles and query arrays are complete)
+  if ((e = hipMalloc(reinterpret_cast<void**>(&d_raw), (R + SCAN_GUARD) * sizeof(uint2))) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_rctr), SCAN_REGIONS * RC_STRIDE * 4)) != hipSuccess ||
+      (e = hipMalloc(reinterpret_cast<void**>(&d_qpairs), std::max<size_t>(nq, 1) * 4)) != hipSuccess)
+    return fail_hip(e);
+  if ((e = hipMemset(d_raw, 0xFE, (R + SCAN_GUARD) * sizeof(uint2))) != hipSuccess || (e = hipMemset(d_rctr, 0, SCAN_REGIONS * RC_STRIDE * 4)) != hipSuccess ||
+      (e = hipMemset(d_qpairs, 0, std::max<size_t>(nq, 1) * 4)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)
+    return fail_hip(e);
+  ScanStage S{};
+  S.ntiles = ntiles;
+  S.raw = d_raw; S.region_cap = 1u << in.region_shift; S.rctr = d_rctr;
+  S.chunk = in.chunk; S.chunk_fused = in.chunk_fused; S.chunk_first = in.chunk_first;
+  S.want_exact = in.want_exact ? 1 : 0; S.drop_len = in.drop_len ? 1 : 0; S.fuse = in.fuse ? 1 : 0; S.twins = in.twins ? 1 : 0;
+  S.qpairs = in.count_pairs ? d_qpairs : nullptr; S.dbg = 0;
+  const Tile* d_tiles = nullptr;
+  const uint32_t *d_qorig = nullptr, *d_qmeta = nullptr;
+  uint32_t nadj = 0, nsad = 0;
+  if (small) {
+    c = small_ctx_acquire(dl, err);
+    if (!c) { (void)hipGetLastError(); cleanup(); return ANX_ENODEVICE; }
+    uint32_t* h_off = reinterpret_cast<uint32_t*>(c->h_in + SMALL_IN_BLOB);
+    size_t pos = 0;
+    for (size_t i = 0; i < in.n; ++i) {  // the inputs -> pinned staging, as small_find packs them
+      h_off[i] = (uint32_t)pos;
+      if (lens[i]) memcpy(c->h_in + pos, in.utf8[i], lens[i]);
+      c->h_in[pos + lens[i]] = '\0';
+      pos += (size_t)lens[i] + 1;
+    }
+    h_off[in.n] = (uint32_t)pos;
+    memset(c->h_in + pos, 0, 16);
+    const uint32_t qw = std::max<uint32_t>(1u, (maxbytes + 15u) / 16u);
+    SmallEnc enc = c->enc;
+    enc.text = nullptr; enc.textoff = nullptr;
+    SmallZero z{};  // (the context's counters are not this call's: nothing to clear)
+    const int rc = small_encode_launch(m, dl, enc, reinterpret_cast<const uint8_t*>(c->h_in), h_off, (uint32_t)in.n, qw, *in.params, z, in.slots, true, h_off, c->st, err);
+    if (rc) { cleanup(); return rc; }
+    S.tiles = c->enc.tiles; S.q_bits = c->enc.q_bits; S.q_cv = c->enc.q_cv; S.q_rec = c->enc.q_rec; S.qexact = c->enc.qexact;
+    launch_scan_small(dl, S, c->st);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(c->st)) != hipSuccess) return fail_hip(e);
+    d_tiles = c->enc.tiles; d_qorig = c->enc.q_orig; d_qmeta = c->enc.q_meta;
+  } else {
+    nsad = b->n_sad_tiles; nadj = std::min(b->n_adj_tiles, ntiles - nsad);
+    S.tiles = b->d_tiles; S.n_adj_tiles = b->n_adj_tiles; S.n_sad_tiles = nsad; S.q_bits = b->q_bits; S.q_cv = b->q_cv; S.q_rec = b->q_rec; S.qexact = b->qexact;
+    if (ntiles) scan_stage_launch(dl, S, 0, nullptr, nullptr);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e);
+    d_tiles = b->d_tiles; d_qorig = b->q_orig; d_qmeta = b->q_meta;
+  }
+  // ---- everything back ----------------------------------------------------------------------------------------------------------------
+  static_assert(sizeof(Tile) == 15 * sizeof(uint32_t), "a tile is 15 words");
+  uint32_t* tiles = static_cast<uint32_t*>(malloc(std::max<size_t>(ntiles, 1) * sizeof(Tile)));
+  std::vector<uint2> guard(SCAN_GUARD);
+  if (!tiles) { cleanup(); err = "out of memory"; return ANX_EINVAL; }
+  if ((ntiles && (e = hipMemcpy(tiles, d_tiles, (size_t)ntiles * sizeof(Tile), hipMemcpyDeviceToHost)) != hipSuccess) ||
+      (nq && ((e = hipMemcpy(out.q_orig, d_qorig, nq * 4, hipMemcpyDeviceToHost)) != hipSuccess || (e = hipMemcpy(out.q_meta, d_qmeta, nq * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+              (e = hipMemcpy(out.qpairs, d_qpairs, nq * 4, hipMemcpyDeviceToHost)) != hipSuccess)) ||
+      (e = hipMemcpy(out.raw, d_raw, R * sizeof(uint2), hipMemcpyDeviceToHost)) != hipSuccess ||
+      (e = hipMemcpy(guard.data(), d_raw + R, SCAN_GUARD * sizeof(uint2), hipMemcpyDeviceToHost)) != hipSuccess ||
+      (e = hipMemcpy(out.rctr, d_rctr, SCAN_REGIONS * RC_STRIDE * 4, hipMemcpyDeviceToHost)) != hipSuccess) {
+    free(tiles);
+    return fail_hip(e);
+  }
+  cleanup();
+  // the kind of every query as its tile tests it (kend), 0 = count vectors; UINT32_MAX = in no tile
+  for (size_t q = 0; q < nq; ++q) out.q_kind[q] = 0xFFFFFFFFu;
+  for (uint32_t i = 0; i < ntiles; ++i) {
+    const Tile& t = reinterpret_cast<const Tile*>(tiles)[i];
+    for (uint32_t j = 0; j < t.nq && (size_t)t.q0 + j < nq; ++j)
+      out.q_kind[t.q0 + j] = t.kind == 0u ? 0u : j < (t.kend & 0xFFu) ? 1u : j < ((t.kend >> 8) & 0xFFu) ? 2u : j < ((t.kend >> 16) & 0xFFu) ? 3u : 4u;
+  }
+  uint32_t touched = 0;
+  for (const uint2& g : guard) touched += (g.x != 0xFEFEFEFEu || g.y != 0xFEFEFEFEu) ? 1u : 0u;
+  out.counts[0] = ntiles; out.counts[1] = nadj; out.counts[2] = small ? 0u : ntiles - nsad - nadj; out.counts[3] = nsad; out.counts[4] = (uint32_t)nq;
+  out.counts[5] = touched;
+  *out.tiles = tiles;
   return ANX_OK;
 }
 

@@ -8,15 +8,35 @@
 #pragma once
 
 // ---- scan ------------------------------------------------------------------------------------------------------------------------------
-// every lexicon-side field; the caller adds tiles / ntiles, the query arrays (q_bits, q_cv, q_rec, qexact), raw / region_cap / rctr,
-// chunk / chunk_fused, want_exact / drop_len / fuse, qpairs and dbg
-static inline ScanArgs scan_args_of(const DeviceLexicon* dl) {
+// One scan stage: everything of ScanArgs that is not the lexicon's.  The batch path (engine.hip scan_stage_launch), the small call
+// (launch_scan_small below) and the test hook debug_scan_pairs fill this and nothing else.
+struct ScanStage {
+  const Tile* tiles;       // in launch order: [tiles that stream an adjacency list | other bit-plane tiles | count-vector tiles]
+  uint32_t ntiles;
+  uint32_t n_adj_tiles, n_sad_tiles;  // the batch path's launch split (the small call's one launch looks at every tile itself)
+  const uint32_t *q_bits, *q_cv;
+  const uint4* q_rec;
+  const uint32_t* qexact;
+  uint2* raw;
+  uint32_t region_cap;     // pair-list slots per region
+  uint32_t* rctr;
+  uint32_t chunk, chunk_fused, chunk_first;
+  int want_exact, drop_len, fuse, twins;
+  uint32_t* qpairs;        // per-query pair counts, or nullptr
+  int dbg;
+};
+// the ONE fill of the kernels' arguments: the lexicon side and the stage
+static inline ScanArgs scan_args_of(const DeviceLexicon* dl, const ScanStage& S) {
   ScanArgs A{};
   A.cls_bits = dl->cls_bits; A.cls_planes = dl->cls_planes; A.scan_rec = dl->scan_rec; A.scan_rec34 = dl->scan_rec34; A.pad_rec = dl->nentries; A.cstride = dl->cstride; A.pad_class = dl->nclasses;
   A.cls_len = dl->cls_len; A.cls_off = dl->cls_off; A.sig = dl->sig; A.sig_e = dl->sig_e; A.sig_cbeg = dl->sig_cbeg; A.sighash = dl->sighash; A.sighash_e = dl->sighash_e; A.hash_mask = dl->hash_mask; A.ball = dl->ball;
   A.adj_hdr = dl->adj_hdr; A.adj_planes = dl->adj_planes; A.adj_ids = dl->adj_ids;
   A.e_rec = dl->e_rec;
-  A.twins = switches().scan_twins;
+  A.tiles = S.tiles; A.ntiles = S.ntiles; A.q_bits = S.q_bits; A.q_cv = S.q_cv; A.q_rec = S.q_rec; A.qexact = S.qexact;
+  A.raw = S.raw; A.region_cap = S.region_cap; A.rctr = S.rctr;
+  A.chunk = S.chunk; A.chunk_fused = S.chunk_fused; A.chunk_first = S.chunk_first;
+  A.want_exact = S.want_exact; A.drop_len = S.drop_len; A.fuse = S.fuse; A.twins = S.twins;
+  A.qpairs = S.qpairs; A.dbg = S.dbg;
   return A;
 }
 // f(std::integral_constant<int, NP>) for the count-vector width the kernels of the SAD tiles are instantiated for (launch_scan<NP>, k_scan_small<NP>)
@@ -29,6 +49,16 @@ static inline void with_nplanes(int nplanes, F&& f) {
     case 32: f(std::integral_constant<int, 32>{}); break;
     default: f(std::integral_constant<int, 42>{}); break;
   }
+}
+// the small call's flat reservations (SCAN_CHUNK / SCAN_CHUNK_FUSED of the batch path: 256 / 128 -- a wave here holds a share of ONE query's pairs)
+constexpr uint32_t SMALL_CHUNK = 64, SMALL_CHUNK_FUSED = 32, SMALL_CHUNK_FIRST = 64;
+// the small call's scan as small_find and the test hook both launch it: ONE launch of k_scan_small over every tile slot, a wave per slot
+static inline void launch_scan_small(const DeviceLexicon* dl, const ScanStage& S, hipStream_t st) {
+  const ScanArgs A = scan_args_of(dl, S);
+  const dim3 grid((A.ntiles + 3) / 4);
+  const int kt = ktimer_begin("k_scan_small", st);  // (off unless anx_debug_kernel_timer(1): no event, no launch)
+  with_nplanes(dl->nplanes, [&](auto np) { hipLaunchKernelGGL(k_scan_small<decltype(np)::value>, grid, dim3(256), 0, st, A); });
+  ktimer_end(kt, st);
 }
 
 // ---- score -----------------------------------------------------------------------------------------------------------------------------

@@ -245,15 +245,15 @@ int small_find(const HostModel& m, const DeviceLexicon* dl, const char* const* u
   // ---- scan -----------------------------------------------------------------------------------------------------------------------------
   const uint32_t region_cap = 1u << SMALL_SHIFT;
   {
-    ScanArgs A = scan_args_of(dl);
-    A.tiles = c->enc.tiles; A.ntiles = slots * n32; A.q_bits = c->enc.q_bits; A.q_cv = c->enc.q_cv;
-    A.chunk = 64; A.chunk_fused = 32; A.chunk_first = 64;  // flat reservations (SCAN_CHUNK / SCAN_CHUNK_FUSED of the batch path: 256 / 128 -- a wave here holds a share of ONE query's pairs)
-    A.raw = c->raw; A.region_cap = region_cap; A.rctr = c->rctr; A.qexact = c->enc.qexact; A.want_exact = 0; A.drop_len = 1;
-    A.q_rec = c->enc.q_rec;
-    A.fuse = (switches().fuse_prefilter && switches().prefilter) ? 1 : 0;  // (the batch path: only with drop_len, which is always 1 here)
-    A.qpairs = nullptr; A.dbg = 0;
-    const dim3 grid((A.ntiles + 3) / 4);
-    with_nplanes(dl->nplanes, [&](auto np) { hipLaunchKernelGGL(k_scan_small<decltype(np)::value>, grid, dim3(256), 0, st, A); });
+    ScanStage S{};
+    S.tiles = c->enc.tiles; S.ntiles = slots * n32; S.q_bits = c->enc.q_bits; S.q_cv = c->enc.q_cv;
+    S.chunk = SMALL_CHUNK; S.chunk_fused = SMALL_CHUNK_FUSED; S.chunk_first = SMALL_CHUNK_FIRST;  // flat reservations (launch_plan.hpp)
+    S.raw = c->raw; S.region_cap = region_cap; S.rctr = c->rctr; S.qexact = c->enc.qexact; S.want_exact = 0; S.drop_len = 1;
+    S.q_rec = c->enc.q_rec;
+    S.fuse = (switches().fuse_prefilter && switches().prefilter) ? 1 : 0;  // (the batch path: only with drop_len, which is always 1 here)
+    S.twins = switches().scan_twins;
+    S.qpairs = nullptr; S.dbg = 0;
+    launch_scan_small(dl, S, st);
   }
   // ---- score: the plan of the batch path (launch_plan.hpp) at fixed capacities ------------------------------------------------------------
   ScorePlan plan = score_plan_of(m, dl, p.score_threshold, qw, d);

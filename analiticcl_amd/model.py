@@ -1328,6 +1328,36 @@ class VariantModel:
                                              lds=int(arrs["lds_of"][j])))
         return res
 
+    def debug_scan_pairs(self, batch: Optional["Batch"] = None, inputs: Optional[Sequence[str]] = None, params: Optional[SearchParameters] = None,
+                         region_shift: int = 12, chunk: int = 256, chunk_fused: int = 128, chunk_first: int = 32, fuse: bool = True,
+                         twins: bool = True, drop_len: bool = True, want_exact: bool = False, count_pairs: bool = False, slots: int = 32) -> dict:
+        """Test hook (anx_debug_scan_pairs): the scan stage alone.  With `batch`: the batch's own tiles through a run's three launches;
+        with `inputs` and `params`: the small call's encoder (slots tile slots per query) and k_scan_small.  Returns the tiles as launched
+        [tiles, 15], nadj / nbits / nsad, per query of the sorted order q_orig / kind / meta (len | k << 8 | d << 16) / qpairs, the whole
+        pair list raw [64, slots per region, 2] (0xFEFEFEFE = never touched), rctr [64, 32] and guard (slots written behind the pair
+        list).  A refusal raises AnxError before anything is launched."""
+        import numpy as np
+        o = L.ScanOpts(region_shift, chunk, chunk_fused, chunk_first, int(fuse), int(twins), int(drop_len), int(want_exact), int(count_pairs), slots)
+        if batch is not None:
+            n, arr, cp = batch.n, None, None
+        else:
+            n = len(inputs)
+            arr = (C.c_char_p * max(n, 1))(*[_b(s) for s in inputs])
+            cp = C.byref(params._c())
+        if not 10 <= region_shift <= 25:
+            raw = np.zeros((64, 1, 2), np.uint32)   # (refused below; the output is sized by the shift)
+        else:
+            raw = np.zeros((64, 1 << region_shift, 2), np.uint32)
+        counts, query, rctr = np.zeros(6, np.uint32), np.zeros((4, max(n, 1)), np.uint32), np.zeros((64, 32), np.uint32)
+        pt = C.POINTER(C.c_uint32)()
+        L.check(L.lib().anx_debug_scan_pairs(self.h, batch.h if batch is not None else None, arr, n, cp, C.byref(o), counts.ctypes.data, C.byref(pt),
+                                             query.ctypes.data, raw.ctypes.data, rctr.ctypes.data))
+        nt, nq = int(counts[0]), int(counts[4])
+        tiles = np.ctypeslib.as_array(pt, shape=(max(nt, 1), 15)).copy()[:nt]
+        L.lib().anx_counts_free(pt)
+        return dict(tiles=tiles, nadj=int(counts[1]), nbits=int(counts[2]), nsad=int(counts[3]), nq=nq, guard=int(counts[5]),
+                    q_orig=query[0, :nq], kind=query[1, :nq], meta=query[2, :nq], qpairs=query[3, :nq], raw=raw, rctr=rctr)
+
     def contextrule_element_matches(self, rule: int, position: int, vocab_id: int, lexindex: int, flat: bool = False) -> bool:
         """Test hook (anx_debug_contextrule_match): element `position` of context rule `rule` on (vocab_id, lexindex), evaluated as
         the parsed pattern (flat=False) or as the flattened element the device decoder reads (flat=True)."""

@@ -47,7 +47,8 @@ extern "C" {
  *    anx_mine_params / anx_mine_site / anx_mine_result and the hooks anx_debug_mine_stats / anx_debug_mine_chunk: confusable patterns
  *    mined from string pairs (additive, nothing else changed); anx_evaluate_sweep / _packed, the struct anx_gold_summary and the hooks
  *    anx_debug_evaluate_sweep_chunk / anx_debug_sweep_stats: several parameter sets over the same gold pairs (additive); the test hooks
- *    anx_debug_lattice_decode (with the struct anx_lattice_debug) and anx_debug_portable_log (additive). */
+ *    anx_debug_lattice_decode (with the struct anx_lattice_debug) and anx_debug_portable_log (additive); the test hook
+ *    anx_debug_scan_pairs and its options struct anx_debug_scan_opts: additive. */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -565,6 +566,33 @@ int anx_debug_score_slots(const anx_model *model, const anx_batch *batch, uint32
                           const uint32_t *slots, uint32_t seg_cap, uint32_t surv_region_cap, uint32_t list_cap, uint32_t blk,
                           int one_launch, uint32_t *out_meta, double *out_score, uint32_t *out_qcount, void *out_surv,
                           uint32_t *out_ctr, void *out_seg, uint32_t *out_skipped);
+/* Test hook: the scan stage (k_scan_adj, k_scan_bits, k_scan_sad; k_scan_small) alone, on tiles the product's own encoders made, with
+ * the whole pair list returned.  Batch form (`batch` != NULL: anx_batch_encode[_packed] on a resident single-device model, one shard; it
+ * need not have run and is left as it is; utf8 / n / params are ignored): the batch's tiles through the three launches of a run.  Small form
+ * (`batch` == NULL): 1 .. 4096 strings of at most 64 bytes are encoded by the small call's encoder with opts->slots (8, 16 or 32; slots * n
+ * <= 32768) tile slots per query and scanned by k_scan_small; want_exact, count_pairs and drop_len == 0 are refused there.  opts: the pair
+ * list has 64 regions of 2^region_shift slots (10 .. 25); chunk, chunk_fused, chunk_first (32 .. 1024) are the slots a wave reserves at a
+ * time (a run: 256 / 128 / 32, the small call: 64 / 32 / 64); fuse = the band-match bound where a pair is born; twins = queries with equal
+ * planes are tested once; drop_len = pairs with |lq - lc| > d are counted, not written; want_exact = bit 31 on pairs of the query's exact
+ * class (only with a batch encoded for StopAtExactMatch); count_pairs = per-query counts.  The kernel instance follows from these as in a
+ * run.  Everything is validated on the host before anything is launched (ANX_EINVAL).
+ * Outputs: out_counts[6] = tiles, of them in the adjacency / other bit-plane / count-vector launch (small form: 0), queries nq, slots
+ * written behind the pair list (0 unless the kernel is wrong); *out_tiles = malloc'd [tiles][15] words (struct Tile of
+ * analiticcl_amd/csrc/kernels_common.hpp, in launch order; the small form's unused slots have nq = 0; release with anx_counts_free);
+ * out_query[4][N], N = the batch's inputs or n, the first nq of each row in the SORTED order the tiles' q0 refers to: input index, kind as
+ * the tile tests the query (0 = count vectors, 1 .. 4 planes), len | k << 8 | d << 16 | lowercase << 24, per-query pair count;
+ * out_raw[64 << region_shift][2] = the pair list (query in sorted order, entry id | flags; UINT32_MAX = an unused slot of a reservation;
+ * 0xFEFEFEFE = never touched); out_rctr[64][32] = the regions' counter blocks (word 0 slots reserved, 1 scored pairs, 2 pairs the fused
+ * filter tested, 4 + 2 * kind class tests as uint64, 14 / 15 adjacency rows streamed / by the first tile of a group).
+ * tests/test_gpu_scan_door.py compares all of it with the reference set of tests/scan_cases.py. */
+typedef struct anx_debug_scan_opts {
+  uint32_t region_shift, chunk, chunk_fused, chunk_first;
+  int32_t fuse, twins, drop_len, want_exact, count_pairs;
+  uint32_t slots;
+} anx_debug_scan_opts;
+int anx_debug_scan_pairs(const anx_model *model, const anx_batch *batch, const char *const *utf8_inputs, size_t n,
+                         const anx_params *params, const anx_debug_scan_opts *opts, uint32_t *out_counts, uint32_t **out_tiles,
+                         uint32_t *out_query, uint32_t *out_raw, uint32_t *out_rctr);
 
 /* ---- output of `analiticcl query` --------------------------------------------------
  * The TSV lines / JSON items of output_matches_as_tsv / output_matches_as_json (src/bin/analiticcl.rs:21-187) for n

@@ -32,6 +32,7 @@ void kernel_timer_enable(bool) {}
 bool kernel_timer_read(const char*, double* ms, uint64_t* n) { if (ms) *ms = 0.0; if (n) *n = 0; return false; }
 int debug_band_bound(int, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, size_t, int, int, uint8_t*, std::string& err) { err = "stub: no device"; return ANX_ENODEVICE; }
 int debug_score_slots(const HostModel&, const DeviceLexicon*, const Batch*, const DebugScoreIn&, const DebugScoreOut&, std::string& err) { err = "stub: no device"; return ANX_ENODEVICE; }
+int debug_scan_pairs(const HostModel&, const DeviceLexicon*, const Batch*, const DebugScanIn&, const DebugScanOut&, std::string& err) { err = "stub: no device"; return ANX_ENODEVICE; }
 void* stream_create(int, std::string&, bool) { return malloc(1); }
 void stream_destroy(int, void* s) { free(s); }
 void* host_result_alloc(size_t bytes) { return malloc(bytes ? bytes : 1); }
