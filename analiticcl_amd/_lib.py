@@ -276,6 +276,13 @@ def lib():
         "anx_debug_evaluate_sweep_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), sz, C.POINTER(GoldSummary),
                                                      C.POINTER(GoldEval), C.POINTER(PairScore), sz]),
         "anx_debug_sweep_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
+        "anx_evaluate_sweep_weights": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(Weights), sz,
+                                                 C.POINTER(GoldSummary), C.POINTER(GoldEval)]),
+        "anx_evaluate_sweep_weights_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(Params), C.POINTER(Weights), sz,
+                                                        C.POINTER(GoldSummary), C.POINTER(GoldEval)]),
+        "anx_debug_evaluate_sweep_weights_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(Weights), sz,
+                                                             C.POINTER(GoldSummary), C.POINTER(GoldEval), sz]),
+        "anx_debug_weight_sweep_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
         "anx_default_mine_params": (None, [C.POINTER(MineParams)]),
         "anx_mine_confusables": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), C.POINTER(C.c_uint32), sz, C.POINTER(MineParams),
                                            C.POINTER(C.POINTER(MineResult))]),

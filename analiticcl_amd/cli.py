@@ -19,7 +19,9 @@ learned variant list) and writes the table of the change sites of their edit scr
 `sweep` has none either: it reads the `input<TAB>gold` lines of `evaluate` and a `--grid` of parameter sets (a TSV whose header names
 columns among `k d n t T s freq-weight`; every further line is one set in the syntax of those options, absent columns take the command
 line's value, the first set is the baseline) and writes one TSV line per set (evaluate_sweep: the set's seven parameters, pairs,
-accuracy@1, mrr, ranked share, the eight reason counts, gained@1 / lost@1 against the first set, mean list length).
+accuracy@1, mrr, ranked share, the eight reason counts, gained@1 / lost@1 against the first set, mean list length).  A grid that also names
+any of `w-ld w-lcs w-prefix w-suffix w-case` is a weight grid (evaluate_sweep_weights: absent weight columns take `--weight-*`, the five
+weights are printed behind the seven parameters).
 Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
@@ -160,7 +162,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min-count", type=int, default=1, help="mine mode, with --as-confusables: only patterns counted at least this often")
     p.add_argument("--summary-json", default=None, help="evaluate mode: write the summary as JSON to this file instead of as text to standard error; "
                                                         "sweep mode: write the summaries as JSON to this file as well")
-    p.add_argument("--grid", default=None, help="sweep mode: TSV file of parameter sets; the header names columns among `k d n t T s freq-weight`, every further "
+    p.add_argument("--grid", default=None, help="sweep mode: TSV file of parameter sets; the header names columns among `k d n t T s freq-weight` (and `w-ld w-lcs w-prefix w-suffix w-case`: a weight grid), every further "
                                                 "line is one set in the syntax of those options; the first set is the baseline")
     p.add_argument("--index-cache", default=None, help="image of the built model: loaded if the file exists (lexicons are then not read), written after build() otherwise")
     p.add_argument("--device", type=int, default=None)
@@ -567,26 +569,32 @@ def run_evaluate(model, params, a, out) -> None:
 
 
 GRID_COLUMNS = ("k", "d", "n", "t", "T", "s", "freq-weight")   # the grid's columns, named after query's options (freq-weight: --freq-ranking)
+GRID_WEIGHT_COLUMNS = ("w-ld", "w-lcs", "w-prefix", "w-suffix", "w-case")   # a grid that names one of them is a weight grid (evaluate_sweep_weights)
 
 
 def parse_grid(lines, a) -> List[dict]:
     """The parameter sets of a `sweep --grid` file.  The first line names tab-separated columns among GRID_COLUMNS; every further
     non-empty line is one set, its cells in the syntax of the options (k / d: an integer, a ratio, or `ratio;limit`; s: 0 or 1).  A
     column the grid does not have takes the command line's value (`a`: the parsed arguments).  -> one dict per set, GRID_COLUMNS -> the
-    cell as text, in file order; the first set is the baseline."""
+    cell as text, in file order; the first set is the baseline.  The header may also name GRID_WEIGHT_COLUMNS (the five score weights):
+    a grid that names any of them is a weight grid, and every set's dict then holds all five (absent ones: --weight-* of the command
+    line); a grid without them gives the dicts it always gave."""
     rows = [ln.rstrip("\r\n") for ln in lines]
     rows = [ln for ln in rows if ln.strip()]
     if not rows:
         raise ValueError("grid: no header line")
     header = rows[0].split("\t")
     for c in header:
-        if c not in GRID_COLUMNS:
-            raise ValueError("grid: unknown column %r (known: %s)" % (c, " ".join(GRID_COLUMNS)))
+        if c not in GRID_COLUMNS and c not in GRID_WEIGHT_COLUMNS:
+            raise ValueError("grid: unknown column %r (known: %s)" % (c, " ".join(GRID_COLUMNS + GRID_WEIGHT_COLUMNS)))
     if len(set(header)) != len(header):
         raise ValueError("grid: a column is named twice")
     base = {"k": str(a.max_anagram_distance), "d": str(a.max_edit_distance), "n": str(a.max_matches), "t": rust_f64(a.score_threshold),
             "T": rust_f64(a.cutoff_threshold), "s": "1" if a.stop_exact else "0",
             "freq-weight": rust_f64(a.freq_ranking if a.freq_ranking is not None else 0.0)}
+    if any(c in GRID_WEIGHT_COLUMNS for c in header):
+        base.update({"w-ld": rust_f64(a.weight_ld), "w-lcs": rust_f64(a.weight_lcs), "w-prefix": rust_f64(a.weight_prefix),
+                     "w-suffix": rust_f64(a.weight_suffix), "w-case": rust_f64(a.weight_case)})
     sets = []
     for ln in rows[1:]:
         cells = ln.split("\t")
@@ -611,11 +619,20 @@ def grid_params(d: dict, a) -> SearchParameters:
     return make_params(b)
 
 
+def grid_weights(d: dict) -> Weights:
+    """The weights of one set of a weight grid (parse_grid)."""
+    try:
+        return Weights(**{c[2:]: float(d[c]) for c in GRID_WEIGHT_COLUMNS})
+    except ValueError:
+        raise ValueError("grid: a weight is not a number in %r" % [d[c] for c in GRID_WEIGHT_COLUMNS])
+
+
 def sweep_tsv_line(d: dict, s: dict) -> str:
     """The set's parameters (GRID_COLUMNS), pairs, accuracy@1, mrr, ranked share, the eight reason counts (GOLD_REASONS order), gained@1,
-    lost@1 against the first set, the mean number of variants per input.  s: VariantModel.sweep_summary."""
+    lost@1 against the first set, the mean number of variants per input.  s: VariantModel.sweep_summary.  A set of a weight grid
+    prints its five weights (GRID_WEIGHT_COLUMNS) behind the seven parameters."""
     n = s["n"]
-    return "\t".join([d[c] for c in GRID_COLUMNS] + [str(n), rust_f64(s["accuracy_at_1"]), rust_f64(s["mrr"]), rust_f64(s["ranked_share"])] +
+    return "\t".join([d[c] for c in GRID_COLUMNS] + [d[c] for c in GRID_WEIGHT_COLUMNS if c in d] + [str(n), rust_f64(s["accuracy_at_1"]), rust_f64(s["mrr"]), rust_f64(s["ranked_share"])] +
                      [str(s["reasons"][r]) for r in GOLD_REASONS] +
                      [str(s["gained_at_1"]), str(s["lost_at_1"]), rust_f64(s["n_results"] / n if n else 0.0)])
 
@@ -638,7 +655,10 @@ def run_sweep(model, a, out) -> None:
         x, _, y = (line[:-1] if line.endswith("\r") else line).partition("\t")
         pa.append(x)
         pg.append(y.split("\t", 1)[0])
-    summaries = model.evaluate_sweep(pa, pg, [grid_params(d, a) for d in sets])
+    if "w-ld" in sets[0]:   # a weight grid: one base run per (k, d, s), every set re-scored and re-ranked on the device
+        summaries = model.evaluate_sweep_weights(pa, pg, [grid_params(d, a) for d in sets], [grid_weights(d) for d in sets])
+    else:
+        summaries = model.evaluate_sweep(pa, pg, [grid_params(d, a) for d in sets])
     for d, s in zip(sets, summaries):
         out.write(sweep_tsv_line(d, s) + "\n")
     out.flush()

@@ -1844,6 +1844,37 @@ static int vocab_entry_ensure(const HostModel& m, const DeviceLexicon* dl, hipSt
   dl->vocab_ent = t;
   return ANX_OK;
 }
+// The device sequence of anx_batch_fetch_measures, enqueued on st: the offsets of the compact export into d_off[n_input + 1] and one
+// record per ranked row into d_out[n_results], in export order.  d_cnt[n_input], d_tmp (scan_tmp_bytes), d_list[n_surv + 4]: scratch.
+static int measures_enqueue(const HostModel& m, const DeviceLexicon* dl, const Batch* b, hipStream_t st, uint32_t* d_cnt, uint32_t* d_off, uint32_t* d_tmp,
+                            uint4* d_out, uint32_t* d_list, std::string& err) {
+  const uint32_t total = (uint32_t)b->n_surv, n32 = (uint32_t)b->n_input, nq32 = (uint32_t)b->nq;
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, n32 * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(d_list, 0, 4 * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
+  exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
+  ExplainArgs k{};
+  k.nq = nq32; k.total = total; k.V = dl->vocab_ent_n; k.nentries = dl->nentries; k.qw = b->qw; k.cstride = dl->cstride; k.n_out = (uint32_t)b->n_results;
+  k.NP = dl->nplanes; k.bits_ok = (dl->nsym <= 32 && !scan_mode()) ? 1 : 0;
+  k.soff = b->soff; k.r_count = b->r_count; k.q_orig = b->q_orig; k.off_orig = d_off; k.q_meta = b->q_meta; k.r_rows = b->r_rows;
+  k.q_rec = b->q_rec; k.q_rows = b->q_rows; k.q_bits = reinterpret_cast<const uint4*>(b->q_bits); k.q_cv = b->q_cv;
+  k.vocab_ent = dl->vocab_ent; k.e_rec = dl->e_rec; k.scan_rec = dl->scan_rec; k.rows = dl->rows; k.cls_planes = dl->cls_planes; k.quot = dl->quot;
+  k.w_ld = m.weights.ld; k.w_lcs = m.weights.lcs; k.w_prefix = m.weights.prefix; k.w_suffix = m.weights.suffix; k.w_case = m.weights.casew;
+  k.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;  // src/types.rs:69-73, as launch_plan.hpp
+  k.out = d_out; k.list = d_list + 4; k.list_n = d_list;
+  {
+    const int kt = ktimer_begin("k_row_measures", st);
+    hipLaunchKernelGGL(k_row_measures, dim3((total + XM_THREADS - 1) / XM_THREADS), dim3(XM_THREADS), 0, st, k);
+    ktimer_end(kt, st);
+  }
+  {
+    const int kt = ktimer_begin("k_row_measures_long", st);
+    hipLaunchKernelGGL(k_row_measures_long, dim3(std::min<uint32_t>(XM_LONG_BLOCKS, total)), dim3(64), 0, st, k);
+    ktimer_end(kt, st);
+  }
+  HIP_TRY(hipGetLastError());
+  return ANX_OK;
+}
 int batch_fetch_measures_into(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_row_measures* out, uint32_t* off, uint32_t base, std::string& err) {
   static_assert(sizeof(anx_row_measures) == sizeof(uint4), "the record leaves as one 16-byte store");
   if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
@@ -1857,7 +1888,7 @@ int batch_fetch_measures_into(const HostModel& m, const DeviceLexicon* dl, const
   if (b->n_results >= 0xFFFFFFFFull || b->n_surv >= 0xFFFFFFFFull) { err = "more than 2^32 result rows"; return ANX_ELIMIT; }
   hipStream_t st = reinterpret_cast<hipStream_t>(b->last_stream);
   if (const int rc = vocab_entry_ensure(m, dl, st, err)) return rc;
-  const uint32_t total = (uint32_t)b->n_surv, n32 = (uint32_t)n, nq32 = (uint32_t)b->nq;
+  const uint32_t total = (uint32_t)b->n_surv;
   uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr, *d_list = nullptr;
   uint4* d_out = nullptr;
   auto body = [&]() -> int {
@@ -1866,30 +1897,7 @@ int batch_fetch_measures_into(const HostModel& m, const DeviceLexicon* dl, const
     HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), scan_tmp_bytes(n)));
     HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_out), b->n_results * sizeof(uint4)));
     HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_list), ((size_t)total + 4) * sizeof(uint32_t)));  // [0]: the list's length, rows from [4] on
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, n32 * sizeof(uint32_t), st));
-    HIP_TRY(hipMemsetAsync(d_list, 0, 4 * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
-    exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
-    ExplainArgs k{};
-    k.nq = nq32; k.total = total; k.V = dl->vocab_ent_n; k.nentries = dl->nentries; k.qw = b->qw; k.cstride = dl->cstride; k.n_out = (uint32_t)b->n_results;
-    k.NP = dl->nplanes; k.bits_ok = (dl->nsym <= 32 && !scan_mode()) ? 1 : 0;
-    k.soff = b->soff; k.r_count = b->r_count; k.q_orig = b->q_orig; k.off_orig = d_off; k.q_meta = b->q_meta; k.r_rows = b->r_rows;
-    k.q_rec = b->q_rec; k.q_rows = b->q_rows; k.q_bits = reinterpret_cast<const uint4*>(b->q_bits); k.q_cv = b->q_cv;
-    k.vocab_ent = dl->vocab_ent; k.e_rec = dl->e_rec; k.scan_rec = dl->scan_rec; k.rows = dl->rows; k.cls_planes = dl->cls_planes; k.quot = dl->quot;
-    k.w_ld = m.weights.ld; k.w_lcs = m.weights.lcs; k.w_prefix = m.weights.prefix; k.w_suffix = m.weights.suffix; k.w_case = m.weights.casew;
-    k.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;  // src/types.rs:69-73, as launch_plan.hpp
-    k.out = d_out; k.list = d_list + 4; k.list_n = d_list;
-    {
-      const int kt = ktimer_begin("k_row_measures", st);
-      hipLaunchKernelGGL(k_row_measures, dim3((total + XM_THREADS - 1) / XM_THREADS), dim3(XM_THREADS), 0, st, k);
-      ktimer_end(kt, st);
-    }
-    {
-      const int kt = ktimer_begin("k_row_measures_long", st);
-      hipLaunchKernelGGL(k_row_measures_long, dim3(std::min<uint32_t>(XM_LONG_BLOCKS, total)), dim3(64), 0, st, k);
-      ktimer_end(kt, st);
-    }
-    HIP_TRY(hipGetLastError());
+    if (const int rc = measures_enqueue(m, dl, b, st, d_cnt, d_off, d_tmp, d_out, d_list, err)) return rc;
     HIP_TRY(hipMemcpyAsync(off, d_off, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out, d_out, b->n_results * sizeof(uint4), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1901,6 +1909,54 @@ int batch_fetch_measures_into(const HostModel& m, const DeviceLexicon* dl, const
   if (rc) (void)hipStreamSynchronize(st);  // nothing of this call may still be in flight when its blocks return to the pool
   for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_out, (void*)d_list}) pool_free(p);
   return rc;
+}
+
+// The same records for the weight sweep (reweigh.hip): not downloaded but placed at dst on device dst_device, beside the shard's section
+// of batch_gather_compact_via -- record r belongs to record r of that section.  Computed on the batch's own device into a pool block
+// (in place when the batch lives on dst_device), copied over as gather_compact copies a section; returns when the bytes are there.
+int batch_gather_measures(const HostModel& m, const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err) {
+  if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
+  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
+  if (!b->nq || !b->n_results) return ANX_OK;
+  if (b->n_results >= 0xFFFFFFFFull || b->n_surv >= 0xFFFFFFFFull) { err = "more than 2^32 result rows"; return ANX_ELIMIT; }
+  const size_t need = (size_t)b->n_results * sizeof(uint4), n = b->n_input;
+  if (!dst || capacity < need) { err = "measure buffer too small: " + std::to_string(need) + " bytes needed for this shard"; return ANX_ELIMIT; }
+  HIP_TRY(hipSetDevice(b->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (const int rc = vocab_entry_ensure(m, dl, st, err)) return rc;
+  const bool local = b->device == dst_device;
+  uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr, *d_list = nullptr;
+  uint4* d_tmp_out = nullptr;
+  auto body = [&]() -> int {
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), scan_tmp_bytes(n)));
+    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_list), ((size_t)b->n_surv + 4) * sizeof(uint32_t)));
+    if (!local) HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp_out), need));
+    uint4* d_out = local ? static_cast<uint4*>(dst) : d_tmp_out;
+    if (const int rc = measures_enqueue(m, dl, b, st, d_cnt, d_off, d_tmp, d_out, d_list, err)) return rc;
+    if (!local) HIP_TRY(hipMemcpyPeerAsync(dst, dst_device, d_out, b->device, need, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return ANX_OK;
+  };
+  const int rc = body();
+  if (rc) (void)hipStreamSynchronize(st);  // nothing of this call may still be in flight when its blocks return to the pool
+  for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_list, (void*)d_tmp_out}) pool_free(p);
+  return rc;
+}
+// ---- what reweigh.hip asks of this translation unit: the replica's vocabulary id -> entry table, the prefix sum and k_rank ---------------
+int replica_vocab_entries(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, std::string& err) { return vocab_entry_ensure(m, dl, st, err); }
+size_t prefix_scan_tmp_bytes(size_t n) { return scan_tmp_bytes(n); }
+int prefix_scan_enqueue(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* tmp, hipStream_t st, uint32_t* copy) { return exclusive_scan(in, n, out, tmp, st, copy); }
+void rank_rows_enqueue(const RankPlain& r, hipStream_t st, uint32_t nq, const uint32_t* soff, const SurvRow* c_rows, const uint32_t* qmaxfreq, double* t_key, DevRow* r_rows,
+                       uint32_t* r_count, uint32_t row_cap, const uint32_t* overflow) {
+  RankArgs ra{};
+  ra.cutoff_threshold = r.cutoff_threshold;
+  ra.max_matches = r.max_matches;
+  ra.freq_weight = r.freq_weight;
+  ra.have_freq = r.have_freq;
+  ra.any_variants = 0;
+  launch_rank(ra, st, nq, soff, c_rows, qmaxfreq, nullptr, t_key, r_rows, r_count, row_cap, overflow, SegRows{nullptr, 0u, nullptr});
 }
 
 int batch_fetch(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_result** rows, size_t** offs,

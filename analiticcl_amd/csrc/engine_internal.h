@@ -164,6 +164,19 @@ struct PairsOnDevice {
 int pairs_chunk_enqueue(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, const anx_params* thr, PairScratch& sc,
                         PairsOnDevice& pd, std::string& err);
 
+// ---- the weight sweep (reweigh.hip): what it uses of engine.hip's translation unit --------------------------------------------------------
+// the measures behind the rows of a shard's gathered section, on the gather's device (engine.hip, next to batch_fetch_measures_into)
+int batch_gather_measures(const HostModel& m, const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err);
+// dl->vocab_ent (vocabulary id -> lexicon entry), built on first use as anx_batch_fetch_measures builds it; waits on st
+int replica_vocab_entries(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, std::string& err);
+// the run's exclusive prefix sum (kernels_prefix.hpp): out[n + 1]; tmp: prefix_scan_tmp_bytes(n); copy: nullptr or a second array for out[0 .. n)
+size_t prefix_scan_tmp_bytes(size_t n);
+int prefix_scan_enqueue(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* tmp, hipStream_t st, uint32_t* copy);
+// launch_rank (launch_plan.hpp) for rows of a model without variant lists and without segments: k_rank<true | false> as a run launches it
+struct RankPlain { double cutoff_threshold; uint64_t max_matches; float freq_weight; int have_freq; };
+void rank_rows_enqueue(const RankPlain& r, hipStream_t st, uint32_t nq, const uint32_t* soff, const SurvRow* c_rows, const uint32_t* qmaxfreq, double* t_key, DevRow* r_rows,
+                       uint32_t* r_count, uint32_t row_cap, const uint32_t* overflow);
+
 // ---- the vocabulary table of learn mode and anx_evaluate_gold (built by learn.hip): text hash -> id -----------------------------------------
 struct LearnVocab {
   int device = -1;

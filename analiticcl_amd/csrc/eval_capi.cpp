@@ -25,6 +25,9 @@ size_t anx_export_num_shards(const anx_batch* b);
 void anx_export_shard(const anx_batch* b, size_t g, void* caller_stream, const anx::DeviceLexicon** dl, anx::Batch** sb, void** stream);
 int anx_fail(int code, const std::string& msg);
 int anx_learn_code();
+namespace anx {
+int batch_gather_measures(const HostModel& m, const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err);  // engine.hip
+}
 
 namespace {
 void release_vocab(void* p) { anx::learn_vocab_free(static_cast<anx::LearnVocab*>(p)); }
@@ -82,6 +85,15 @@ int anx_eval_gather_rows(anx_model* m, const char* const* in, const anx::PairSpa
       if (so[(size_t)g] + off_bytes + rows * (sizeof(anx_topk_record) + sizeof(uint32_t)) > so[(size_t)g + 1]) {  // (every record lies inside the shard's part of the buffer)
         rc = anx_fail(ANX_EINVAL, "evaluate: a gathered section is smaller than its rows");
         break;
+      }
+      if (out.want_measures) {  // the measures behind the section's records, computed on the shard's replica and placed beside them
+        void* mb = anx::eval_device_alloc(dev0, std::max<size_t>(rows, 1) * sizeof(anx_row_measures));
+        if (!mb) { rc = anx_fail(ANX_ENODEVICE, "out of device memory for the evaluate gather"); break; }
+        bufs.push_back(mb);
+        std::string err;
+        if (rows && sb)
+          if (const int mrc = anx::batch_gather_measures(anx_learn_host(m), sdl, sb, dev0, mb, rows * sizeof(anx_row_measures), sst, err)) { rc = anx_fail(mrc, err); break; }
+        out.sec_meas.push_back(static_cast<const anx_row_measures*>(mb));
       }
       secs.push_back(anx::LearnSection{static_cast<char*>(buf) + so[(size_t)g], ns, lo + first, idx});
       sec_rows.push_back(rows);

@@ -14,6 +14,9 @@ struct anx_eval_gather {
   std::vector<size_t> sec_rows;
   std::deque<std::vector<uint32_t>> idx_store;
   size_t batch_runs = 0;
+  // want_measures (anx_evaluate_sweep_weights): sec_meas[s] = one anx_row_measures per record of section s, beside it on the same device
+  bool want_measures = false;
+  std::vector<const anx_row_measures*> sec_meas;
   anx_eval_gather() = default;
   anx_eval_gather(const anx_eval_gather&) = delete;
   anx_eval_gather& operator=(const anx_eval_gather&) = delete;

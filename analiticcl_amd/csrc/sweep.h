@@ -25,6 +25,20 @@ int sweep_chunk_set(SweepChunk* c, const anx_params& p, bool baseline, const std
 // what score_pairs_chunk writes for the chunk's pairs
 int sweep_chunk_pairs(SweepChunk* c, anx_pair_score* pairs, std::string& err);
 void sweep_chunk_end(SweepChunk* c);
+// What anx_evaluate_sweep_weights (reweigh.hip) reads of a chunk: what begin left on the chunk's device, and the chunk's stream.
+struct SweepChunkView {
+  const HostModel* m;
+  const DeviceLexicon* dl;
+  size_t n;
+  void* stream;
+  const uint32_t *meta, *kind, *cv, *bits;  // k_enc_strings over the 2 n strings (SweepKArgs, sweep.hip)
+  const unsigned long long* sig;
+  const anx_pair_score* pair;               // [n]
+  const uint32_t* gid;                      // [n] gold id or 0xFFFFFFFF
+  const uint8_t* vflags;                    // [V]
+  uint8_t* at1;                             // [n] gold at rank 0 under set 0
+};
+void sweep_chunk_view(const SweepChunk* c, SweepChunkView* v);
 
 // anx_debug_sweep_stats: running totals since process start
 enum { SWEEP_CALLS = 0, SWEEP_CHUNKS, SWEEP_SETS, SWEEP_PAIR_PASSES, SWEEP_LOOKUPS, SWEEP_BATCH_RUNS, SWEEP_BYTES_DOWN, SWEEP_NSTATS };

@@ -433,6 +433,10 @@ int sweep_chunk_pairs(SweepChunk* c, anx_pair_score* pairs, std::string& err) {
   return ANX_OK;
 }
 
+void sweep_chunk_view(const SweepChunk* c, SweepChunkView* v) {
+  *v = SweepChunkView{c->m, c->dl, c->n, c->sc.st, c->pd.e.meta, c->pd.e.kind, c->pd.e.cv, c->pd.e.bits, c->pd.e.sig, c->pd.out, c->d_gid, c->d_vflags, c->d_at1};
+}
+
 void sweep_chunk_end(SweepChunk* c) {
   if (!c) return;
   (void)hipSetDevice(c->dl->device);  // (the scratch returns its blocks to the current device's pool)

@@ -938,6 +938,54 @@ class VariantModel:
         L.check(L.lib().anx_debug_sweep_stats(out, len(keys)))
         return {k: int(out[i]) for i, k in enumerate(keys)}
 
+    # -- weight sweep ------------------------------------------------------------------------------------
+    def evaluate_sweep_weights_arrays(self, inputs: Sequence[str], gold: Sequence[str], params_list: Sequence[SearchParameters],
+                                      weights_list: Sequence[Weights], with_records: bool = False, packed: bool = True,
+                                      chunk: Optional[int] = None):
+        """anx_evaluate_sweep_weights: evaluate_sweep_arrays for sets that also differ in the score weights -- set s is
+        (params_list[s], weights_list[s]) and its summary is what evaluate_arrays gives on a model created with weights_list[s].
+        One batch run per distinct (max_anagram_distance, max_edit_distance, stop_criterion) serves every set; the model's own
+        weights play no part.  Plain models only (no variant list, no confusable list).  Returns the summaries (SUMMARY_DTYPE), or
+        (summaries, records[P][n]) with with_records.  packed = False: the pointer form; chunk: the test hook (pointer form)."""
+        import numpy as np
+        n, P = len(inputs), len(params_list)
+        if len(gold) != n:
+            raise ValueError("evaluate_sweep_weights: inputs and gold differ in length")
+        if len(weights_list) != P:
+            raise ValueError("evaluate_sweep_weights: params_list and weights_list differ in length")
+        dt = np.dtype(self.SUMMARY_DTYPE)
+        sums = np.zeros(max(P, 1), dtype=dt)
+        sptr = sums.ctypes.data_as(C.POINTER(L.GoldSummary))
+        sets = (L.Params * max(P, 1))(*[p._c() for p in params_list])
+        ws = (L.Weights * max(P, 1))(*[w._c() for w in weights_list])
+        rec = np.zeros((max(P, 1), max(n, 1)), dtype=np.dtype(self.GOLD_DTYPE)) if with_records else None   # [P][n] set-major (n == 0: untouched)
+        optr = rec.ctypes.data_as(C.POINTER(L.GoldEval)) if with_records else None
+        if packed and chunk is None:
+            ba, bg = _pack(inputs), _pack(gold)
+            L.check(L.lib().anx_evaluate_sweep_weights_packed(self.h, ba, len(ba), bg, len(bg), n, sets, ws, P, sptr, optr))
+        else:
+            aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
+            ag = (C.c_char_p * max(n, 1))(*[_b(t) for t in gold])
+            if chunk is None:
+                L.check(L.lib().anx_evaluate_sweep_weights(self.h, aa, ag, n, sets, ws, P, sptr, optr))
+            else:
+                L.check(L.lib().anx_debug_evaluate_sweep_weights_chunk(self.h, aa, ag, n, sets, ws, P, sptr, optr, int(chunk)))
+        return (sums[:P], rec[:P, :n]) if with_records else sums[:P]
+
+    def evaluate_sweep_weights(self, inputs: Sequence[str], gold: Sequence[str], params_list: Sequence[SearchParameters],
+                               weights_list: Sequence[Weights]) -> List[dict]:
+        """evaluate_sweep_weights_arrays as one dict per set (sweep_summary), the set's weights under "weights"."""
+        sums = self.evaluate_sweep_weights_arrays(inputs, gold, params_list, weights_list)
+        return [dict(self.sweep_summary(s), weights=w.to_dict()) for s, w in zip(sums, weights_list)]
+
+    @staticmethod
+    def weight_sweep_stats() -> dict:
+        """anx_debug_weight_sweep_stats: running totals of the weight-sweep calls since process start."""
+        keys = ("calls", "chunks", "groups", "sets", "pair_passes", "batch_runs", "rows_rescored", "bytes_down")
+        out = (C.c_uint64 * len(keys))()
+        L.check(L.lib().anx_debug_weight_sweep_stats(out, len(keys)))
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
     def query_output(self, inputs: Sequence[str], params: SearchParameters, json: bool = False,
                      output_lexmatch: bool = False, first_seqnr: int = 1) -> str:
         """One device batch + the text `analiticcl query` prints for it (anx_format_query_output: the TSV lines or JSON

@@ -48,7 +48,8 @@ extern "C" {
  *    mined from string pairs (additive, nothing else changed); anx_evaluate_sweep / _packed, the struct anx_gold_summary and the hooks
  *    anx_debug_evaluate_sweep_chunk / anx_debug_sweep_stats: several parameter sets over the same gold pairs (additive); the test hooks
  *    anx_debug_lattice_decode (with the struct anx_lattice_debug) and anx_debug_portable_log (additive); the test hook
- *    anx_debug_scan_pairs and its options struct anx_debug_scan_opts: additive. */
+ *    anx_debug_scan_pairs and its options struct anx_debug_scan_opts: additive; anx_evaluate_sweep_weights / _packed and the hooks
+ *    anx_debug_evaluate_sweep_weights_chunk / anx_debug_weight_sweep_stats: sets that also differ in the score weights (additive). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -827,8 +828,8 @@ int anx_debug_evaluate_gold_chunk(anx_model *, const char *const *inputs, const 
  * out == NULL the pass downloads 624 bytes per set and chunk; the summaries of a call's chunks are added up.
  * Errors and limits are anx_evaluate_gold's (the learn lock is held for the call; confusables weighted on the host are refused), and:
  * ANX_EINVAL for n_sets == 0, n_sets > ANX_SWEEP_MAX_SETS, sets == NULL or summaries == NULL; n == 0 zeroes the summaries and returns
- * ANX_OK without a build or a device.  The weights are the model's: a sweep over weights, confusable lists or variant lists is not
- * built.  _packed: the blobs as anx_evaluate_gold_packed. */
+ * ANX_OK without a build or a device.  The weights are the model's: a sweep over weights is anx_evaluate_sweep_weights (below); one over
+ * confusable lists or variant lists is not built.  _packed: the blobs as anx_evaluate_gold_packed. */
 #define ANX_SWEEP_MAX_SETS 256
 #define ANX_GOLD_RANK_BINS 64
 typedef struct anx_gold_summary {
@@ -857,6 +858,40 @@ int anx_debug_evaluate_sweep_chunk(anx_model *, const char *const *inputs, const
  * sweep's own pass downloaded (624 per set and chunk, + 32 per pair and set with `out`, + 24 per pair with `pairs`; the batch path's
  * control reads inside anx_batch_run are not part of it). */
 int anx_debug_sweep_stats(uint64_t *out, int n);
+
+/* ---- weight sweep: sets that also differ in the five score weights, without a model, a build or a batch run per set -------------------
+ * Set s is (sets[s], weights[s]).  summaries[s] holds the integers one gets by reducing the records that
+ * anx_evaluate_gold(model_w, inputs, gold, n, &sets[s], ...) writes, model_w being a model with the same alphabet, lexicons and flags
+ * created with weights[s] instead of its own weights; out (may be NULL; [n_sets][n], set-major) is byte for byte those records,
+ * gold_score included: for rank >= 0 the row's dist_score under weights[s], else the direct pair's score under weights[s], recomputed
+ * from the pair's measures.  gained_at_1 / lost_at_1 compare with set 0, as in anx_evaluate_sweep.  The model's own weights play no part
+ * in any result.  There is no `pairs` output: its score would be the model's.
+ * How: the candidates of an input are fixed by k, d and stop_at_exact_match, their five measures are integers and max_freq is taken
+ * before the score threshold, so the sets are grouped by (max_anagram_distance, max_edit_distance, stop_at_exact_match != 0), groups in
+ * order of first appearance, and per chunk and group ONE base run of the batch path yields every instance with ld <= d (max_matches 0, no
+ * cutoff, no frequency weight, a score threshold of minus infinity) with its measures (the kernels of anx_batch_fetch_measures) on
+ * replica 0.  Per set reweigh.hip re-scores the rows under the set's weights, applies the set's score threshold, ranks them with the
+ * batch path's own k_rank under the set's max_matches / cutoff_threshold / freq_weight, classifies and reduces: no batch run per set,
+ * and a download of 624 bytes per set and chunk (+ 32 per pair with out).
+ * Errors and limits: everything anx_evaluate_sweep refuses; ANX_EINVAL for NULL sets / weights / summaries, n_sets == 0 or
+ * > ANX_SWEEP_MAX_SETS, a weight that is not finite or below 0, a set whose five weights sum to 0, and for a model whose own weights are
+ * not finite or sum to 0 (its base run would score NaN); n == 0 zeroes the summaries and returns ANX_OK without a build or a device.
+ * PLAIN MODELS ONLY: a model with a variant list or a confusable list gets ANX_EINVAL (both multiply or expand the score after the
+ * weights).  Models with frequencies are served, and a freq_weight per set.  The learn lock is held and the device pass runs on replica 0,
+ * as for anx_evaluate_gold.  More than 2^31 base rows in one chunk and group: ANX_ELIMIT. */
+int anx_evaluate_sweep_weights(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const anx_params *sets,
+                               const anx_weights *weights, size_t n_sets, anx_gold_summary *summaries, anx_gold_eval *out);
+int anx_evaluate_sweep_weights_packed(anx_model *, const char *blob_in, size_t len_in, const char *blob_gold, size_t len_gold, size_t n,
+                                      const anx_params *sets, const anx_weights *weights, size_t n_sets, anx_gold_summary *summaries,
+                                      anx_gold_eval *out);
+/* Test hook: the pointer form with a caller-chosen chunk size (1 .. 2^20 pairs). */
+int anx_debug_evaluate_sweep_weights_chunk(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const anx_params *sets,
+                                           const anx_weights *weights, size_t n_sets, anx_gold_summary *summaries, anx_gold_eval *out,
+                                           size_t chunk);
+/* Running totals of the weight-sweep calls since process start, the first min(n, 8) of: [0] calls, [1] chunks, [2] groups (base runs per
+ * chunk), [3] sets re-ranked (per chunk), [4] pair-side passes, [5] batch runs, [6] base rows re-scored (rows x sets), [7] bytes the
+ * pass downloaded (624 per set and chunk, + 32 per pair and set with `out`). */
+int anx_debug_weight_sweep_stats(uint64_t *out, int n);
 
 /* ---- anx_mine_confusables: confusable patterns from (observed, correct) string pairs ---------------------------------------------------
  * For every pair (a[i], b[i]) the change sites of shortest_edit_script(a[i], b[i]) -- a site is a maximal run of consecutive non-`=`
