@@ -27,15 +27,6 @@
 
 namespace anx {
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      err = std::string(#expr) + ": " + hipGetErrorString(_e);                                 \
-      return ANX_ENODEVICE;                                                                    \
-    }                                                                                          \
-  } while (0)
-
 #include "kernels_common.hpp"
 
 struct EncArgs {
@@ -78,30 +69,8 @@ __device__ inline void load_window(const uint8_t* __restrict__ blob, uint32_t po
 #pragma unroll
   for (uint32_t x = 0; x < 4u; ++x) r[x] = __builtin_amdgcn_alignbyte(dw[x + 1], dw[x], sh);
 }
-// dword w of the count vector (4 symbol slots, a byte each) of a string whose counts are all <= 4, from its thermometer planes
-__device__ inline uint32_t cv_word_of_planes(const uint4 pl, uint32_t w) {
-  uint32_t word = 0;
-  if (w < 8u) {
-#pragma unroll
-    for (uint32_t y = 0; y < 4u; ++y) {
-      const uint32_t sl = 4u * w + y;
-      word |= (((pl.x >> sl) & 1u) + ((pl.y >> sl) & 1u) + ((pl.z >> sl) & 1u) + ((pl.w >> sl) & 1u)) << (8u * y);
-    }
-  }
-  return word;
-}
+// (cv_word_of_planes and dev_clamp_threshold: kernels_common.hpp -- the gold classification reads count vectors and clamps the same way)
 __device__ inline int dev_u8len(uint32_t c) { return c < 0x80u ? 1 : (c >> 5) == 0x6u ? 2 : (c >> 4) == 0xEu ? 3 : (c >> 3) == 0x1Eu ? 4 : 1; }
-
-__device__ inline int dev_clamp_threshold(const anx_threshold& t, int len, int absolute_max) {  // host_model.cpp clamp_threshold
-  if (t.kind == ANX_RATIO || t.kind == ANX_RATIO_WITH_LIMIT) {
-    const float v = floorf((float)len * t.ratio);
-    const int x = v < 0.0f ? 0 : v > 255.0f ? 255 : (int)v;
-    const int lim = t.kind == ANX_RATIO ? absolute_max : (int)t.value;
-    return x < lim ? x : lim;
-  }
-  const int half = len / 2 < 255 ? len / 2 : 255;
-  return (int)t.value < half ? (int)t.value : half;
-}
 
 // STAGE (the small call): the blob is pinned HOST memory; the block first copies the bytes of its 256 strings into LDS with coalesced
 // 16-byte loads (one burst over PCIe instead of a dword read per lane and window) and the lanes walk them there.  Strings of at most

@@ -31,15 +31,6 @@
 
 namespace anx {
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      err = std::string(#expr) + ": " + hipGetErrorString(_e);                                 \
-      return ANX_ENODEVICE;                                                                    \
-    }                                                                                          \
-  } while (0)
-
 #include "kernels_common.hpp"
 #include "kernels_swar.hpp"
 #include "kernels_scan.hpp"

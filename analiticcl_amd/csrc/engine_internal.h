@@ -5,6 +5,16 @@
 #include "engine.h"
 #include "sig_hash.h"
 
+// in a function that returns a code and has a std::string err
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t _e = (expr);                                                                    \
+    if (_e != hipSuccess) {                                                                    \
+      err = std::string(#expr) + ": " + hipGetErrorString(_e);                                 \
+      return ANX_ENODEVICE;                                                                    \
+    }                                                                                          \
+  } while (0)
+
 namespace anx {
 
 // a tile probes the hash table instead of walking its window when the ball is cheaper (a probe step costs ~3 walk steps) and
@@ -122,24 +132,36 @@ int conf_launch_pairs(const HostModel& m, const DeviceLexicon* dl, hipStream_t s
 // pairs_encode_launch with the caller's thresholds behind meta's k / d bits (anx_evaluate_gold reads them there)
 int pairs_encode_launch_thr(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n,
                             const anx_params& thr, hipStream_t st, std::string& err);
-// pool blocks and pinned host blocks of one call released together, and the private stream of the call
-struct PairScratch {
-  std::vector<void*> blocks, host;
-  int device;
-  hipStream_t st;
-  explicit PairScratch(int dev) : device(dev), st(encoder_stream_acquire(dev)) {}
-  PairScratch(const PairScratch&) = delete;
-  PairScratch& operator=(const PairScratch&) = delete;
+// Pool blocks that go back to the current device's pool together.  The owner calls release() once nothing enqueued may still use them
+// (it waits for its stream first): a call (PairScratch), a group of the weight sweep, a set of the sweep.
+struct PoolBlocks {
+  std::vector<void*> v;
   template <typename T>
   int get(T** p, size_t count, std::string& err) {
     void* q = nullptr;
     const size_t bytes = count * sizeof(T) < 16 ? 16 : count * sizeof(T);
     const hipError_t e = pool_malloc(&q, bytes);
     if (e != hipSuccess) { err = std::string("pool_malloc: ") + hipGetErrorString(e); return ANX_ENODEVICE; }
-    blocks.push_back(q);
+    v.push_back(q);
     *p = static_cast<T*>(q);
     return ANX_OK;
   }
+  void release() {
+    for (void* q : v) pool_free(q);
+    v.clear();
+  }
+};
+// pool blocks and pinned host blocks of one call released together, and the private stream of the call
+struct PairScratch {
+  PoolBlocks blocks;
+  std::vector<void*> host;
+  int device;
+  hipStream_t st;
+  explicit PairScratch(int dev) : device(dev), st(encoder_stream_acquire(dev)) {}
+  PairScratch(const PairScratch&) = delete;
+  PairScratch& operator=(const PairScratch&) = delete;
+  template <typename T>
+  int get(T** p, size_t count, std::string& err) { return blocks.get(p, count, err); }
   void* pinned(size_t bytes) {
     void* q = host_result_alloc(bytes < 16 ? 16 : bytes);
     if (q) host.push_back(q);
@@ -148,7 +170,7 @@ struct PairScratch {
   // nothing enqueued by this call may still use the blocks when they return to their pools (an error path has not waited yet)
   ~PairScratch() {
     (void)hipStreamSynchronize(st);
-    for (void* q : blocks) pool_free(q);
+    blocks.release();
     for (void* q : host) host_result_free(q);
     encoder_stream_release(device, st);
   }

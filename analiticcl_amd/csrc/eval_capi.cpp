@@ -15,10 +15,10 @@
 #include "engine.h"
 #include "eval_gather.h"
 #include "host_model.h"
+#include "pair_spans.h"
 
 anx::HostModel& anx_learn_host(anx_model* m);
 const anx::DeviceLexicon* anx_replica_of(const anx_model* m, size_t i);
-void** anx_learn_vocab_slot(anx_model* m, void (*release)(void*));
 std::mutex& anx_learn_mutex();
 bool anx_batch_host_rescored(const anx_batch* b);
 size_t anx_export_num_shards(const anx_batch* b);
@@ -28,10 +28,6 @@ int anx_learn_code();
 namespace anx {
 int batch_gather_measures(const HostModel& m, const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err);  // engine.hip
 }
-
-namespace {
-void release_vocab(void* p) { anx::learn_vocab_free(static_cast<anx::LearnVocab*>(p)); }
-}  // namespace
 
 // the ranked rows of the chunk's inputs as sections on replica 0's device (inputs relative to the chunk): eval_gather.h
 int anx_eval_gather_rows(anx_model* m, const char* const* in, const anx::PairSpan* sa, size_t n, const anx_params* p, anx_eval_gather& out) {
@@ -110,7 +106,7 @@ int evaluate_chunk(anx_model* m, const char* const* in, const anx::PairSpan* sa,
   anx_eval_gather rows;
   if (int rc = anx_eval_gather_rows(m, in, sa, n, p, rows)) return rc;
   std::string err;
-  anx::LearnVocab** vocab = reinterpret_cast<anx::LearnVocab**>(anx_learn_vocab_slot(m, release_vocab));
+  anx::LearnVocab** vocab = anx::learn_vocab_slot(m);
   const int rc = anx::evaluate_chunk(anx_learn_host(m), anx_replica_of(m, 0), vocab, sa, sg, n, *p, rows.secs, rows.sec_rows, out, pairs, err);
   return rc ? anx_fail(rc, err) : ANX_OK;
 }
@@ -143,25 +139,9 @@ int pointer_call(anx_model* m, const char* const* a, const char* const* g, size_
   bool run;
   if (int rc = check_call(m, a, g, n, p, out, &run); rc || !run) return rc;
   if (chunk < 1 || chunk > anx::PAIRS_CHUNK) return anx_fail(ANX_EINVAL, "evaluate: chunk size outside 1 .. 2^20");
-  std::vector<anx::PairSpan> sa(n), sg(n);
-  for (size_t i = 0; i < n; ++i) {
-    if (!a[i] || !g[i]) return anx_fail(ANX_EINVAL, "NULL string");
-    sa[i] = anx::PairSpan{a[i], strlen(a[i])};
-    sg[i] = anx::PairSpan{g[i], strlen(g[i])};
-  }
+  std::vector<anx::PairSpan> sa, sg;
+  if (!anx::spans_of_pointers(a, n, sa) || !anx::spans_of_pointers(g, n, sg)) return anx_fail(ANX_EINVAL, "NULL string");
   return run_call(m, a, sa, sg, p, out, pairs, chunk);
-}
-// the first n NUL-terminated spans of blob[0, len)
-bool spans_of(const char* blob, size_t len, size_t n, std::vector<anx::PairSpan>& out) {
-  out.resize(n);
-  size_t pos = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const char* z = pos < len ? static_cast<const char*>(memchr(blob + pos, 0, len - pos)) : nullptr;
-    if (!z) return false;
-    out[i] = anx::PairSpan{blob + pos, (size_t)(z - (blob + pos))};
-    pos = (size_t)(z - blob) + 1;
-  }
-  return true;
 }
 }  // namespace
 
@@ -180,7 +160,7 @@ int anx_evaluate_gold_packed(anx_model* m, const char* blob_in, size_t len_in, c
   if (int rc = check_call(m, blob_in, blob_gold, n, p, out, &run); rc || !run) return rc;
   if (len_in >= ((size_t)1 << 32) || len_gold >= ((size_t)1 << 32)) return anx_fail(ANX_ELIMIT, "packed pairs exceed 4 GB per blob: split the call");
   std::vector<anx::PairSpan> sa, sg;
-  if (!spans_of(blob_in, len_in, n, sa) || !spans_of(blob_gold, len_gold, n, sg)) return anx_fail(ANX_EINVAL, "packed inputs hold fewer strings than announced");
+  if (!anx::spans_of(blob_in, len_in, n, sa) || !anx::spans_of(blob_gold, len_gold, n, sg)) return anx_fail(ANX_EINVAL, "packed inputs hold fewer strings than announced");
   return run_call(m, nullptr, sa, sg, p, out, pairs, anx::PAIRS_CHUNK);  // (the spans lie back to back, each behind its NUL byte)
 }
 }  // extern "C"

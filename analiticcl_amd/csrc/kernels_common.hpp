@@ -277,3 +277,27 @@ struct Batch {
 
 typedef const __attribute__((address_space(4))) uint32_t* cptr_u32;  // constant address space: s_load
 
+// ---- what the encoder (encode.hip) and the gold classification (kernels_gold.hpp) both compute per string --------------------------------
+// dword w of the count vector (4 symbol slots, a byte each) of a string whose counts are all <= 4, from its thermometer planes
+__device__ inline uint32_t cv_word_of_planes(const uint4 pl, uint32_t w) {
+  uint32_t word = 0;
+  if (w < 8u) {
+#pragma unroll
+    for (uint32_t y = 0; y < 4u; ++y) {
+      const uint32_t sl = 4u * w + y;
+      word |= (((pl.x >> sl) & 1u) + ((pl.y >> sl) & 1u) + ((pl.z >> sl) & 1u) + ((pl.w >> sl) & 1u)) << (8u * y);
+    }
+  }
+  return word;
+}
+__device__ inline int dev_clamp_threshold(const anx_threshold& t, int len, int absolute_max) {  // host_model.cpp clamp_threshold
+  if (t.kind == ANX_RATIO || t.kind == ANX_RATIO_WITH_LIMIT) {
+    const float v = floorf((float)len * t.ratio);
+    const int x = v < 0.0f ? 0 : v > 255.0f ? 255 : (int)v;
+    const int lim = t.kind == ANX_RATIO ? absolute_max : (int)t.value;
+    return x < lim ? x : lim;
+  }
+  const int half = len / 2 < 255 ? len / 2 : 255;
+  return (int)t.value < half ? (int)t.value : half;
+}
+

@@ -35,15 +35,6 @@
 
 namespace anx {
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      err = std::string(#expr) + ": " + hipGetErrorString(_e);                                 \
-      return ANX_ENODEVICE;                                                                    \
-    }                                                                                          \
-  } while (0)
-
 namespace {
 constexpr uint32_t LF_NONE = 0xFFFFFFFFu;     // input without rows: no id
 constexpr uint32_t LF_PENDING = 0xFFFFFFFEu;  // input with rows whose string is not in the vocabulary (yet)

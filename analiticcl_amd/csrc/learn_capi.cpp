@@ -12,9 +12,9 @@
 
 #include "engine.h"
 #include "host_model.h"
+#include "pair_spans.h"
 
 anx::HostModel& anx_learn_host(anx_model* m);
-void** anx_learn_vocab_slot(anx_model* m, void (*release)(void*));
 std::mutex& anx_learn_mutex();
 uint64_t anx_learn_host_fold(anx_model* m, const char* const* text, size_t n, const anx_result* rows, const size_t* off, double* ms);
 void anx_learn_count_device_fold(uint64_t rows, uint64_t refs);
@@ -28,7 +28,6 @@ int anx_learn_code();
 namespace {
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-void release_vocab(void* p) { anx::learn_vocab_free(static_cast<anx::LearnVocab*>(p)); }
 
 // the inputs packed for the device fold (each followed by a NUL byte)
 int pack_offsets(const char* const* utf8, size_t n, std::vector<uint32_t>& soff) {
@@ -99,7 +98,7 @@ int strict_device(anx_model* m, const char* const* utf8, size_t n, const anx_par
   ms[0] = ms_since(t0);
   const auto t1 = Clock::now();
   std::string err;
-  anx::LearnVocab** vocab = reinterpret_cast<anx::LearnVocab**>(anx_learn_vocab_slot(m, release_vocab));
+  anx::LearnVocab** vocab = anx::learn_vocab_slot(m);
   const int rc = anx::learn_fold_device(anx_learn_host(m), dev0, vocab, blob.data(), soff.data(), n, secs, rows, fold, err);
   release();
   ms[1] = ms_since(t1);
@@ -213,7 +212,7 @@ int anx_debug_learn_fold_rows(anx_model* m, const char* const* utf8, size_t n, c
   }
   std::string err;
   anx::LearnFold fold;
-  anx::LearnVocab** vocab = reinterpret_cast<anx::LearnVocab**>(anx_learn_vocab_slot(m, release_vocab));
+  anx::LearnVocab** vocab = anx::learn_vocab_slot(m);
   const int rc = anx::learn_fold_device(host, dev0, vocab, blob.data(), soff.data(), n, secs, offsets[n], fold, err);
   release();
   if (rc) return anx_learn_fail(rc, err);

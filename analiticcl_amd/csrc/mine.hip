@@ -33,15 +33,6 @@
 
 namespace anx {
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      err = std::string(#expr) + ": " + hipGetErrorString(_e);                                 \
-      return ANX_ENODEVICE;                                                                    \
-    }                                                                                          \
-  } while (0)
-
 #include "kernels_common.hpp"  // (DeviceLexicon)
 
 namespace {
@@ -358,7 +349,7 @@ int mine_chunk_run(const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b
     for (size_t i = 0; i < n; ++i) host_pairs[i] = (uint32_t)i;
     return ANX_OK;
   }
-  sc.blocks.push_back(wk);
+  sc.blocks.v.push_back(wk);
   const int bits = switches().mine_hash_bits;
   MineArgs A{};
   A.n = (uint32_t)n; A.context = context; A.anchors = anchors ? 1u : 0u;

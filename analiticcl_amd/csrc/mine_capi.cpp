@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "mine.h"
+#include "pair_spans.h"
 
 const anx::HostModel& anx_host_of(const anx_model* m);
 const anx::DeviceLexicon* anx_replica_of(const anx_model* m, size_t i);
@@ -303,17 +304,6 @@ int check_call(const anx_model* m, const void* a, const void* b, size_t n, const
   }
   return ANX_OK;
 }
-bool spans_of(const char* blob, size_t len, size_t n, std::vector<anx::PairSpan>& out) {
-  out.resize(n);
-  size_t pos = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const char* z = pos < len ? static_cast<const char*>(memchr(blob + pos, 0, len - pos)) : nullptr;
-    if (!z) return false;
-    out[i] = anx::PairSpan{blob + pos, (size_t)(z - (blob + pos))};
-    pos = (size_t)(z - blob) + 1;
-  }
-  return true;
-}
 }  // namespace
 
 extern "C" {
@@ -323,12 +313,8 @@ void anx_default_mine_params(anx_mine_params* out) {
 int anx_mine_confusables(const anx_model* m, const char* const* a, const char* const* b, const uint32_t* count, size_t n, const anx_mine_params* p,
                          anx_mine_result** out) {
   if (int rc = check_call(m, a, b, n, p, out)) return rc;
-  std::vector<anx::PairSpan> sa(n), sb(n);
-  for (size_t i = 0; i < n; ++i) {
-    if (!a[i] || !b[i]) return anx_fail(ANX_EINVAL, "NULL string");
-    sa[i] = anx::PairSpan{a[i], strlen(a[i])};
-    sb[i] = anx::PairSpan{b[i], strlen(b[i])};
-  }
+  std::vector<anx::PairSpan> sa, sb;
+  if (!anx::spans_of_pointers(a, n, sa) || !anx::spans_of_pointers(b, n, sb)) return anx_fail(ANX_EINVAL, "NULL string");
   return run(m, sa, sb, count, p, out);
 }
 int anx_mine_confusables_packed(const anx_model* m, const char* blob_a, size_t len_a, const char* blob_b, size_t len_b, const uint32_t* count, size_t n,
@@ -336,7 +322,7 @@ int anx_mine_confusables_packed(const anx_model* m, const char* blob_a, size_t l
   if (int rc = check_call(m, blob_a, blob_b, n, p, out)) return rc;
   if (len_a >= ((size_t)1 << 32) || len_b >= ((size_t)1 << 32)) return anx_fail(ANX_ELIMIT, "packed pairs exceed 4 GB per blob: split the call");
   std::vector<anx::PairSpan> sa, sb;
-  if (!spans_of(blob_a, len_a, n, sa) || !spans_of(blob_b, len_b, n, sb)) return anx_fail(ANX_EINVAL, "packed inputs hold fewer strings than announced");
+  if (!anx::spans_of(blob_a, len_a, n, sa) || !anx::spans_of(blob_b, len_b, n, sb)) return anx_fail(ANX_EINVAL, "packed inputs hold fewer strings than announced");
   return run(m, sa, sb, count, p, out);
 }
 void anx_mine_result_free(anx_mine_result* r) {

@@ -41,15 +41,6 @@
 
 namespace anx {
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      err = std::string(#expr) + ": " + hipGetErrorString(_e);                                 \
-      return ANX_ENODEVICE;                                                                    \
-    }                                                                                          \
-  } while (0)
-
 #include "kernels_common.hpp"
 
 struct PairKArgs {
@@ -431,7 +422,7 @@ int score_pairs_chunk(const HostModel& m, const DeviceLexicon* dl, const PairSpa
       (void)hipGetLastError();
       on_device = false;  // (same weights from the host)
     } else {
-      sc.blocks.push_back(wk);
+      sc.blocks.v.push_back(wk);
       cr.work = static_cast<uint32_t*>(wk);
       char* tmp = nullptr;
       cr.sort_tmp_bytes = conf_pairs_sort_tmp_bytes((uint32_t)n);

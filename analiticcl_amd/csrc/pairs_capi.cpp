@@ -14,6 +14,7 @@
 
 #include "engine.h"
 #include "host_model.h"
+#include "pair_spans.h"
 
 const anx::HostModel& anx_host_of(const anx_model* m);
 const anx::DeviceLexicon* anx_replica_of(const anx_model* m, size_t i);
@@ -42,33 +43,16 @@ int run_chunks(const anx_model* m, const std::vector<anx::PairSpan>& a, const st
   }
   return ANX_OK;
 }
-// the first n NUL-terminated spans of blob[0, len)
-bool spans_of(const char* blob, size_t len, size_t n, std::vector<anx::PairSpan>& out);
 int pointer_call(const anx_model* m, const char* const* a, const char* const* b, size_t n, anx_pair_score* out, double* weight) {
-  std::vector<anx::PairSpan> sa(n), sb(n);
-  for (size_t i = 0; i < n; ++i) {
-    if (!a[i] || !b[i]) return anx_fail(ANX_EINVAL, "NULL string");
-    sa[i] = anx::PairSpan{a[i], strlen(a[i])};
-    sb[i] = anx::PairSpan{b[i], strlen(b[i])};
-  }
+  std::vector<anx::PairSpan> sa, sb;
+  if (!anx::spans_of_pointers(a, n, sa) || !anx::spans_of_pointers(b, n, sb)) return anx_fail(ANX_EINVAL, "NULL string");
   return run_chunks(m, sa, sb, out, weight);
 }
 int packed_call(const anx_model* m, const char* blob_a, size_t len_a, const char* blob_b, size_t len_b, size_t n, anx_pair_score* out, double* weight) {
   if (len_a >= ((size_t)1 << 32) || len_b >= ((size_t)1 << 32)) return anx_fail(ANX_ELIMIT, "packed pairs exceed 4 GB per blob: split the call");
   std::vector<anx::PairSpan> sa, sb;
-  if (!spans_of(blob_a, len_a, n, sa) || !spans_of(blob_b, len_b, n, sb)) return anx_fail(ANX_EINVAL, "packed inputs hold fewer strings than announced");
+  if (!anx::spans_of(blob_a, len_a, n, sa) || !anx::spans_of(blob_b, len_b, n, sb)) return anx_fail(ANX_EINVAL, "packed inputs hold fewer strings than announced");
   return run_chunks(m, sa, sb, out, weight);
-}
-bool spans_of(const char* blob, size_t len, size_t n, std::vector<anx::PairSpan>& out) {
-  out.resize(n);
-  size_t pos = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const char* z = pos < len ? static_cast<const char*>(memchr(blob + pos, 0, len - pos)) : nullptr;
-    if (!z) return false;
-    out[i] = anx::PairSpan{blob + pos, (size_t)(z - (blob + pos))};
-    pos = (size_t)(z - blob) + 1;
-  }
-  return true;
 }
 }  // namespace
 

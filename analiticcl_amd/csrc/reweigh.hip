@@ -7,11 +7,12 @@
 // no cutoff, no frequency weight and a score threshold nothing falls below -- yields every instance with ld <= d, and explain's kernels
 // (kernels_explain.hpp) their measures.  From there, on the chunk's device:
 //   once per group (reweigh_group_begin):
-//     k_rw_base     : flat over a section's rows, the lanes on consecutive 16-byte records: the row's pair by the binary search of
-//                     k_eval_rows, vocab_id -> entry (DeviceLexicon::vocab_ent) -> {entry order, absolute frequency}; keeps 16 bytes of
+//     k_rw_base     : flat over a section's rows, the lanes on consecutive 16-byte records: the row's pair by the binary search
+//                     k_eval_rows runs (gold_section_slot, kernels_gold.hpp), vocab_id -> entry (DeviceLexicon::vocab_ent) -> {entry order, absolute frequency}; keeps 16 bytes of
 //                     {pair, order, frequency, vocabulary id} and 8 bytes of packed measures per row, and the pair's largest frequency
 //                     with one atomicMax per run of equal pairs in a wave
-//     k_rw_pre      : a lane per pair: the reasons that do not depend on the weights (STATUS .. EDIT) and the clamped k / d, one word
+//     k_rw_pre      : a lane per pair: the reasons that do not depend on the weights (STATUS .. EDIT: gold_pre_reason, the function
+//                     k_eval_classify and k_sweep_classify call) and the clamped k / d, one word
 //   once per set (reweigh_group_set):
 //     k_rw_score    : flat over the rows: the f64 score under the set's weights (score_finish restated term by term, as
 //                     kernels_explain.hpp xm_score: same association, w_sum in launch_plan.hpp's order, the w_sum == 1.0 shortcut,
@@ -21,8 +22,9 @@
 //     k_rw_fill     : the kept rows as SurvRow {score, order << 20, vocabulary id, frequency, no via} at soff[pair] + cursor
 //     k_rank        : engine.hip's own kernel through launch_rank (rank_rows_enqueue): sort, crop, tie rule and cutoff are NOT restated
 //     k_rw_classify : a lane per pair: rank of gold, n_results and the top row from the pair's ranked rows, THRESHOLD from the direct
-//                     pair's score under the set's weights, the record when asked for, then k_sweep_classify's reduction (LDS
-//                     counters, one 64-bit integer atomic per non-zero counter and block; no float atomics)
+//                     pair's score under the set's weights, the record when asked for (gold_store_record), then the reduction
+//                     k_sweep_classify runs (gold_summary_begin / _end: LDS counters, one 64-bit integer atomic per non-zero
+//                     counter and block; no float atomics)
 //   and one download of 624 bytes per set (+ 32 n with the records).  No host round trip between a set's first launch and its download.
 // Every append is bounds-checked against the scan's own offsets and the row buffer.
 #include <hip/hip_runtime.h>
@@ -39,27 +41,11 @@
 
 namespace anx {
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      err = std::string(#expr) + ": " + hipGetErrorString(_e);                                 \
-      return ANX_ENODEVICE;                                                                    \
-    }                                                                                          \
-  } while (0)
-
 #include "kernels_common.hpp"
+#include "kernels_gold.hpp"
+#include "gold_host.hpp"
 
 namespace {
-constexpr uint32_t RW_NONE = 0xFFFFFFFFu;
-constexpr int RW_BLOCK = 256;
-constexpr uint32_t RW_LATER = 0xFFu;  // k_rw_pre: the pair passes every weight-independent test (THRESHOLD or CROPPED, per set)
-constexpr uint32_t RW_COUNTERS = sizeof(anx_gold_summary) / sizeof(uint64_t);  // 78, in the struct's order (as sweep.hip)
-constexpr uint32_t RW_CELLS32 = RW_COUNTERS - 2;
-constexpr uint32_t RW_N = 0, RW_KNOWN = 1, RW_REASON = 2, RW_HIST = 10, RW_RR = 74, RW_NRES = 75, RW_GAINED = 76, RW_LOST = 77;
-static_assert(RW_COUNTERS == 78 && RW_HIST + ANX_GOLD_RANK_BINS == RW_RR, "the counters follow anx_gold_summary's layout");
-inline unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>(1, (n + RW_BLOCK - 1) / RW_BLOCK); }
-
 std::atomic<uint64_t> g_stats[RW_NSTATS];
 }  // namespace
 
@@ -102,8 +88,8 @@ __device__ __forceinline__ RwRun rw_run(uint32_t key) {
   return RwRun{start, end, ((2ull << end) - 1ull) & ~((1ull << start) - 1ull)};
 }
 
-// one compact export section of the base run with its measures; inputs (= pairs of the chunk) lo + j, or idx[j]
-struct RwSection { const anx_topk_record* rec; const uint4* meas; const uint32_t* off; const uint32_t* idx; uint32_t n, lo, rows; };
+// one compact export section of the base run with the measures of its rows
+struct RwSection : GoldSection { const uint4* meas; };
 
 struct RwBaseArgs {
   RwSection sec;
@@ -117,23 +103,17 @@ struct RwBaseArgs {
   uint2* meas;                   // [R] {ld | lcs << 8 | prefix << 16 | suffix << 24, len_input | samecase << 8}
   uint32_t* maxf;                // [n] largest frequency of the pair's rows
 };
-__global__ __launch_bounds__(RW_BLOCK) void k_rw_base(RwBaseArgs k) {
-  const uint32_t r = blockIdx.x * RW_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(GOLD_BLOCK) void k_rw_base(RwBaseArgs k) {
+  const uint32_t r = blockIdx.x * GOLD_BLOCK + threadIdx.x;
   const RwSection& sec = k.sec;
-  uint32_t pair = RW_NONE, freq = 0u;
+  uint32_t pair = GOLD_NONE, freq = 0u;
   const bool inside = r < sec.rows && sec.n != 0u && k.row0 + r < k.R;
   if (inside) {
-    // the last j in [0, sec.n) with off[j] <= r: inputs without rows share their offset with the next one and are stepped over
-    uint32_t lo = 0, hi = sec.n - 1u;
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi + 1u) >> 1;
-      if (sec.off[mid] <= r) lo = mid;
-      else hi = mid - 1u;
-    }
+    const uint32_t lo = gold_section_slot(sec, r);
     const uint32_t i = sec.idx ? sec.idx[lo] : sec.lo + lo;
     const uint32_t vocab = sec.rec[r].vocab_id;
-    uint32_t e = vocab < k.V ? k.vocab_ent[vocab] : RW_NONE;
-    uint4 inf = make_uint4(RW_NONE, 0u, 0u, vocab);
+    uint32_t e = vocab < k.V ? k.vocab_ent[vocab] : GOLD_NONE;
+    uint4 inf = make_uint4(GOLD_NONE, 0u, 0u, vocab);
     uint2 mm = make_uint2(0u, 0u);
     if (sec.off[lo] <= r && r < sec.off[lo + 1u] && i < k.n && e < k.nentries) {  // (a ranked row always has an entry)
       const EntRec er = k.ent_rec[e];
@@ -155,7 +135,7 @@ __global__ __launch_bounds__(RW_BLOCK) void k_rw_base(RwBaseArgs k) {
     const uint32_t u = (uint32_t)__shfl_up((int)mf, o);
     if (lane >= run.start + o) mf = max(mf, u);
   }
-  if (lane == run.end && pair != RW_NONE && mf) atomicMax(&k.maxf[pair], mf);
+  if (lane == run.end && pair != GOLD_NONE && mf) atomicMax(&k.maxf[pair], mf);
 }
 
 struct RwSetArgs {
@@ -171,9 +151,9 @@ struct RwSetArgs {
   uint4* c_rows;                 // [row_cap] SurvRow as two 16-byte words
   uint32_t row_cap;
 };
-__global__ __launch_bounds__(RW_BLOCK) void k_rw_score(RwSetArgs k) {
-  const uint32_t r = blockIdx.x * RW_BLOCK + threadIdx.x;
-  uint32_t pair = RW_NONE;
+__global__ __launch_bounds__(GOLD_BLOCK) void k_rw_score(RwSetArgs k) {
+  const uint32_t r = blockIdx.x * GOLD_BLOCK + threadIdx.x;
+  uint32_t pair = GOLD_NONE;
   bool keep = false;
   if (r < k.R) {
     pair = k.info[r].x;
@@ -182,17 +162,17 @@ __global__ __launch_bounds__(RW_BLOCK) void k_rw_score(RwSetArgs k) {
       const uint2 m = k.meas[r];
       s = rw_score(k.w, m.y & 0xFFu, m.x & 0xFFu, (m.x >> 8) & 0xFFu, (m.x >> 16) & 0xFFu, m.x >> 24, (m.y >> 8) & 1u);
       keep = s >= k.score_threshold;  // src/lib.rs:1475
-    } else pair = RW_NONE;
+    } else pair = GOLD_NONE;
     k.score[r] = s;
   }
   const RwRun run = rw_run(pair);
   const uint32_t c = (uint32_t)__popcll(__ballot(keep) & run.lanes);
-  if ((threadIdx.x & 63u) == run.end && pair != RW_NONE && c) atomicAdd(&k.cnt[pair], c);
+  if ((threadIdx.x & 63u) == run.end && pair != GOLD_NONE && c) atomicAdd(&k.cnt[pair], c);
 }
-__global__ __launch_bounds__(RW_BLOCK) void k_rw_fill(RwSetArgs k) {
-  const uint32_t r = blockIdx.x * RW_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(GOLD_BLOCK) void k_rw_fill(RwSetArgs k) {
+  const uint32_t r = blockIdx.x * GOLD_BLOCK + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
-  uint4 inf = make_uint4(RW_NONE, 0u, 0u, 0u);
+  uint4 inf = make_uint4(GOLD_NONE, 0u, 0u, 0u);
   double s = 0.0;
   bool keep = false;
   if (r < k.R) {
@@ -200,7 +180,7 @@ __global__ __launch_bounds__(RW_BLOCK) void k_rw_fill(RwSetArgs k) {
     if (inf.x < k.n) {
       s = k.score[r];
       keep = s >= k.score_threshold;  // (the test k_rw_score counted with, on the value it stored)
-    } else inf.x = RW_NONE;
+    } else inf.x = GOLD_NONE;
   }
   const RwRun run = rw_run(inf.x);
   const unsigned long long km = __ballot(keep) & run.lanes;
@@ -212,96 +192,24 @@ __global__ __launch_bounds__(RW_BLOCK) void k_rw_fill(RwSetArgs k) {
   if (pos >= k.soff[inf.x + 1u] || pos >= k.row_cap) return;  // (cannot happen: the offsets are the scan of these very counts)
   const unsigned long long sb = (unsigned long long)__double_as_longlong(s), ord = (unsigned long long)inf.y << 20;
   k.c_rows[2 * (size_t)pos] = make_uint4((uint32_t)sb, (uint32_t)(sb >> 32), (uint32_t)ord, (uint32_t)(ord >> 32));
-  k.c_rows[2 * (size_t)pos + 1] = make_uint4(inf.w, inf.z, RW_NONE, 0u);  // {vocab, freq, no via, pad}
+  k.c_rows[2 * (size_t)pos + 1] = make_uint4(inf.w, inf.z, GOLD_NONE, 0u);  // {vocab, freq, no via, pad}
 }
 
-// ---- the direct pairs: the reasons that do not depend on the weights (k_sweep_classify's tests, sweep.hip, restated) ---------------------
+// ---- the direct pairs: the reasons that do not depend on the weights ----------------------------------------------------------------------
 struct RwPreArgs {
-  uint32_t n;
-  const uint32_t *meta, *kind, *cv;
-  const uint4* bits;
-  const unsigned long long* sig;
-  int NP;
-  const anx_pair_score* pair;
-  const uint32_t* gid;
-  const uint8_t* vflags;
-  uint32_t V;
-  const uint4* sigtab;
-  const uint32_t* siglen_begin;
-  const uint32_t* cls_planes;
-  uint32_t cstride;
+  GoldPairSide side;             // meta: k_enc_strings ran without thresholds
   anx_threshold kth, dth;
-  int stop_exact;
-  uint32_t* pre;                 // [n] reason (RW_LATER: none of them) | k << 8 | d << 16
+  uint32_t* pre;                 // [n] reason (GOLD_LATER: none of them; THRESHOLD or CROPPED, per set) | k << 8 | d << 16
 };
-// host_model.cpp clamp_threshold, as encode.hip's dev_clamp_threshold
-__device__ inline uint32_t rw_clamp_threshold(const anx_threshold& t, int len, int absolute_max) {
-  if (t.kind == ANX_RATIO || t.kind == ANX_RATIO_WITH_LIMIT) {
-    const float v = floorf((float)len * t.ratio);
-    const int x = v < 0.0f ? 0 : v > 255.0f ? 255 : (int)v;
-    const int lim = t.kind == ANX_RATIO ? absolute_max : (int)t.value;
-    return (uint32_t)(x < lim ? x : lim);
-  }
-  const int half = len / 2 < 255 ? len / 2 : 255;
-  return (uint32_t)((int)t.value < half ? (int)t.value : half);
-}
-// dword w of the count vector (4 symbol slots, a byte each): from cv, or (counts all <= 4) from the thermometer planes (as encode.hip)
-__device__ inline uint32_t rw_cv_word(const RwPreArgs& k, uint32_t s, uint32_t kind, const uint4 pl, uint32_t w) {
-  if (!kind) return k.cv[(size_t)s * (size_t)k.NP + w];
-  uint32_t word = 0;
-  if (w < 8u) {
-#pragma unroll
-    for (uint32_t y = 0; y < 4u; ++y) {
-      const uint32_t sl = 4u * w + y;
-      word |= (((pl.x >> sl) & 1u) + ((pl.y >> sl) & 1u) + ((pl.z >> sl) & 1u) + ((pl.w >> sl) & 1u)) << (8u * y);
-    }
-  }
-  return word;
-}
-__global__ __launch_bounds__(RW_BLOCK) void k_rw_pre(RwPreArgs k) {
-  const uint32_t i = blockIdx.x * RW_BLOCK + threadIdx.x;
-  if (i >= k.n) return;
-  const anx_pair_score pr = k.pair[i];
-  const uint32_t g = k.gid[i];
-  const uint32_t ma = pr.status == ANX_OK ? k.meta[i] : 0u;
+__global__ __launch_bounds__(GOLD_BLOCK) void k_rw_pre(RwPreArgs k) {
+  const uint32_t i = blockIdx.x * GOLD_BLOCK + threadIdx.x;
+  if (i >= k.side.n) return;
+  const anx_pair_score pr = k.side.pair[i];
+  const uint32_t ma = pr.status == ANX_OK ? k.side.meta[i] : 0u;
   const uint32_t len = ma & 0xFFu;
-  const uint32_t kk = ma ? rw_clamp_threshold(k.kth, (int)len, kMaxAnagramDistance) : 0u;
-  const uint32_t dd = ma ? rw_clamp_threshold(k.dth, (int)len, kMaxEditDistance) : 0u;
-  uint32_t reason = RW_LATER;
-  if (pr.status != ANX_OK) {
-    reason = ANX_GOLD_STATUS;
-  } else if (g == RW_NONE || g >= k.V || !(k.vflags[g] & ANX_VOCAB_INDEXED) || (k.vflags[g] & ANX_VOCAB_TRANSPARENT)) {
-    reason = ANX_GOLD_NOT_A_RESULT;
-  } else {
-    const uint32_t ka = k.kind[i], kg = k.kind[k.n + i];
-    const uint4 pa = k.bits[i], pg = k.bits[k.n + i];
-    uint32_t l1 = 0;
-    for (uint32_t w = 0; w < (uint32_t)k.NP; ++w) l1 = __builtin_amdgcn_sad_u8(rw_cv_word(k, i, ka, pa, w), rw_cv_word(k, k.n + i, kg, pg, w), l1);
-    bool exact_stop = false;
-    if (k.stop_exact && l1 != 0u) {  // the input's own anagram class: the run of its signature in its charcount range, then the count vectors
-      const unsigned long long sig = k.sig[i];
-      int lo = (int)k.siglen_begin[len], hi = (int)k.siglen_begin[len + 1u] - 1;
-      while (lo <= hi && !exact_stop) {
-        const int mid = (lo + hi) >> 1;
-        const uint4 t = k.sigtab[mid];  // {sig lo, sig hi, first class, classes}
-        const unsigned long long v = (unsigned long long)t.x | (unsigned long long)t.y << 32;
-        if (sig < v) hi = mid - 1;
-        else if (sig > v) lo = mid + 1;
-        else {
-          for (uint32_t c = t.z; c < t.z + t.w && !exact_stop; ++c) {
-            bool eq = true;
-            for (uint32_t w = 0; w < (uint32_t)k.NP; ++w) eq = eq && k.cls_planes[(size_t)w * k.cstride + c] == rw_cv_word(k, i, ka, pa, w);
-            exact_stop = eq;
-          }
-          break;
-        }
-      }
-    }
-    if (exact_stop) reason = ANX_GOLD_EXACT_STOP;
-    else if (l1 > kk || l1 >= (uint32_t)pr.len_a + (uint32_t)pr.len_b) reason = ANX_GOLD_ANAGRAM;
-    else if ((uint32_t)pr.ld > dd) reason = ANX_GOLD_EDIT;
-  }
-  k.pre[i] = reason | kk << 8 | dd << 16;
+  const uint32_t kk = ma ? (uint32_t)dev_clamp_threshold(k.kth, (int)len, kMaxAnagramDistance) : 0u;
+  const uint32_t dd = ma ? (uint32_t)dev_clamp_threshold(k.dth, (int)len, kMaxEditDistance) : 0u;
+  k.pre[i] = gold_pre_reason(k.side, i, pr, kk, dd) | kk << 8 | dd << 16;
 }
 
 // ---- per set: the record and the reduction ------------------------------------------------------------------------------------------------
@@ -314,103 +222,48 @@ struct RwClassArgs {
   double score_threshold;
   uint8_t* at1_base;             // [n] gold at rank 0 under set 0
   int baseline;
-  unsigned long long* summary;   // [RW_COUNTERS]
+  unsigned long long* summary;   // [GOLD_COUNTERS]
   uint4* out;                    // [n][2] the records, or nullptr
 };
-// floor(2^32 / (rank + 1)) in 32-bit arithmetic for rank >= 1: 2^32 = 0xFFFFFFFF + 1
-__device__ inline unsigned long long rw_rr_fixed(uint32_t rank) {
-  if (rank == 0u) return 1ull << 32;
-  const uint32_t d = rank + 1u, q = 0xFFFFFFFFu / d, r = 0xFFFFFFFFu - q * d;
-  return (unsigned long long)(q + (r + 1u == d ? 1u : 0u));
-}
-__device__ inline unsigned long long rw_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o);
-  return v;
-}
-__global__ __launch_bounds__(RW_BLOCK) void k_rw_classify(RwClassArgs k) {
-  __shared__ unsigned long long s_wide[2];   // rr_fixed, n_results
-  __shared__ uint32_t s_cell[RW_CELLS32];    // the other counters in the struct's order, gained / lost behind the histogram
-  for (uint32_t x = threadIdx.x; x < RW_CELLS32; x += RW_BLOCK) s_cell[x] = 0u;
-  if (threadIdx.x < 2u) s_wide[threadIdx.x] = 0ull;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * RW_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(GOLD_BLOCK) void k_rw_classify(RwClassArgs k) {
+  __shared__ GoldCells s_cells;
+  gold_summary_begin(s_cells);
+  const uint32_t i = blockIdx.x * GOLD_BLOCK + threadIdx.x;
   const bool live = i < k.n;
-  uint32_t reason = 8u, g = RW_NONE, rk = RW_NONE, cnt = 0u;  // (reason 8: a lane behind the last pair counts nowhere)
+  uint32_t reason = 8u, g = GOLD_NONE, rk = GOLD_NONE, cnt = 0u;  // (reason 8: a lane behind the last pair counts nowhere)
   if (live) {
     const anx_pair_score pr = k.pair[i];
     g = k.gid[i];
     const uint32_t row0 = k.soff[i], room = min(k.soff[i + 1u], k.row_cap) - min(row0, k.row_cap);
     cnt = min(k.r_count[i], room);  // (k_rank never writes more rows than the pair has kept)
     const DevRow* rows = k.r_rows + row0;
-    const uint32_t top = cnt ? rows[0].vocab_id : RW_NONE;
-    if (g != RW_NONE)
+    const uint32_t top = cnt ? rows[0].vocab_id : GOLD_NONE;
+    if (g != GOLD_NONE)
       for (uint32_t j = 0; j < cnt; ++j)
         if (rows[j].vocab_id == g) { rk = j; break; }
     const uint32_t pw = k.pre[i];
     // the direct pair's score under the set's weights, from the measures the pair kernels left (0 for a pair with a status)
     double score = pr.status == ANX_OK ? rw_score(k.w, pr.len_a, pr.ld, pr.lcs, pr.prefixlen, pr.suffixlen, pr.samecase) : 0.0;
-    if (rk != RW_NONE) {
+    if (rk != GOLD_NONE) {
       reason = ANX_GOLD_RANKED;
       score = rows[rk].dist_score;
-    } else if ((pw & 0xFFu) != RW_LATER) {
+    } else if ((pw & 0xFFu) != GOLD_LATER) {
       reason = pw & 0xFFu;
     } else if (!(score >= k.score_threshold)) {
       reason = ANX_GOLD_THRESHOLD;
     } else {
       reason = ANX_GOLD_CROPPED;
     }
-    if (k.out) {
-      const unsigned long long sb = (unsigned long long)__double_as_longlong(score);
-      const uint32_t rank_word = reason == ANX_GOLD_RANKED ? rk : 0xFFFFFFFFu;  // int32 -1
-      k.out[2 * (size_t)i] = make_uint4(g, rank_word, cnt, top);
-      k.out[2 * (size_t)i + 1] = make_uint4((uint32_t)sb, (uint32_t)(sb >> 32), (uint32_t)pr.ld | (pw & 0xFFFF00u) << 8,
-                                            ((uint32_t)(int)pr.status & 0xFFu) | reason << 8);
-    }
+    if (k.out) gold_store_record(k.out, i, g, rk, cnt, top, score, pr.ld, (pw >> 8) & 0xFFu, (pw >> 16) & 0xFFu, pr.status, reason);
   }
-  // ---- the reduction: ballot counts and shuffle sums per wave -> LDS -> one atomic per non-zero counter and block ----
-  const bool ranked = reason == ANX_GOLD_RANKED;
-  const bool at1 = ranked && rk == 0u;
-  bool base1 = at1;
-  if (live) {
-    if (k.baseline) k.at1_base[i] = at1 ? 1 : 0;
-    else base1 = k.at1_base[i] != 0;
-  }
-  const bool lane0 = (threadIdx.x & 63u) == 0u;
-  const uint32_t c_live = (uint32_t)__popcll(__ballot(live)), c_known = (uint32_t)__popcll(__ballot(live && g != RW_NONE));
-  const uint32_t c_at1 = (uint32_t)__popcll(__ballot(at1));
-  const uint32_t c_gained = (uint32_t)__popcll(__ballot(at1 && !base1)), c_lost = (uint32_t)__popcll(__ballot(live && !at1 && base1));
-  if (lane0) {
-    if (c_live) atomicAdd(&s_cell[RW_N], c_live);
-    if (c_known) atomicAdd(&s_cell[RW_KNOWN], c_known);
-    if (c_at1) atomicAdd(&s_cell[RW_HIST], c_at1);
-    if (c_gained) atomicAdd(&s_cell[RW_GAINED - 2u], c_gained);
-    if (c_lost) atomicAdd(&s_cell[RW_LOST - 2u], c_lost);
-  }
-#pragma unroll
-  for (uint32_t r = 0; r < 8u; ++r) {
-    const uint32_t c = (uint32_t)__popcll(__ballot(reason == r));
-    if (lane0 && c) atomicAdd(&s_cell[RW_REASON + r], c);
-  }
-  if (ranked && rk != 0u) atomicAdd(&s_cell[RW_HIST + min(rk, (uint32_t)ANX_GOLD_RANK_BINS - 1u)], 1u);
-  const unsigned long long w_rr = rw_wave_sum(ranked ? rw_rr_fixed(rk) : 0ull), w_res = rw_wave_sum((unsigned long long)cnt);
-  if (lane0) {
-    if (w_rr) atomicAdd(&s_wide[0], w_rr);
-    if (w_res) atomicAdd(&s_wide[1], w_res);
-  }
-  __syncthreads();
-  if (threadIdx.x < RW_COUNTERS) {
-    const uint32_t t = threadIdx.x;
-    const unsigned long long v = t < RW_RR ? (unsigned long long)s_cell[t] : t <= RW_NRES ? s_wide[t - RW_RR] : (unsigned long long)s_cell[t - 2u];
-    if (v) atomicAdd(&k.summary[t], v);
-  }
+  gold_summary_end(s_cells, live, i, reason, g, rk, cnt, k.at1_base, k.baseline, k.summary);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
 struct RwGroup {
   SweepChunkView v{};
   size_t n = 0, R = 0;
-  std::vector<void*> blocks;       // pool blocks of the group, back to the pool at its end
+  PoolBlocks blocks;               // pool blocks of the group, back to the pool at its end
   void* h_down = nullptr;          // pinned: the summary | the records
   uint4* info = nullptr;
   uint2* meas = nullptr;
@@ -421,14 +274,7 @@ struct RwGroup {
   unsigned long long* d_sum = nullptr;
   uint4* d_out = nullptr;
   template <typename T>
-  int get(T** p, size_t count, std::string& err) {
-    void* q = nullptr;
-    const hipError_t e = pool_malloc(&q, std::max<size_t>(count * sizeof(T), 16));
-    if (e != hipSuccess) { err = std::string("pool_malloc: ") + hipGetErrorString(e); return ANX_ENODEVICE; }
-    blocks.push_back(q);
-    *p = static_cast<T*>(q);
-    return ANX_OK;
-  }
+  int get(T** p, size_t count, std::string& err) { return blocks.get(p, count, err); }
 };
 
 size_t reweigh_group_rows(const RwGroup* g) { return g->R; }
@@ -437,7 +283,7 @@ void reweigh_group_end(RwGroup* g) {
   if (!g) return;
   (void)hipSetDevice(g->v.dl->device);
   (void)hipStreamSynchronize(reinterpret_cast<hipStream_t>(g->v.stream));  // nothing of the group may still use the blocks
-  for (void* q : g->blocks) pool_free(q);
+  g->blocks.release();
   if (g->h_down) host_result_free(g->h_down);
   delete g;
 }
@@ -450,7 +296,6 @@ int reweigh_group_begin(const SweepChunkView& v, const anx_params& group, const 
   if (secs.size() != sec_rows.size() || secs.size() != sec_meas.size()) { err = "reweigh_group_begin: sections, row counts and measures differ"; return ANX_EINVAL; }
   size_t R = 0;
   for (size_t s = 0; s < secs.size(); ++s) {
-    if (secs[s].n > n || (!secs[s].idx && secs[s].lo + secs[s].n > n)) { err = "reweigh_group_begin: a section beyond the chunk"; return ANX_EINVAL; }
     R += sec_rows[s];
     if (R >= 0x7FFFFFFFull) { err = "weight sweep: more than 2^31 base rows in a chunk"; return ANX_ELIMIT; }
   }
@@ -458,6 +303,7 @@ int reweigh_group_begin(const SweepChunkView& v, const anx_params& group, const 
   HIP_TRY(hipSetDevice(dl->device));  // (the batch runs in between may have left another replica's device current)
   hipStream_t st = reinterpret_cast<hipStream_t>(v.stream);
   if (const int rc = replica_vocab_entries(*v.m, dl, st, err)) return rc;
+  std::vector<GoldSection> hs;  // the sections as k_rw_base reads them: each goes into its launch by value
   RwGroup* g = new RwGroup;
   struct Guard { RwGroup* g; ~Guard() { if (g) reweigh_group_end(g); } } guard{g};
   g->v = v; g->n = n; g->R = R;
@@ -466,15 +312,12 @@ int reweigh_group_begin(const SweepChunkView& v, const anx_params& group, const 
   if ((rc = g->get(&g->info, Rc, err)) || (rc = g->get(&g->meas, Rc, err)) || (rc = g->get(&g->score, Rc, err)) || (rc = g->get(&g->t_key, Rc, err)) ||
       (rc = g->get(&g->c_rows, Rc, err)) || (rc = g->get(&g->r_rows, Rc, err)) || (rc = g->get(&g->cnt, n, err)) || (rc = g->get(&g->soff, n + 1, err)) ||
       (rc = g->get(&g->cur, n, err)) || (rc = g->get(&g->maxf, n, err)) || (rc = g->get(&g->r_count, n, err)) || (rc = g->get(&g->pre, n, err)) ||
-      (rc = g->get(&g->ovf, 4, err)) || (rc = g->get(&g->d_sum, RW_COUNTERS, err)) || (want_records && (rc = g->get(&g->d_out, 2 * n, err))))
+      (rc = g->get(&g->ovf, 4, err)) || (rc = g->get(&g->d_sum, GOLD_COUNTERS, err)) || (want_records && (rc = g->get(&g->d_out, 2 * n, err))))
     return rc;
-  {
-    void* q = nullptr;
-    const hipError_t e = pool_malloc(&q, std::max<size_t>(prefix_scan_tmp_bytes(n), 16));
-    if (e != hipSuccess) { err = std::string("pool_malloc: ") + hipGetErrorString(e); return ANX_ENODEVICE; }
-    g->blocks.push_back(q);
-    g->tmp = static_cast<uint32_t*>(q);
-  }
+  uint8_t* tmp = nullptr;
+  if ((rc = g->get(&tmp, prefix_scan_tmp_bytes(n), err))) return rc;
+  g->tmp = reinterpret_cast<uint32_t*>(tmp);
+  if ((rc = gold_sections_upload("reweigh_group_begin", secs, sec_rows, n, g->blocks, st, hs, nullptr, err))) return rc;
   g->h_down = host_result_alloc(sizeof(anx_gold_summary) + (want_records ? n * sizeof(anx_gold_eval) : 0));
   if (!g->h_down) { err = "out of host memory"; return ANX_EINVAL; }
   HIP_TRY(hipMemsetAsync(g->maxf, 0, n * sizeof(uint32_t), st));
@@ -484,37 +327,27 @@ int reweigh_group_begin(const SweepChunkView& v, const anx_params& group, const 
   {
     const int kt = ktimer_begin("k_rw_base", st);
     for (size_t s = 0; s < secs.size(); ++s) {
-      const LearnSection& L = secs[s];
-      const size_t off_bytes = ((L.n + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
       RwBaseArgs k{};
-      k.sec.off = static_cast<const uint32_t*>(L.base);
-      k.sec.rec = reinterpret_cast<const anx_topk_record*>(static_cast<const char*>(L.base) + off_bytes);
-      k.sec.meas = reinterpret_cast<const uint4*>(sec_meas[s]);
-      k.sec.n = (uint32_t)L.n; k.sec.lo = (uint32_t)L.lo; k.sec.rows = (uint32_t)sec_rows[s];
-      k.sec.idx = nullptr;
-      if (L.idx && L.n) {
-        uint32_t* d_idx = nullptr;
-        if ((rc = g->get(&d_idx, L.n, err))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_idx, L.idx, L.n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        k.sec.idx = d_idx;
-      }
+      k.sec = RwSection{hs[s], reinterpret_cast<const uint4*>(sec_meas[s])};
       k.row0 = (uint32_t)row0; k.n = n32; k.R = (uint32_t)R;
       k.vocab_ent = dl->vocab_ent; k.V = dl->vocab_ent_n; k.nentries = dl->nentries; k.ent_rec = dl->ent_rec; k.have_freq = v.m->have_freq ? 1 : 0;
       k.info = g->info; k.meas = g->meas; k.maxf = g->maxf;
-      if (k.sec.n && k.sec.rows) hipLaunchKernelGGL(k_rw_base, dim3(grid_of(k.sec.rows)), dim3(RW_BLOCK), 0, st, k);
+      if (k.sec.n && k.sec.rows) hipLaunchKernelGGL(k_rw_base, dim3(gold_grid(k.sec.rows)), dim3(GOLD_BLOCK), 0, st, k);
       row0 += sec_rows[s];
     }
     ktimer_end(kt, st);
   }
   RwPreArgs p{};
-  p.n = n32; p.meta = v.meta; p.kind = v.kind; p.cv = v.cv; p.bits = reinterpret_cast<const uint4*>(v.bits); p.sig = v.sig; p.NP = dl->nplanes;
-  p.pair = v.pair; p.gid = v.gid; p.vflags = v.vflags; p.V = (uint32_t)v.m->decoder.size();
-  p.sigtab = dl->sig; p.siglen_begin = dl->alpha.siglen_begin; p.cls_planes = dl->cls_planes; p.cstride = dl->cstride;
-  p.kth = group.max_anagram_distance; p.dth = group.max_edit_distance; p.stop_exact = group.stop_at_exact_match ? 1 : 0;
+  GoldPairSide& d = p.side;
+  d.n = n32; d.meta = v.meta; d.kind = v.kind; d.cv = v.cv; d.bits = reinterpret_cast<const uint4*>(v.bits); d.sig = v.sig;
+  d.NP = dl->nplanes; d.pair = v.pair; d.gid = v.gid; d.vflags = v.vflags; d.V = (uint32_t)v.m->decoder.size();
+  d.sigtab = dl->sig; d.siglen_begin = dl->alpha.siglen_begin; d.cls_planes = dl->cls_planes; d.cstride = dl->cstride;
+  d.stop_exact = group.stop_at_exact_match ? 1 : 0;
+  p.kth = group.max_anagram_distance; p.dth = group.max_edit_distance;
   p.pre = g->pre;
   {
     const int kt = ktimer_begin("k_rw_pre", st);
-    hipLaunchKernelGGL(k_rw_pre, dim3(grid_of(n)), dim3(RW_BLOCK), 0, st, p);
+    hipLaunchKernelGGL(k_rw_pre, dim3(gold_grid(n)), dim3(GOLD_BLOCK), 0, st, p);
     ktimer_end(kt, st);
   }
   HIP_TRY(hipGetLastError());
@@ -525,7 +358,6 @@ int reweigh_group_begin(const SweepChunkView& v, const anx_params& group, const 
 }
 
 int reweigh_group_set(RwGroup* g, const anx_params& p, const anx_weights& w, bool baseline, anx_gold_summary* sum, anx_gold_eval* out, std::string& err) {
-  static_assert(sizeof(anx_gold_summary) == RW_COUNTERS * sizeof(unsigned long long), "the summary is its counters");
   if (out && !g->d_out) { err = "reweigh_group_set: the group keeps no record buffer"; return ANX_EINVAL; }
   const SweepChunkView& v = g->v;
   const size_t n = g->n, R = g->R;
@@ -541,13 +373,13 @@ int reweigh_group_set(RwGroup* g, const anx_params& p, const anx_weights& w, boo
   k.score = g->score; k.cnt = g->cnt; k.soff = g->soff; k.cur = g->cur; k.c_rows = reinterpret_cast<uint4*>(g->c_rows); k.row_cap = (uint32_t)R;
   if (R) {
     const int kt = ktimer_begin("k_rw_score", st);
-    hipLaunchKernelGGL(k_rw_score, dim3(grid_of(R)), dim3(RW_BLOCK), 0, st, k);
+    hipLaunchKernelGGL(k_rw_score, dim3(gold_grid(R)), dim3(GOLD_BLOCK), 0, st, k);
     ktimer_end(kt, st);
   }
   if (prefix_scan_enqueue(g->cnt, (uint32_t)n, g->soff, g->tmp, st, g->cur)) { err = "weight sweep: the prefix sum could not be enqueued"; return ANX_ENODEVICE; }
   if (R) {
     const int kt = ktimer_begin("k_rw_fill", st);
-    hipLaunchKernelGGL(k_rw_fill, dim3(grid_of(R)), dim3(RW_BLOCK), 0, st, k);
+    hipLaunchKernelGGL(k_rw_fill, dim3(gold_grid(R)), dim3(GOLD_BLOCK), 0, st, k);
     ktimer_end(kt, st);
   }
   {
@@ -561,20 +393,14 @@ int reweigh_group_set(RwGroup* g, const anx_params& p, const anx_weights& w, boo
   c.w = k.w; c.score_threshold = p.score_threshold; c.at1_base = v.at1; c.baseline = baseline ? 1 : 0; c.summary = g->d_sum; c.out = out ? g->d_out : nullptr;
   {
     const int kt = ktimer_begin("k_rw_classify", st);
-    hipLaunchKernelGGL(k_rw_classify, dim3(grid_of(n)), dim3(RW_BLOCK), 0, st, c);
+    hipLaunchKernelGGL(k_rw_classify, dim3(gold_grid(n)), dim3(GOLD_BLOCK), 0, st, c);
     ktimer_end(kt, st);
   }
   HIP_TRY(hipGetLastError());
-  char* h = static_cast<char*>(g->h_down);
-  HIP_TRY(hipMemcpyAsync(h, g->d_sum, sizeof(anx_gold_summary), hipMemcpyDeviceToHost, st));
-  if (out) HIP_TRY(hipMemcpyAsync(h + sizeof(anx_gold_summary), g->d_out, n * sizeof(anx_gold_eval), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  reweigh_stats_add(RW_BYTES_DOWN, sizeof(anx_gold_summary) + (out ? n * sizeof(anx_gold_eval) : 0));
+  size_t bytes = 0;
+  if (int rc = gold_set_download(static_cast<char*>(g->h_down), g->d_sum, g->d_out, n, st, sum, out, &bytes, err)) return rc;
+  reweigh_stats_add(RW_BYTES_DOWN, bytes);
   reweigh_stats_add(RW_ROWS_RESCORED, R);
-  const uint64_t* got = reinterpret_cast<const uint64_t*>(h);
-  uint64_t* acc = reinterpret_cast<uint64_t*>(sum);
-  for (uint32_t j = 0; j < RW_COUNTERS; ++j) acc[j] += got[j];
-  if (out) memcpy(out, h + sizeof(anx_gold_summary), n * sizeof(anx_gold_eval));
   return ANX_OK;
 }
 

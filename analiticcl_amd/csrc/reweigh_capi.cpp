@@ -16,17 +16,16 @@
 #include "engine.h"
 #include "eval_gather.h"
 #include "host_model.h"
+#include "pair_spans.h"
 #include "reweigh.h"
 #include "sweep.h"
 
 anx::HostModel& anx_learn_host(anx_model* m);
 const anx::DeviceLexicon* anx_replica_of(const anx_model* m, size_t i);
-void** anx_learn_vocab_slot(anx_model* m, void (*release)(void*));
 std::mutex& anx_learn_mutex();
 int anx_fail(int code, const std::string& msg);
 
 namespace {
-void release_vocab(void* p) { anx::learn_vocab_free(static_cast<anx::LearnVocab*>(p)); }
 
 struct Tail {  // what every form of the call ends in
   const anx_params* sets;
@@ -69,7 +68,7 @@ bool model_weights_score_numbers(const anx_weights& w) {
 int chunk_run(anx_model* m, const char* const* in, const anx::PairSpan* sa, const anx::PairSpan* sg, size_t lo, size_t cnt, size_t n, const Tail& t,
               const std::vector<std::vector<size_t>>& groups) {
   std::string err;
-  anx::LearnVocab** vocab = reinterpret_cast<anx::LearnVocab**>(anx_learn_vocab_slot(m, release_vocab));
+  anx::LearnVocab** vocab = anx::learn_vocab_slot(m);
   anx::SweepChunk* c = nullptr;
   if (int rc = anx::sweep_chunk_begin(anx_learn_host(m), anx_replica_of(m, 0), vocab, sa, sg, cnt, false, &c, err)) return anx_fail(rc, err);
   struct End { anx::SweepChunk* c; ~End() { anx::sweep_chunk_end(c); } } end{c};
@@ -147,25 +146,9 @@ int pointer_call(anx_model* m, const char* const* a, const char* const* g, size_
   bool run;
   if (int rc = check_call(m, a, g, n, t, &run); rc || !run) return rc;
   if (chunk < 1 || chunk > anx::PAIRS_CHUNK) return anx_fail(ANX_EINVAL, "weight sweep: chunk size outside 1 .. 2^20");
-  std::vector<anx::PairSpan> sa(n), sg(n);
-  for (size_t i = 0; i < n; ++i) {
-    if (!a[i] || !g[i]) return anx_fail(ANX_EINVAL, "NULL string");
-    sa[i] = anx::PairSpan{a[i], strlen(a[i])};
-    sg[i] = anx::PairSpan{g[i], strlen(g[i])};
-  }
+  std::vector<anx::PairSpan> sa, sg;
+  if (!anx::spans_of_pointers(a, n, sa) || !anx::spans_of_pointers(g, n, sg)) return anx_fail(ANX_EINVAL, "NULL string");
   return run_call(m, a, sa, sg, t, chunk);
-}
-// the first n NUL-terminated spans of blob[0, len)
-bool spans_of(const char* blob, size_t len, size_t n, std::vector<anx::PairSpan>& out) {
-  out.resize(n);
-  size_t pos = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const char* z = pos < len ? static_cast<const char*>(memchr(blob + pos, 0, len - pos)) : nullptr;
-    if (!z) return false;
-    out[i] = anx::PairSpan{blob + pos, (size_t)(z - (blob + pos))};
-    pos = (size_t)(z - blob) + 1;
-  }
-  return true;
 }
 }  // namespace
 
@@ -185,7 +168,7 @@ int anx_evaluate_sweep_weights_packed(anx_model* m, const char* blob_in, size_t 
   if (int rc = check_call(m, blob_in, blob_gold, n, t, &run); rc || !run) return rc;
   if (len_in >= ((size_t)1 << 32) || len_gold >= ((size_t)1 << 32)) return anx_fail(ANX_ELIMIT, "packed pairs exceed 4 GB per blob: split the call");
   std::vector<anx::PairSpan> sa, sg;
-  if (!spans_of(blob_in, len_in, n, sa) || !spans_of(blob_gold, len_gold, n, sg)) return anx_fail(ANX_EINVAL, "packed inputs hold fewer strings than announced");
+  if (!anx::spans_of(blob_in, len_in, n, sa) || !anx::spans_of(blob_gold, len_gold, n, sg)) return anx_fail(ANX_EINVAL, "packed inputs hold fewer strings than announced");
   return run_call(m, nullptr, sa, sg, t, anx::PAIRS_CHUNK);  // (the spans lie back to back, each behind its NUL byte)
 }
 int anx_debug_weight_sweep_stats(uint64_t* out, int n) {
