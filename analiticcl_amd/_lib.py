@@ -283,6 +283,17 @@ def lib():
         "anx_debug_evaluate_sweep_weights_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(Weights), sz,
                                                              C.POINTER(GoldSummary), C.POINTER(GoldEval), sz]),
         "anx_debug_weight_sweep_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
+        "anx_evaluate_sweep_confusables": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(C.c_double),
+                                                     C.POINTER(C.c_uint8), sz, C.POINTER(GoldSummary), C.POINTER(GoldEval)]),
+        "anx_evaluate_sweep_confusables_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(cp), sz, C.POINTER(Params),
+                                                            C.POINTER(C.c_double), C.POINTER(C.c_uint8), sz, C.POINTER(GoldSummary), C.POINTER(GoldEval)]),
+        "anx_debug_evaluate_sweep_confusables_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(cp), sz, C.POINTER(Params),
+                                                                 C.POINTER(C.c_double), C.POINTER(C.c_uint8), sz, C.POINTER(GoldSummary),
+                                                                 C.POINTER(GoldEval), sz]),
+        "anx_debug_sweep_conf_masks": (C.c_int, [vp, C.POINTER(cp), sz, C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(C.POINTER(C.c_uint32)),
+                                                 C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(sz)]),
+        "anx_debug_conf_mask_text": (C.c_int, [C.POINTER(cp), sz, cp, cp, C.POINTER(C.c_uint64)]),
+        "anx_debug_conf_sweep_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
         "anx_default_mine_params": (None, [C.POINTER(MineParams)]),
         "anx_mine_confusables": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), C.POINTER(C.c_uint32), sz, C.POINTER(MineParams),
                                            C.POINTER(C.POINTER(MineResult))]),

@@ -21,7 +21,11 @@ columns among `k d n t T s freq-weight`; every further line is one set in the sy
 line's value, the first set is the baseline) and writes one TSV line per set (evaluate_sweep: the set's seven parameters, pairs,
 accuracy@1, mrr, ranked share, the eight reason counts, gained@1 / lost@1 against the first set, mean list length).  A grid that also names
 any of `w-ld w-lcs w-prefix w-suffix w-case` is a weight grid (evaluate_sweep_weights: absent weight columns take `--weight-*`, the five
-weights are printed behind the seven parameters).
+weights are printed behind the seven parameters).  `sweep --candidates LIST.tsv --candidate-weights 1.1,0.9` needs no grid: LIST.tsv is a
+confusable list (what `mine --as-confusables` writes; its weight column is ignored) of at most 64 candidate patterns, and under the
+command line's parameters the output is one TSV line per set (evaluate_sweep_confusables) -- first the baseline with every candidate
+off, then one per (pattern, weight) with only that pattern on: pattern, weight, accuracy@1, mrr, gained@1 / lost@1 against the baseline,
+the eight reason counts; `--early-confusables` weights before pruning.
 Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
@@ -164,6 +168,9 @@ def build_parser() -> argparse.ArgumentParser:
                                                         "sweep mode: write the summaries as JSON to this file as well")
     p.add_argument("--grid", default=None, help="sweep mode: TSV file of parameter sets; the header names columns among `k d n t T s freq-weight` (and `w-ld w-lcs w-prefix w-suffix w-case`: a weight grid), every further "
                                                 "line is one set in the syntax of those options; the first set is the baseline")
+    p.add_argument("--candidates", default=None, metavar="LIST.tsv",
+                   help="sweep mode: a confusable list of candidate patterns (at most 64; the weight column is ignored): every candidate is tried alone at every --candidate-weights value")
+    p.add_argument("--candidate-weights", default=None, metavar="W,W,..", help="sweep mode, with --candidates: the weights to try, comma-separated (each finite, above 0)")
     p.add_argument("--index-cache", default=None, help="image of the built model: loaded if the file exists (lexicons are then not read), written after build() otherwise")
     p.add_argument("--device", type=int, default=None)
     p.add_argument("--single-thread", "-1", action="store_true", help="accepted for compatibility, no effect")
@@ -637,12 +644,97 @@ def sweep_tsv_line(d: dict, s: dict) -> str:
                      [str(s["gained_at_1"]), str(s["lost_at_1"]), rust_f64(s["n_results"] / n if n else 0.0)])
 
 
+CANDIDATES_MAX, CANDIDATE_SETS_MAX = 64, 256   # anx_evaluate_sweep_confusables' limits
+
+
+def parse_candidates(lines) -> List[str]:
+    """The patterns of a `sweep --candidates` file: the first column of every non-empty line of a confusable list, in file order."""
+    pats = [ln.rstrip("\r\n").split("\t", 1)[0] for ln in lines]
+    pats = [p for p in pats if p.strip()]
+    if not pats:
+        raise ValueError("candidates: no pattern")
+    if len(pats) > CANDIDATES_MAX:
+        raise ValueError("candidates: %d patterns, the limit is %d" % (len(pats), CANDIDATES_MAX))
+    return pats
+
+
+def parse_candidate_weights(text) -> List[float]:
+    """`--candidate-weights 1.1,1.25,0.9` as floats (finite, above 0)."""
+    import math
+    if not text or not text.strip():
+        raise ValueError("candidate weights: none given (--candidate-weights 1.1,0.9)")
+    try:
+        ws = [float(c) for c in text.split(",")]
+    except ValueError:
+        raise ValueError("candidate weights: not a number in %r" % text)
+    if any(not math.isfinite(w) or not w > 0.0 for w in ws):
+        raise ValueError("candidate weights: every weight is finite and above 0, not %r" % text)
+    return ws
+
+
+def candidate_grid(patterns: List[str], weights: List[float]):
+    """The one-pattern-on grid: set 0 is the baseline with every candidate at 1.0, then one set per (pattern, weight) in pattern order
+    with only that pattern on.  -> (labels, weights_list): labels[s] = (pattern or "-", weight), weights_list[s] = one weight per pattern."""
+    n_sets = 1 + len(patterns) * len(weights)
+    if len(patterns) > CANDIDATES_MAX:
+        raise ValueError("candidates: %d patterns, the limit is %d" % (len(patterns), CANDIDATES_MAX))
+    if n_sets > CANDIDATE_SETS_MAX:
+        raise ValueError("candidates: %d patterns x %d weights + the baseline = %d sets, the limit is %d" % (len(patterns), len(weights), n_sets, CANDIDATE_SETS_MAX))
+    labels, rows = [("-", 1.0)], [[1.0] * len(patterns)]
+    for j, p in enumerate(patterns):
+        for w in weights:
+            labels.append((p, w))
+            rows.append([w if x == j else 1.0 for x in range(len(patterns))])
+    return labels, rows
+
+
+def candidate_tsv_line(label, s: dict) -> str:
+    """One set of the candidate sweep: pattern (`-`: the baseline), weight, accuracy@1, mrr, gained@1, lost@1 against the baseline, the
+    eight reason counts (GOLD_REASONS order).  s: VariantModel.sweep_summary."""
+    return "\t".join([label[0], rust_f64(label[1]), rust_f64(s["accuracy_at_1"]), rust_f64(s["mrr"]), str(s["gained_at_1"]), str(s["lost_at_1"])] +
+                     [str(s["reasons"][r]) for r in GOLD_REASONS])
+
+
+def run_sweep_candidates(model, a, out) -> None:
+    """`sweep --candidates`: every candidate pattern alone at every weight over the `input<TAB>gold` lines, in one
+    evaluate_sweep_confusables call under the command line's parameters: one TSV line per set (candidate_tsv_line), the baseline first."""
+    import json
+    if a.grid:
+        sys.stderr.write("ERROR: sweep takes --grid or --candidates, not both (the candidates run under the command line's parameters)\n")
+        sys.exit(2)
+    try:
+        with open(a.candidates, encoding="utf-8", newline="") as f:
+            patterns = parse_candidates(f.read().split("\n"))
+        labels, rows = candidate_grid(patterns, parse_candidate_weights(a.candidate_weights))
+    except ValueError as e:
+        sys.stderr.write("ERROR: %s\n" % e)
+        sys.exit(2)
+    pa: List[str] = []
+    pg: List[str] = []
+    for line in _lines(a.files):
+        x, _, y = (line[:-1] if line.endswith("\r") else line).partition("\t")
+        pa.append(x)
+        pg.append(y.split("\t", 1)[0])
+    params = make_params(a)
+    summaries = model.evaluate_sweep_confusables(pa, pg, patterns, [params] * len(rows), rows, [bool(a.early_confusables)] * len(rows))
+    for lab, s in zip(labels, summaries):
+        out.write(candidate_tsv_line(lab, s) + "\n")
+    out.flush()
+    if a.summary_json:
+        with open(a.summary_json, "w") as f:
+            json.dump([dict(s, pattern=lab[0], weight=lab[1]) for lab, s in zip(labels, summaries)], f, indent=1)
+            f.write("\n")
+
+
 def run_sweep(model, a, out) -> None:
     """`sweep`: the `input<TAB>gold` lines of the input under every parameter set of --grid in one evaluate_sweep call: one TSV line per
     set (sweep_tsv_line), in grid order; --summary-json: the same as a JSON list (the set's parameters under "params")."""
     import json
+    if a.candidates:
+        run_sweep_candidates(model, a, out)
+        return
     if not a.grid:
-        sys.stderr.write("ERROR: sweep needs --grid\n")
+        sys.stderr.write("ERROR: sweep needs --grid or --candidates\n")
         sys.exit(2)
     with open(a.grid, encoding="utf-8", newline="") as f:
         sets = parse_grid(f.read().split("\n"), a)

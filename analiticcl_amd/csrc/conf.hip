@@ -387,48 +387,6 @@ struct PairConfArgs {
   uint32_t* key;                   // [n] shape key per list entry (conf_shape_key's idea), preset to all ones behind the list
 };
 
-// The ASCII presence bits of one side from its bytes, and whether the bytes are anything but well-formed UTF-8 (a stray continuation
-// byte, a lead byte without its continuation bytes, an overlong form, 0xF8..).  The decoder of k_pairs_conf_script and of the host
-// takes the length from the lead byte alone: on such bytes it may swallow an ASCII byte into a character, or produce an ASCII
-// character from non-ASCII bytes, so bits and byte-wise prefix / suffix say nothing about the decoded string.
-__device__ inline bool pairs_side_bits(const uint8_t* __restrict__ blob, uint32_t t0, uint32_t t1, cdiff::CharSet& cs) {
-  cs.w[0] = cs.w[1] = 0;
-  cs.other = 0;
-  bool bad = false;
-  uint32_t pend = 0, lo = 0x80u;
-  for (uint32_t x = t0; x < t1; ++x) {
-    const uint32_t ch = blob[x];
-    if (ch < 64u) cs.w[0] |= 1ull << ch; else if (ch < 128u) cs.w[1] |= 1ull << (ch - 64u); else cs.other = 1;
-    if (pend) {
-      if ((ch & 0xC0u) != 0x80u || ch < lo) bad = true;
-      --pend;
-      lo = 0x80u;
-    } else if (ch >= 0x80u) {
-      if (ch >= 0xC2u && ch < 0xE0u) pend = 1;
-      else if (ch >= 0xE0u && ch < 0xF0u) { pend = 2; lo = ch == 0xE0u ? 0xA0u : 0x80u; }
-      else if (ch >= 0xF0u && ch < 0xF8u) { pend = 3; lo = ch == 0xF0u ? 0x90u : 0x80u; }
-      else bad = true;
-    }
-  }
-  return bad || pend != 0;
-}
-
-// An instruction with a multi-character or non-ASCII option, on presence bits: one of its options must have every ASCII character in
-// the set (s0, s1) and, if it has a character beyond ASCII, the string(s) must have one too (`other`).  Necessary like the bits of a
-// `simple` instruction: the option is a substring of the text it is matched against.
-__device__ inline bool pairs_opt_may(const cdiff::Patterns& P, const cdiff::FlatOp& o, uint64_t s0, uint64_t s1, bool other) {
-  for (uint32_t k = 0; k < o.nopt; ++k) {
-    const cdiff::FlatOpt opt = P.opts[o.opt_begin + k];
-    bool all = true;
-    for (uint32_t i = 0; i < opt.len && all; ++i) {
-      const uint32_t cp = P.pool[opt.off + i];
-      all = cp < 64u ? (s0 >> cp) & 1ull : cp < 128u ? (s1 >> (cp - 64u)) & 1ull : other;
-    }
-    if (all) return true;
-  }
-  return false;
-}
-
 // One lane per pair: k_conf_screen's two looks with both sides taken from bytes -- the presence bits of the whole strings against the
 // patterns' `simple` instructions, then the bits of the middles (what is left between the common ASCII prefix and suffix).  The list
 // positions of a wave are reserved with one atomic.
@@ -579,22 +537,10 @@ void conf_free(DeviceConf* dc) {
   delete dc;
 }
 
-// The replica's copy of the pattern tables and of the vocabulary (code points + presence bits): built on first use, rebuilt when
-// patterns or vocabulary items were added since.  vocab = false (caller-chosen pairs: both sides are the caller's text): the
-// vocabulary copy is left as it is.
-static int conf_ensure(const HostModel& m, const DeviceLexicon* dl, std::string& err, bool vocab = true) {
-  std::lock_guard<std::mutex> g(g_conf_mu);
-  DeviceConf*& dc = dl->dconf;
-  if (!dc) { dc = new DeviceConf(); dc->device = dl->device; }
+// The vocabulary half of conf_ensure: the replica's copy of the vocabulary as code points with offsets and presence bits, and the
+// alphabetic ranges.  The caller holds g_conf_mu.
+static int conf_ensure_vocab_locked(const HostModel& m, DeviceConf* dc, bool vocab, std::string& err) {
   int rc;
-  if (dc->built_patterns != m.confusables.size() || !dc->conf) {
-    const HostModel::ConfTables& t = m.conf_tables;
-    if ((rc = cf_upload(&dc->conf, t.conf.data(), t.conf.size(), err)) || (rc = cf_upload(&dc->ops, t.ops.data(), t.ops.size(), err)) ||
-        (rc = cf_upload(&dc->opts, t.opts.data(), t.opts.size(), err)) || (rc = cf_upload(&dc->pool, t.pool.data(), t.pool.size(), err)))
-      return rc;
-    dc->nconf = (uint32_t)t.conf.size();
-    dc->built_patterns = m.confusables.size();
-  }
   if (vocab && (dc->built_vocab != m.decoder.size() || !dc->v_cs)) {
     const uint32_t *pool, *off;
     const void* cs;
@@ -614,6 +560,25 @@ static int conf_ensure(const HostModel& m, const DeviceLexicon* dl, std::string&
     dc->alpha = reinterpret_cast<uint32_t(*)[2]>(p);
     dc->nalpha = na;
   }
+  return ANX_OK;
+}
+// The replica's copy of the pattern tables and of the vocabulary (code points + presence bits): built on first use, rebuilt when
+// patterns or vocabulary items were added since.  vocab = false (caller-chosen pairs: both sides are the caller's text): the
+// vocabulary copy is left as it is.
+static int conf_ensure(const HostModel& m, const DeviceLexicon* dl, std::string& err, bool vocab = true) {
+  std::lock_guard<std::mutex> g(g_conf_mu);
+  DeviceConf*& dc = dl->dconf;
+  if (!dc) { dc = new DeviceConf(); dc->device = dl->device; }
+  int rc;
+  if (dc->built_patterns != m.confusables.size() || !dc->conf) {
+    const HostModel::ConfTables& t = m.conf_tables;
+    if ((rc = cf_upload(&dc->conf, t.conf.data(), t.conf.size(), err)) || (rc = cf_upload(&dc->ops, t.ops.data(), t.ops.size(), err)) ||
+        (rc = cf_upload(&dc->opts, t.opts.data(), t.opts.size(), err)) || (rc = cf_upload(&dc->pool, t.pool.data(), t.pool.size(), err)))
+      return rc;
+    dc->nconf = (uint32_t)t.conf.size();
+    dc->built_patterns = m.confusables.size();
+  }
+  if ((rc = conf_ensure_vocab_locked(m, dc, vocab, err))) return rc;
   return ANX_OK;
 }
 
@@ -762,6 +727,32 @@ int conf_launch_pairs(const HostModel& m, const DeviceLexicon* dl, hipStream_t s
   ktimer_end(kt2, st);
   HIP_TRY(hipGetLastError());
   return ANX_OK;
+}
+
+// ---- what the confusable sweep (csweep.hip) shares ------------------------------------------------------------------------------------
+// The vocabulary copy alone, for a model that owns no list.
+int conf_vocab_view(const HostModel& m, const DeviceLexicon* dl, ConfVocabView* v, std::string& err) {
+  std::lock_guard<std::mutex> g(g_conf_mu);
+  DeviceConf*& dc = dl->dconf;
+  if (!dc) { dc = new DeviceConf(); dc->device = dl->device; }
+  if (const int rc = conf_ensure_vocab_locked(m, dc, true, err)) return rc;
+  *v = ConfVocabView{dc->v_pool, dc->v_off, dc->v_cs, dc->nvocab, dc->alpha, dc->nalpha};
+  return ANX_OK;
+}
+// the radix pass of conf_launch_pairs: (shape key, value) pairs by their 13 key bits
+int conf_sort_enqueue(void* tmp, size_t tmp_bytes, const uint32_t* keys, uint32_t* keys_out, const uint32_t* vals, uint32_t* vals_out, uint32_t n, hipStream_t st,
+                      std::string& err) {
+  HIP_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, vals, vals_out, (size_t)n, 0u, 13u, st));
+  return ANX_OK;
+}
+// k_conf_apply_late on rows ranked elsewhere: weight[soff[s] + j] belongs to ranked row j of query s
+void conf_apply_late_enqueue(hipStream_t st, uint32_t nq, uint32_t row_cap, const uint32_t* soff, DevRow* r_rows, const double* weight, const uint32_t* overflow,
+                             double cutoff_threshold, float freq_weight, uint32_t* r_count) {
+  ConfArgs a{};
+  a.nq = nq; a.row_cap = row_cap; a.early = 0; a.soff = soff; a.r_count = r_count; a.overflow = overflow; a.r_rows = r_rows;
+  a.weight = const_cast<double*>(weight);
+  a.cutoff_threshold = cutoff_threshold; a.freq_weight = freq_weight;
+  hipLaunchKernelGGL(k_conf_apply_late, dim3((nq + 255u) / 256u), dim3(256), 0, st, a, r_count);
 }
 
 }  // namespace anx

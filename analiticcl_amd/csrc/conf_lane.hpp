@@ -43,4 +43,46 @@ __device__ inline bool pairs_conf_decode(const cdiff::Ctx& c, const uint8_t* __r
   return true;
 }
 
+// The ASCII presence bits of one side from its bytes, and whether the bytes are anything but well-formed UTF-8 (a stray continuation
+// byte, a lead byte without its continuation bytes, an overlong form, 0xF8..).  The decoder of k_pairs_conf_script and of the host
+// takes the length from the lead byte alone: on such bytes it may swallow an ASCII byte into a character, or produce an ASCII
+// character from non-ASCII bytes, so bits and byte-wise prefix / suffix say nothing about the decoded string.
+__device__ inline bool pairs_side_bits(const uint8_t* __restrict__ blob, uint32_t t0, uint32_t t1, cdiff::CharSet& cs) {
+  cs.w[0] = cs.w[1] = 0;
+  cs.other = 0;
+  bool bad = false;
+  uint32_t pend = 0, lo = 0x80u;
+  for (uint32_t x = t0; x < t1; ++x) {
+    const uint32_t ch = blob[x];
+    if (ch < 64u) cs.w[0] |= 1ull << ch; else if (ch < 128u) cs.w[1] |= 1ull << (ch - 64u); else cs.other = 1;
+    if (pend) {
+      if ((ch & 0xC0u) != 0x80u || ch < lo) bad = true;
+      --pend;
+      lo = 0x80u;
+    } else if (ch >= 0x80u) {
+      if (ch >= 0xC2u && ch < 0xE0u) pend = 1;
+      else if (ch >= 0xE0u && ch < 0xF0u) { pend = 2; lo = ch == 0xE0u ? 0xA0u : 0x80u; }
+      else if (ch >= 0xF0u && ch < 0xF8u) { pend = 3; lo = ch == 0xF0u ? 0x90u : 0x80u; }
+      else bad = true;
+    }
+  }
+  return bad || pend != 0;
+}
+
+// An instruction with a multi-character or non-ASCII option, on presence bits: one of its options must have every ASCII character in
+// the set (s0, s1) and, if it has a character beyond ASCII, the string(s) must have one too (`other`).  Necessary like the bits of a
+// `simple` instruction: the option is a substring of the text it is matched against.
+__device__ inline bool pairs_opt_may(const cdiff::Patterns& P, const cdiff::FlatOp& o, uint64_t s0, uint64_t s1, bool other) {
+  for (uint32_t k = 0; k < o.nopt; ++k) {
+    const cdiff::FlatOpt opt = P.opts[o.opt_begin + k];
+    bool all = true;
+    for (uint32_t i = 0; i < opt.len && all; ++i) {
+      const uint32_t cp = P.pool[opt.off + i];
+      all = cp < 64u ? (s0 >> cp) & 1ull : cp < 128u ? (s1 >> (cp - 64u)) & 1ull : other;
+    }
+    if (all) return true;
+  }
+  return false;
+}
+
 }  // namespace anx

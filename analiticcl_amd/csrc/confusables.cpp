@@ -108,9 +108,8 @@ void edit_script_ops(const uint32_t* a, size_t la, const uint32_t* b, size_t lb,
 }
 
 // the flattened pattern tables host and device read (confusables_core.hpp Patterns)
-void HostModel::rebuild_conf_tables() {
-  ConfTables& t = conf_tables;
-  t = ConfTables();
+void conf_tables_build(const std::vector<Confusable>& confusables, HostModel::ConfTables& t) {
+  t = HostModel::ConfTables();
   for (const Confusable& c : confusables) {
     cdiff::FlatConf fc;
     fc.weight = c.weight;
@@ -136,19 +135,28 @@ void HostModel::rebuild_conf_tables() {
   }
   if (t.pool.empty()) t.pool.push_back(0);
 }
-cdiff::Patterns HostModel::conf_patterns() const {
+void HostModel::rebuild_conf_tables() { conf_tables_build(confusables, conf_tables); }
+cdiff::Patterns conf_patterns_of(const HostModel::ConfTables& t) {
   cdiff::Patterns P;
-  P.conf = conf_tables.conf.data();
-  P.nconf = (uint32_t)conf_tables.conf.size();
-  P.ops = conf_tables.ops.data();
-  P.opts = conf_tables.opts.data();
-  P.pool = conf_tables.pool.data();
+  P.conf = t.conf.data();
+  P.nconf = (uint32_t)t.conf.size();
+  P.ops = t.ops.data();
+  P.opts = t.opts.data();
+  P.pool = t.pool.data();
   return P;
 }
+cdiff::Patterns HostModel::conf_patterns() const { return conf_patterns_of(conf_tables); }
 
 int HostModel::add_to_confusables(const std::string& script, double weight, std::string& err) {  // src/lib.rs:446-458
-  if (script.empty()) { err = "empty confusable pattern"; return ANX_EINVAL; }
   Confusable c;
+  if (const int rc = parse_confusable(script, weight, c, err)) return rc;
+  confusables.push_back(std::move(c));
+  rebuild_conf_tables();
+  return ANX_OK;
+}
+int parse_confusable(const std::string& script, double weight, Confusable& c, std::string& err) {
+  if (script.empty()) { err = "empty confusable pattern"; return ANX_EINVAL; }
+  c = Confusable();
   c.weight = weight;
   c.strictbegin = script.front() == '^';
   c.strictend = script.back() == '$';
@@ -182,8 +190,6 @@ int HostModel::add_to_confusables(const std::string& script, double weight, std:
       begin = i + 1;
     }
   if (c.ops.empty()) { err = "confusable pattern without instructions"; return ANX_EINVAL; }
-  confusables.push_back(std::move(c));
-  rebuild_conf_tables();
   return ANX_OK;
 }
 
@@ -283,6 +289,25 @@ double HostModel::confusable_weight_text(const char* a, size_t la, const char* b
     if (HC::confusable_weight(h.c, P, h.in, ins, h.cand, cs, &weight)) break;
   }
   return weight;
+}
+
+// confusable_weight_text's question per pattern of tables no model needs to hold (confusables_core.hpp confusable_mask): the host body
+// of k_cs_mask (csweep.hip), its fallback and what the CPU tests pin
+uint64_t confusable_mask_text(const HostModel::ConfTables& t, const char* a, size_t la, const char* b, size_t lb) {
+  if (t.conf.empty()) return 0;
+  const U in = to_u32(a, la), cand = to_u32(b, lb);
+  const cdiff::cp_t* inp = reinterpret_cast<const cdiff::cp_t*>(in.data());
+  const cdiff::cp_t* candp = reinterpret_cast<const cdiff::cp_t*>(cand.data());
+  const cdiff::CharSet ins = cdiff::charset_of_array(inp, (uint32_t)in.size()), cs = cdiff::charset_of_array(candp, (uint32_t)cand.size());
+  const cdiff::Patterns P = conf_patterns_of(t);
+  HostCtx& h = host_ctx();
+  uint64_t mask = 0;
+  for (unsigned scale = 1;; scale *= 2) {
+    h.size_for(in.size(), cand.size(), scale);
+    h.load(inp, candp);
+    if (HC::confusable_mask(h.c, P, h.in, ins, h.cand, cs, &mask)) break;
+  }
+  return mask;
 }
 
 const std::vector<uint32_t>& HostModel::vocab_gather_order() const {

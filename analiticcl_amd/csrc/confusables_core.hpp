@@ -559,11 +559,15 @@ ANX_HDS void cleanup_semantic(Ctx& c) {
 }
 
 // shortest_edit_script(a, b): the diffs [0, nd) of the context (empty texts removed); false = the context overflowed
-ANX_HDS bool edit_script(Ctx& c, const View& a, const View& b) {
+// In two steps, for a caller that runs them as separate kernels (csweep.hip): between the two, the lane memory and the context's
+// arena_used / nd / overflow carry the state.
+ANX_HDS void edit_script_begin(Ctx& c, const View& a, const View& b) {
   c.arena_used = 0;
   c.nd = 0;
   c.overflow = false;
   diff_main(c, a, b);
+}
+ANX_HDS bool edit_script_finish(Ctx& c) {
   if (!c.overflow) cleanup_semantic(c);
   if (!c.overflow) cleanup_merge(c, 0);
   if (c.overflow) return false;
@@ -572,6 +576,10 @@ ANX_HDS bool edit_script(Ctx& c, const View& a, const View& b) {
     if (d_len(c, i)) { if (w != i) d_move(c, w, i); ++w; }
   c.nd = w;
   return true;
+}
+ANX_HDS bool edit_script(Ctx& c, const View& a, const View& b) {
+  edit_script_begin(c, a, b);
+  return edit_script_finish(c);
 }
 
 ANX_HDS CharSet charset_of(const Ctx& c, const View& s) {
@@ -671,6 +679,33 @@ ANX_HDS bool confusable_weight(Ctx& c, const Patterns& P, const View& in, const 
   for (uint32_t j = 0; j < P.nconf; ++j)
     if ((j >= 64 || ((live >> j) & 1ull)) && found_in(c, P, P.conf[j])) w *= P.conf[j].weight;
   *weight = w;
+  return true;
+}
+// confusable_weight's question per pattern: bit j of *mask = pattern j (j < 64; later ones are not looked at) is found in the edit
+// script of (input, candidate); 0 when no pattern can match (the script is then not computed).  The weight of any assignment of
+// weights to the patterns is the product over the set bits in ascending order.  false = the context overflowed.
+// Its steps: the patterns that can match at all (may_match, a necessary condition of found_in), and of those the ones found in the
+// script the context holds.
+ANX_HDS uint64_t mask_live(const Ctx& c, const Patterns& P, const View& in, const CharSet& ins, const View& cand, const CharSet& cs) {
+  const uint32_t np = P.nconf < 64u ? P.nconf : 64u;
+  uint64_t live = 0;
+  for (uint32_t j = 0; j < np; ++j)
+    if (may_match(c, P, P.conf[j], in, ins, cand, cs)) live |= 1ull << j;
+  return live;
+}
+ANX_HDS uint64_t mask_found(const Ctx& c, const Patterns& P, uint64_t live) {
+  const uint32_t np = P.nconf < 64u ? P.nconf : 64u;
+  uint64_t found = 0;
+  for (uint32_t j = 0; j < np; ++j)
+    if (((live >> j) & 1ull) && found_in(c, P, P.conf[j])) found |= 1ull << j;
+  return found;
+}
+ANX_HDS bool confusable_mask(Ctx& c, const Patterns& P, const View& in, const CharSet& ins, const View& cand, const CharSet& cs, uint64_t* mask) {
+  *mask = 0;
+  const uint64_t live = mask_live(c, P, in, ins, cand, cs);
+  if (!live) return true;
+  if (!edit_script(c, in, cand)) return false;
+  *mask = mask_found(c, P, live);
   return true;
 }
 };  // Core<S>

@@ -129,6 +129,20 @@ struct PairConfRun {
 };
 size_t conf_pairs_sort_tmp_bytes(uint32_t n);
 int conf_launch_pairs(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, const PairConfRun& r, std::string& err);
+// What the confusable sweep (csweep.hip) uses of conf.hip.  conf_vocab_view: the replica's copy of the vocabulary (code points,
+// offsets [V + 1], presence bits [V]) and the alphabetic ranges, uploaded on first use -- the vocabulary half of what conf_launch
+// ensures, for a model that owns no list.  conf_sort_enqueue: conf_launch_pairs' radix pass over 13 key bits (tmp of
+// conf_pairs_sort_tmp_bytes(n)).  conf_apply_late_enqueue: k_conf_apply_late (weight, stable re-sort, cutoff, new count) over rows
+// ranked by rank_rows_enqueue: weight[soff[s] + j] belongs to ranked row j of query s.
+struct ConfVocabView {
+  const uint32_t* v_pool; const uint32_t* v_off; const cdiff::CharSet* v_cs; uint32_t nvocab;
+  const uint32_t (*alpha)[2]; uint32_t nalpha;
+};
+int conf_vocab_view(const HostModel& m, const DeviceLexicon* dl, ConfVocabView* v, std::string& err);
+int conf_sort_enqueue(void* tmp, size_t tmp_bytes, const uint32_t* keys, uint32_t* keys_out, const uint32_t* vals, uint32_t* vals_out, uint32_t n, hipStream_t st,
+                      std::string& err);
+void conf_apply_late_enqueue(hipStream_t st, uint32_t nq, uint32_t row_cap, const uint32_t* soff, DevRow* r_rows, const double* weight, const uint32_t* overflow,
+                             double cutoff_threshold, float freq_weight, uint32_t* r_count);
 // pairs_encode_launch with the caller's thresholds behind meta's k / d bits (anx_evaluate_gold reads them there)
 int pairs_encode_launch_thr(const HostModel& m, const DeviceLexicon* dl, const SmallEnc& e, const uint8_t* blob, const uint32_t* off, uint32_t n,
                             const anx_params& thr, hipStream_t st, std::string& err);

@@ -345,6 +345,14 @@ class HostModel {
   void build_lm();
 };
 
+// The pattern parser, the flattening and the matcher without a model that holds the list (confusables.cpp): what add_to_confusables and
+// rebuild_conf_tables run, and what anx_evaluate_sweep_confusables runs on candidate patterns.  confusable_mask_text: bit j = pattern j
+// of the tables is found in the edit script of (a -> b), both decoded as confusable_weight_text decodes them.
+int parse_confusable(const std::string& script, double weight, Confusable& out, std::string& err);
+void conf_tables_build(const std::vector<Confusable>& list, HostModel::ConfTables& out);
+cdiff::Patterns conf_patterns_of(const HostModel::ConfTables& t);
+uint64_t confusable_mask_text(const HostModel::ConfTables& t, const char* a, size_t la, const char* b, size_t lb);
+
 // threshold clamps of find_variants (src/lib.rs:982-994, 1000-1012)
 int index_read_tag(const std::string& path, std::string* tag, std::string& err);  // index_cache.cpp
 int clamp_threshold(const anx_threshold& t, int len, int absolute_max);

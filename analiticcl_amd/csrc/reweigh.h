@@ -24,6 +24,10 @@ int reweigh_group_begin(const SweepChunkView& v, const anx_params& group, const 
 // want_records): the n records anx_evaluate_gold writes under p on a model created with w.  baseline: this is set 0 (it writes the
 // rank-0 byte per pair every other set compares with).  One download, one wait.
 int reweigh_group_set(RwGroup* g, const anx_params& p, const anx_weights& w, bool baseline, anx_gold_summary* sum, anx_gold_eval* out, std::string& err);
+// The end of a set by itself (reweigh_group_set ends in it; anx_evaluate_sweep_confusables, csweep.hip, ranks the group's rows its own way
+// first): k_rw_classify over the ranked rows the group holds, the direct pair's score under w for THRESHOLD, the reduction, one download,
+// one wait.  The group's summary words were cleared on the stream before; *bytes: what came down.
+int reweigh_group_finish(RwGroup* g, const anx_params& p, const anx_weights& w, bool baseline, anx_gold_summary* sum, anx_gold_eval* out, size_t* bytes, std::string& err);
 size_t reweigh_group_rows(const RwGroup* g);
 void reweigh_group_end(RwGroup* g);
 

@@ -44,6 +44,7 @@ namespace anx {
 #include "kernels_common.hpp"
 #include "kernels_gold.hpp"
 #include "gold_host.hpp"
+#include "reweigh_shared.hpp"
 
 namespace {
 std::atomic<uint64_t> g_stats[RW_NSTATS];
@@ -54,38 +55,6 @@ void reweigh_stats_add(int which, uint64_t v) {
 }
 void reweigh_stats(uint64_t out[RW_NSTATS]) {
   for (int i = 0; i < RW_NSTATS; ++i) out[i] = g_stats[i].load(std::memory_order_relaxed);
-}
-
-// the score's operands for one set
-struct RwWeights {
-  double w_ld, w_lcs, w_prefix, w_suffix, w_case, w_sum;
-  const double* quot;  // [33][33] x / L as the host divides (DeviceLexicon::quot), or nullptr
-};
-// src/lib.rs:1433-1452 with input_length = la, as score_finish (kernels_score.hpp) and xm_score (kernels_explain.hpp) write it
-__device__ inline double rw_score(const RwWeights& k, uint32_t la, uint32_t ld, uint32_t lcs, uint32_t pre, uint32_t suf, uint32_t samecase) {
-  const double L = (double)la;
-  const bool tab = k.quot && la <= 32u;
-  auto over_L = [&](uint32_t x) { return (tab && x <= 32u) ? k.quot[x * 33u + la] : (double)x / L; };
-  const double distance_score = ld > la ? 0.0 : 1.0 - over_L(ld);
-  const double lcs_score = over_L(lcs);
-  const double prefix_score = over_L(pre);
-  const double suffix_score = over_L(suf);
-  const double num = k.w_ld * distance_score + k.w_lcs * lcs_score + k.w_prefix * prefix_score + k.w_suffix * suffix_score + (samecase ? k.w_case : 0.0);
-  return k.w_sum == 1.0 ? num : num / k.w_sum;  // x / 1.0 == x
-}
-
-// The run of equal keys among neighbouring lanes this lane lies in (survivor_counts, kernels_score.hpp): its first and last lane and
-// the mask of its lanes.  Every lane of the wave calls this.
-struct RwRun { uint32_t start, end; unsigned long long lanes; };
-__device__ __forceinline__ RwRun rw_run(uint32_t key) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t kprev = (uint32_t)__shfl_up((int)key, 1);
-  const bool head = lane == 0u || kprev != key;
-  const unsigned long long hm = __ballot(head);
-  const uint32_t start = 63u - (uint32_t)__clzll((long long)(hm & ((2ull << lane) - 1ull)));  // (lane 0 is a head)
-  const unsigned long long above = lane == 63u ? 0ull : hm & ~((2ull << lane) - 1ull);
-  const uint32_t end = above ? (uint32_t)__ffsll((long long)above) - 2u : 63u;
-  return RwRun{start, end, ((2ull << end) - 1ull) & ~((1ull << start) - 1ull)};
 }
 
 // one compact export section of the base run with the measures of its rows
@@ -260,23 +229,6 @@ __global__ __launch_bounds__(GOLD_BLOCK) void k_rw_classify(RwClassArgs k) {
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
-struct RwGroup {
-  SweepChunkView v{};
-  size_t n = 0, R = 0;
-  PoolBlocks blocks;               // pool blocks of the group, back to the pool at its end
-  void* h_down = nullptr;          // pinned: the summary | the records
-  uint4* info = nullptr;
-  uint2* meas = nullptr;
-  double *score = nullptr, *t_key = nullptr;
-  uint32_t *cnt = nullptr, *soff = nullptr, *cur = nullptr, *maxf = nullptr, *tmp = nullptr, *r_count = nullptr, *ovf = nullptr, *pre = nullptr;
-  SurvRow* c_rows = nullptr;
-  DevRow* r_rows = nullptr;
-  unsigned long long* d_sum = nullptr;
-  uint4* d_out = nullptr;
-  template <typename T>
-  int get(T** p, size_t count, std::string& err) { return blocks.get(p, count, err); }
-};
-
 size_t reweigh_group_rows(const RwGroup* g) { return g->R; }
 
 void reweigh_group_end(RwGroup* g) {
@@ -357,6 +309,25 @@ int reweigh_group_begin(const SweepChunkView& v, const anx_params& group, const 
   return ANX_OK;
 }
 
+// The end of a set, for reweigh_group_set and for the confusable sweep (csweep.hip): the pairs classified from the ranked rows in
+// r_rows / r_count, THRESHOLD from the direct pair's score under w, the reduction, the download and its wait.  d_sum was cleared on the stream.
+int reweigh_group_finish(RwGroup* g, const anx_params& p, const anx_weights& w, bool baseline, anx_gold_summary* sum, anx_gold_eval* out, size_t* bytes, std::string& err) {
+  const SweepChunkView& v = g->v;
+  const size_t n = g->n, R = g->R;
+  hipStream_t st = reinterpret_cast<hipStream_t>(v.stream);
+  RwClassArgs c{};
+  c.n = (uint32_t)n; c.row_cap = (uint32_t)R; c.pair = v.pair; c.gid = v.gid; c.pre = g->pre; c.soff = g->soff; c.r_count = g->r_count; c.r_rows = g->r_rows;
+  c.w = RwWeights{w.ld, w.lcs, w.prefix, w.suffix, w.casew, w.ld + w.lcs + w.prefix + w.suffix + w.casew, v.dl->quot};  // w_sum: src/types.rs:69-73, as launch_plan.hpp
+  c.score_threshold = p.score_threshold; c.at1_base = v.at1; c.baseline = baseline ? 1 : 0; c.summary = g->d_sum; c.out = out ? g->d_out : nullptr;
+  {
+    const int kt = ktimer_begin("k_rw_classify", st);
+    hipLaunchKernelGGL(k_rw_classify, dim3(gold_grid(n)), dim3(GOLD_BLOCK), 0, st, c);
+    ktimer_end(kt, st);
+  }
+  HIP_TRY(hipGetLastError());
+  return gold_set_download(static_cast<char*>(g->h_down), g->d_sum, g->d_out, n, st, sum, out, bytes, err);
+}
+
 int reweigh_group_set(RwGroup* g, const anx_params& p, const anx_weights& w, bool baseline, anx_gold_summary* sum, anx_gold_eval* out, std::string& err) {
   if (out && !g->d_out) { err = "reweigh_group_set: the group keeps no record buffer"; return ANX_EINVAL; }
   const SweepChunkView& v = g->v;
@@ -388,17 +359,8 @@ int reweigh_group_set(RwGroup* g, const anx_params& p, const anx_weights& w, boo
                       g->r_count, (uint32_t)R, g->ovf);
     ktimer_end(kt, st);
   }
-  RwClassArgs c{};
-  c.n = (uint32_t)n; c.row_cap = (uint32_t)R; c.pair = v.pair; c.gid = v.gid; c.pre = g->pre; c.soff = g->soff; c.r_count = g->r_count; c.r_rows = g->r_rows;
-  c.w = k.w; c.score_threshold = p.score_threshold; c.at1_base = v.at1; c.baseline = baseline ? 1 : 0; c.summary = g->d_sum; c.out = out ? g->d_out : nullptr;
-  {
-    const int kt = ktimer_begin("k_rw_classify", st);
-    hipLaunchKernelGGL(k_rw_classify, dim3(gold_grid(n)), dim3(GOLD_BLOCK), 0, st, c);
-    ktimer_end(kt, st);
-  }
-  HIP_TRY(hipGetLastError());
   size_t bytes = 0;
-  if (int rc = gold_set_download(static_cast<char*>(g->h_down), g->d_sum, g->d_out, n, st, sum, out, &bytes, err)) return rc;
+  if (int rc = reweigh_group_finish(g, p, w, baseline, sum, out, &bytes, err)) return rc;
   reweigh_stats_add(RW_BYTES_DOWN, bytes);
   reweigh_stats_add(RW_ROWS_RESCORED, R);
   return ANX_OK;

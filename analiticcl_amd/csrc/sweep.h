@@ -37,6 +37,8 @@ struct SweepChunkView {
   const uint32_t* gid;                      // [n] gold id or 0xFFFFFFFF
   const uint8_t* vflags;                    // [V]
   uint8_t* at1;                             // [n] gold at rank 0 under set 0
+  const uint8_t* blob;                      // the chunk's 2 n strings as uploaded: input i = blob[off[i] .. off[i + 1] - 1)
+  const uint32_t* off;                      // [2 n + 1]
 };
 void sweep_chunk_view(const SweepChunk* c, SweepChunkView* v);
 

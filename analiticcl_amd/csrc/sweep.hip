@@ -219,7 +219,7 @@ int sweep_chunk_pairs(SweepChunk* c, anx_pair_score* pairs, std::string& err) {
 }
 
 void sweep_chunk_view(const SweepChunk* c, SweepChunkView* v) {
-  *v = SweepChunkView{c->m, c->dl, c->n, c->sc.st, c->pd.e.meta, c->pd.e.kind, c->pd.e.cv, c->pd.e.bits, c->pd.e.sig, c->pd.out, c->d_gid, c->d_vflags, c->d_at1};
+  *v = SweepChunkView{c->m, c->dl, c->n, c->sc.st, c->pd.e.meta, c->pd.e.kind, c->pd.e.cv, c->pd.e.bits, c->pd.e.sig, c->pd.out, c->d_gid, c->d_vflags, c->d_at1, c->pd.blob, c->pd.off};
 }
 
 void sweep_chunk_end(SweepChunk* c) {

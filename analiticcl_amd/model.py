@@ -986,6 +986,99 @@ class VariantModel:
         L.check(L.lib().anx_debug_weight_sweep_stats(out, len(keys)))
         return {k: int(out[i]) for i, k in enumerate(keys)}
 
+    # -- confusable sweep --------------------------------------------------------------------------------
+    CONF_SWEEP_MAX_PATTERNS = 64
+
+    def evaluate_sweep_confusables_arrays(self, inputs: Sequence[str], gold: Sequence[str], patterns: Sequence[str],
+                                          params_list: Sequence[SearchParameters], weights_list: Sequence[Sequence[float]],
+                                          early_list: Optional[Sequence[bool]] = None, with_records: bool = False, packed: bool = True,
+                                          chunk: Optional[int] = None):
+        """anx_evaluate_sweep_confusables: evaluate_sweep_arrays for candidate confusable patterns -- set s is (params_list[s],
+        weights_list[s] = one weight per pattern, early_list[s]) and its summary is what evaluate_arrays gives on a model with the
+        same alphabet, lexicons and score weights whose confusable list is patterns[j] with weight weights_list[s][j], with
+        set_confusables_before_pruning() iff early_list[s] (None: every set is late).  A weight of exactly 1.0 switches a pattern
+        off.  One batch run and one edit-script pass per distinct (max_anagram_distance, max_edit_distance, stop_criterion) serve
+        every set.  Models without a variant list and without a confusable list of their own; at most 64 patterns, 256 sets.
+        Returns the summaries (SUMMARY_DTYPE), or (summaries, records[P][n]) with with_records.  packed = False: the pointer form;
+        chunk: the test hook (pointer form)."""
+        import numpy as np
+        n, P, J = len(inputs), len(params_list), len(patterns)
+        if len(gold) != n:
+            raise ValueError("evaluate_sweep_confusables: inputs and gold differ in length")
+        if len(weights_list) != P:
+            raise ValueError("evaluate_sweep_confusables: params_list and weights_list differ in length")
+        if early_list is not None and len(early_list) != P:
+            raise ValueError("evaluate_sweep_confusables: params_list and early_list differ in length")
+        if any(len(w) != J for w in weights_list):
+            raise ValueError("evaluate_sweep_confusables: every set needs one weight per pattern")
+        sums = np.zeros(max(P, 1), dtype=np.dtype(self.SUMMARY_DTYPE))
+        sptr = sums.ctypes.data_as(C.POINTER(L.GoldSummary))
+        sets = (L.Params * max(P, 1))(*[p._c() for p in params_list])
+        pats = (C.c_char_p * max(J, 1))(*[_b(t) for t in patterns])
+        ws = np.ascontiguousarray(np.asarray([[float(x) for x in w] for w in weights_list], dtype=np.float64).reshape(P, J))
+        wptr = ws.ctypes.data_as(C.POINTER(C.c_double)) if ws.size else (C.c_double * 1)(1.0)
+        early = None if early_list is None else (C.c_uint8 * max(P, 1))(*[1 if e else 0 for e in early_list])
+        rec = np.zeros((max(P, 1), max(n, 1)), dtype=np.dtype(self.GOLD_DTYPE)) if with_records else None   # [P][n] set-major (n == 0: untouched)
+        optr = rec.ctypes.data_as(C.POINTER(L.GoldEval)) if with_records else None
+        if packed and chunk is None:
+            ba, bg = _pack(inputs), _pack(gold)
+            L.check(L.lib().anx_evaluate_sweep_confusables_packed(self.h, ba, len(ba), bg, len(bg), n, pats, J, sets, wptr, early, P, sptr, optr))
+        else:
+            aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
+            ag = (C.c_char_p * max(n, 1))(*[_b(t) for t in gold])
+            if chunk is None:
+                L.check(L.lib().anx_evaluate_sweep_confusables(self.h, aa, ag, n, pats, J, sets, wptr, early, P, sptr, optr))
+            else:
+                L.check(L.lib().anx_debug_evaluate_sweep_confusables_chunk(self.h, aa, ag, n, pats, J, sets, wptr, early, P, sptr, optr, int(chunk)))
+        return (sums[:P], rec[:P, :n]) if with_records else sums[:P]
+
+    def evaluate_sweep_confusables(self, inputs: Sequence[str], gold: Sequence[str], patterns: Sequence[str],
+                                   params_list: Sequence[SearchParameters], weights_list: Sequence[Sequence[float]],
+                                   early_list: Optional[Sequence[bool]] = None, records: bool = False):
+        """evaluate_sweep_confusables_arrays as one dict per set (sweep_summary), the set's weights under "confusable_weights" (pattern ->
+        weight, the patterns at 1.0 left out) and its mode under "early".  records: returns (dicts, records[P][n])."""
+        got = self.evaluate_sweep_confusables_arrays(inputs, gold, patterns, params_list, weights_list, early_list, with_records=records)
+        sums = got[0] if records else got
+        out = [dict(self.sweep_summary(s), confusable_weights={p: float(x) for p, x in zip(patterns, w) if float(x) != 1.0},
+                    early=bool(early_list[i]) if early_list is not None else False)
+               for i, (s, w) in enumerate(zip(sums, weights_list))]
+        return (out, got[1]) if records else out
+
+    def sweep_conf_masks(self, inputs: Sequence[str], patterns: Sequence[str], params: SearchParameters):
+        """anx_debug_sweep_conf_masks (test hook): the base rows of `inputs` under params' k / d / stop criterion as three numpy arrays
+        (input index, vocabulary id, mask): bit j of the mask = patterns[j] is found in the edit script of (input, vocabulary item)."""
+        import numpy as np
+        n, J = len(inputs), len(patterns)
+        aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
+        pats = (C.c_char_p * max(J, 1))(*[_b(t) for t in patterns])
+        pp, pv, pm, rows = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.c_size_t(0)
+        cp = params._c()
+        L.check(L.lib().anx_debug_sweep_conf_masks(self.h, aa, n, pats, J, C.byref(cp), C.byref(pp), C.byref(pv), C.byref(pm), C.byref(rows)))
+        try:
+            r = rows.value
+            return (np.array(pp[:r], dtype=np.uint32), np.array(pv[:r], dtype=np.uint32), np.array(pm[:r], dtype=np.uint64))
+        finally:
+            for p in (pp, pv, pm):
+                L.lib().anx_string_free(C.cast(p, C.c_void_p))
+
+    @staticmethod
+    def conf_mask_text(patterns: Sequence[str], a: str, b: str) -> int:
+        """anx_debug_conf_mask_text: the host body of the mask kernel -- bit j = patterns[j] is found in the edit script of (a -> b)."""
+        J = len(patterns)
+        pats = (C.c_char_p * max(J, 1))(*[_b(t) for t in patterns])
+        out = C.c_uint64(0)
+        L.check(L.lib().anx_debug_conf_mask_text(pats, J, _b(a), _b(b), C.byref(out)))
+        return int(out.value)
+
+    @staticmethod
+    def conf_sweep_stats() -> dict:
+        """anx_debug_conf_sweep_stats: running totals of the confusable-sweep calls since process start."""
+        keys = ("calls", "chunks", "groups", "sets", "pair_passes", "batch_runs", "base_rows", "rows_listed", "rows_patched", "rows_host_mode",
+                "bytes_down")
+        out = (C.c_uint64 * len(keys))()
+        L.check(L.lib().anx_debug_conf_sweep_stats(out, len(keys)))
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
     def query_output(self, inputs: Sequence[str], params: SearchParameters, json: bool = False,
                      output_lexmatch: bool = False, first_seqnr: int = 1) -> str:
         """One device batch + the text `analiticcl query` prints for it (anx_format_query_output: the TSV lines or JSON

@@ -49,7 +49,9 @@ extern "C" {
  *    anx_debug_evaluate_sweep_chunk / anx_debug_sweep_stats: several parameter sets over the same gold pairs (additive); the test hooks
  *    anx_debug_lattice_decode (with the struct anx_lattice_debug) and anx_debug_portable_log (additive); the test hook
  *    anx_debug_scan_pairs and its options struct anx_debug_scan_opts: additive; anx_evaluate_sweep_weights / _packed and the hooks
- *    anx_debug_evaluate_sweep_weights_chunk / anx_debug_weight_sweep_stats: sets that also differ in the score weights (additive). */
+ *    anx_debug_evaluate_sweep_weights_chunk / anx_debug_weight_sweep_stats: sets that also differ in the score weights (additive);
+ *    anx_evaluate_sweep_confusables / _packed and the hooks anx_debug_evaluate_sweep_confusables_chunk / anx_debug_sweep_conf_masks /
+ *    anx_debug_conf_mask_text / anx_debug_conf_sweep_stats: candidate confusable patterns with a weight per set (additive). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -892,6 +894,54 @@ int anx_debug_evaluate_sweep_weights_chunk(anx_model *, const char *const *input
  * chunk), [3] sets re-ranked (per chunk), [4] pair-side passes, [5] batch runs, [6] base rows re-scored (rows x sets), [7] bytes the
  * pass downloaded (624 per set and chunk, + 32 per pair and set with `out`). */
 int anx_debug_weight_sweep_stats(uint64_t *out, int n);
+
+/* ---- confusable sweep: candidate confusable patterns with one weight per pattern and set, without a model or a batch run per set -------
+ * Set s is (sets[s], weights[s * n_patterns .. + n_patterns), early[s]).  summaries[s], and with out the records ([n_sets][n], set-major),
+ * equal field by field what anx_evaluate_gold(model_s, inputs, gold, n, &sets[s], ...) writes, model_s being a model with the same
+ * alphabet, lexicons and score weights whose confusable list is patterns[j] with weight weights[s][j], added in order with
+ * anx_model_add_to_confusables, and anx_model_set_confusables_before_pruning iff early[s] (early == NULL: every set is late).  A weight
+ * of exactly 1.0 switches a pattern off (x * 1.0 == x).  gained_at_1 / lost_at_1 compare with set 0, so a set 0 of all ones is the plain
+ * baseline.  The model's score weights are the model's: this call does not sweep them.  There is no `pairs` output.
+ * How: the candidates of an input, their measures and their unweighted scores do not depend on the list, and whether pattern j is found
+ * in the edit script of (input, candidate) depends on the two texts alone; the weights enter as a product over the matching patterns in
+ * list order.  So per chunk and group of (max_anagram_distance, max_edit_distance, stop_at_exact_match != 0) ONE base run yields every
+ * instance (as for anx_evaluate_sweep_weights), csweep.hip scores them once and computes ONE 64-bit match mask per instance (a screen on
+ * presence bits, then one edit script per row that a pattern can match; a row the device's lane memory cannot hold -- a side above 64
+ * code points -- is done by the host), and per set applies the set's weights to the masks: early to the kept rows before k_rank, late
+ * to the cropped list before the re-sort and the cutoff the batch path runs.  No batch run and no edit script per set; a download of
+ * 624 bytes per set and chunk (+ 32 per pair with out).  Under ANX_CONFUSABLES=host every mask is computed on the host.
+ * Errors, each ANX_EINVAL before the device is asked for: NULL sets / weights / patterns / summaries; n_patterns outside 1 .. 64
+ * (ANX_SWEEP_CONF_MAX_PATTERNS); n_sets outside 1 .. ANX_SWEEP_MAX_SETS; a pattern the list parser rejects (the message names its
+ * index); a weight that is not finite or not above 0; a model with a variant list; a model with a confusable list of its own (the
+ * candidates would multiply on top of it: not built); a model whose own score weights are not finite or sum to 0.  n == 0 zeroes the
+ * summaries and returns ANX_OK without a build or a device.  Otherwise anx_evaluate_gold's limits: replica 0, the learn lock, and
+ * ANX_ELIMIT for more than 2^31 base rows in one chunk and group. */
+#define ANX_SWEEP_CONF_MAX_PATTERNS 64
+int anx_evaluate_sweep_confusables(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const char *const *patterns,
+                                   size_t n_patterns, const anx_params *sets, const double *weights /* [n_sets][n_patterns] */,
+                                   const uint8_t *early /* [n_sets], may be NULL = all late */, size_t n_sets, anx_gold_summary *summaries,
+                                   anx_gold_eval *out /* [n_sets][n] or NULL */);
+int anx_evaluate_sweep_confusables_packed(anx_model *, const char *blob_in, size_t len_in, const char *blob_gold, size_t len_gold, size_t n,
+                                          const char *const *patterns, size_t n_patterns, const anx_params *sets, const double *weights,
+                                          const uint8_t *early, size_t n_sets, anx_gold_summary *summaries, anx_gold_eval *out);
+/* Test hook: the pointer form with a caller-chosen chunk size (1 .. 2^20 pairs). */
+int anx_debug_evaluate_sweep_confusables_chunk(anx_model *, const char *const *inputs, const char *const *gold, size_t n,
+                                               const char *const *patterns, size_t n_patterns, const anx_params *sets, const double *weights,
+                                               const uint8_t *early, size_t n_sets, anx_gold_summary *summaries, anx_gold_eval *out,
+                                               size_t chunk);
+/* Test hook: the mask pass alone.  The base rows of `inputs` under group's max_anagram_distance / max_edit_distance / stop_at_exact_match,
+ * in the order the pass holds them: pair[r] = input index, vocab[r] = vocabulary id, mask[r] bit j = patterns[j] is found in the edit
+ * script of (inputs[pair[r]], vocabulary item vocab[r]).  n <= 2^20.  The three arrays are malloc'ed: free() each. */
+int anx_debug_sweep_conf_masks(anx_model *, const char *const *inputs, size_t n, const char *const *patterns, size_t n_patterns,
+                               const anx_params *group, uint32_t **pair, uint32_t **vocab, uint64_t **mask, size_t *rows);
+/* The host body of the mask kernel for one pair of texts (no model, no device): bit j of *mask = patterns[j] is found in the edit script
+ * of (a -> b). */
+int anx_debug_conf_mask_text(const char *const *patterns, size_t n_patterns, const char *a, const char *b, uint64_t *mask);
+/* Running totals of the confusable-sweep calls since process start, the first min(n, 11) of: [0] calls, [1] chunks, [2] groups,
+ * [3] sets, [4] pair-side passes, [5] batch runs (one per chunk and group), [6] base rows, [7] rows listed for an edit script (counted
+ * when a group's mask pass ends: a set adds none), [8] of those, rows the host computed because the device could not hold them,
+ * [9] rows the host computed under ANX_CONFUSABLES=host, [10] bytes the sets downloaded. */
+int anx_debug_conf_sweep_stats(uint64_t *out, int n);
 
 /* ---- anx_mine_confusables: confusable patterns from (observed, correct) string pairs ---------------------------------------------------
  * For every pair (a[i], b[i]) the change sites of shortest_edit_script(a[i], b[i]) -- a site is a maximal run of consecutive non-`=`
