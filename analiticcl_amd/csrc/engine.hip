@@ -5,9 +5,10 @@
 //   gather_instances        (src/lib.rs:1311-1402, src/distance.rs)  -> k_filter_score, k_score_fast8,
 //                                                                      k_score_pairs                  (kernels_score.hpp)
 //   score_and_rank          (src/lib.rs:1405-1653, src/types.rs:334-365) -> the same + k_compact, k_rank (kernels_rank.hpp)
-// This file: device memory pool, lexicon upload, batch encoding / tiling, the launch sequence, result download.
-// One translation unit (the kernel headers are included below).  Integer work only: no MFMA.  Wave = 64 lanes
-// everywhere.  See DESIGN.md for layout and rooflines.
+// This file: lexicon upload, batch encoding / tiling, the launch sequence of a run and its read-back, the small call
+// (small_path.hpp) and the test doors (debug_doors.hpp).  The device memory pool, the streams, the shells and the kernel timer are
+// runtime.hip's; the ranked rows leave the device through results.hip.  One translation unit for every kernel of a run (the kernel
+// headers are included below).  Integer work only: no MFMA.  Wave = 64 lanes everywhere.  See DESIGN.md for layout and rooflines.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,11 +19,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
-#include <unordered_map>
-#include <numeric>
 #include <thread>
 #include <type_traits>
 
@@ -37,7 +35,6 @@ namespace anx {
 #include "kernels_prefix.hpp"
 #include "kernels_score.hpp"
 #include "kernels_rank.hpp"
-#include "kernels_explain.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // Host side
@@ -46,358 +43,6 @@ namespace anx {
 enum { HR_RCTR = 0, HR_SCTR = SCAN_REGIONS * RC_STRIDE, HR_LCTR = 2 * SCAN_REGIONS * RC_STRIDE, HR_CTR = 5 * SCAN_REGIONS * RC_STRIDE,
        HR_TOTAL_SURV = HR_CTR + CTR_N, HR_TOTAL_RESULTS = HR_TOTAL_SURV + 1, HR_CONF = HR_TOTAL_RESULTS + 1 /* 2 words */, HR_N = HR_CONF + 2 };
 constexpr size_t HR_COLD_OFF = (HR_N * sizeof(uint32_t) + 63) & ~(size_t)63;  // byte offset of the FsCold staging copy in Batch::h_read
-static void shells_destroy(int device);
-static void small_ctxs_destroy(int device);
-
-int device_count(std::string& err) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess) {
-    err = std::string("hipGetDeviceCount: ") + hipGetErrorString(e);
-    return 0;
-  }
-  return n;
-}
-
-// Device memory pool.  A batch needs several GB of scratch (pair list, per-slot arrays, survivor rows); hipMalloc /
-// hipFree of that size cost 100-300 ms per call, far more than the 6 ms the kernels take for a million queries, and
-// search mode issues one batch per n-gram order.  Freed blocks are kept per device and handed out again (best fit,
-// at most 2x the request); lexicon_free() of the last lexicon on a device returns them to the driver.
-struct SmallCtx;  // small_path.hpp
-namespace {
-struct DevPool {
-  std::mutex mu;
-  std::multimap<size_t, void*> free_blocks;        // size -> block
-  std::unordered_map<void*, size_t> size_of;       // every live or cached block of this pool
-  size_t cached = 0;
-  std::unordered_map<void*, uint64_t> freed_at;   // cached blocks: when they came back (a full cache lets its oldest blocks go)
-  uint64_t clock = 0;
-  int lexicons = 0;
-  std::vector<hipStream_t> idle_streams;           // non-blocking streams of the device-side encoder, handed out per call
-  hipStream_t run_streams[2] = {nullptr, nullptr}; // the library's own streams for asynchronous runs (batch_run_async)
-  unsigned run_counter = 0;
-  std::vector<BatchShell> shells;                  // events + pinned read-back blocks of freed batches (batch_free), handed to the next batch
-  std::vector<SmallCtx*> small_idle;               // contexts of the small call (small_path.hpp), checked out per call
-  std::vector<std::pair<void*, size_t>> doomed;    // blocks evicted from the cache, not yet handed to hipFree (pool_free: hipFree waits for the device)
-  size_t doomed_bytes = 0;
-};
-// bytes of freed blocks kept per device (MI355X: 288 GB HBM; a 1 M-query batch holds 3-6 GB of scratch).  ANX_POOL_CACHE_MB
-// overrides the default; anx_device_pool_trim() hands the cache back to the driver at any time.
-static size_t pool_cache_limit() {
-  static const size_t lim = []() {
-    const char* e = getenv("ANX_POOL_CACHE_MB");
-    const long long v = e ? atoll(e) : -1;
-    return v >= 0 ? (size_t)v << 20 : (size_t)96 << 30;   // (32 GB until round 6: six un-hinted first runs of a million queries, 7 GB each, outgrew it)
-  }();
-  return lim;
-}
-DevPool& pool_of(int device) {
-  static DevPool pools[64];
-  return pools[device >= 0 && device < 64 ? device : 0];
-}
-}  // namespace
-// A private non-blocking stream for one encoder call (encode.hip): on the legacy NULL stream every encode would serialise with
-// the in-flight batches of other host threads that run on blocking streams.  Streams are kept per device and reused.
-// A thread may bring its own encoder stream (anx_pipeline's encode thread: created together with the pipeline's run streams, so that
-// the runtime's least-used-hardware-queue rule puts the three on different queues -- see anx_pipeline_new).
-static thread_local hipStream_t t_encoder_stream = nullptr;
-// A non-blocking stream on the current device.  high = the device's highest stream priority: the encoder of batch i + 1 (and search
-// mode's lattice-build kernels) are chains of ~45 short dependent launches that run beside the scan / scoring kernels of batch i --
-// tens of thousands of waves queued on streams of normal priority; at equal priority every launch of the chain waits its turn behind
-// them (round 5: the encoder "under" a run took the run's length), at high priority the dispatcher serves its few workgroups first.
-// ANX_ENC_PRIORITY=0: normal priority (A/B).
-void* make_stream(bool high) {
-  hipStream_t s = nullptr;
-  int least = 0, greatest = 0;
-  if (high && switches().enc_priority && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least) {
-    if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest) == hipSuccess) return s;
-    (void)hipGetLastError();
-  }
-  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  return s;
-}
-void encoder_stream_set_override(void* s) { t_encoder_stream = reinterpret_cast<hipStream_t>(s); }
-hipStream_t encoder_stream_acquire(int device) {
-  if (t_encoder_stream) return t_encoder_stream;
-  DevPool& pl = pool_of(device);
-  {
-    std::lock_guard<std::mutex> g(pl.mu);
-    if (!pl.idle_streams.empty()) { hipStream_t s = pl.idle_streams.back(); pl.idle_streams.pop_back(); return s; }
-  }
-  return static_cast<hipStream_t>(make_stream(true));  // nullptr = the NULL stream: still correct
-}
-void encoder_stream_release(int device, hipStream_t s) {
-  if (!s || s == t_encoder_stream) return;
-  DevPool& pl = pool_of(device);
-  std::lock_guard<std::mutex> g(pl.mu);
-  pl.idle_streams.push_back(s);
-}
-// The calling thread's current HIP device is not ours to change: entry points that run on a CALLER's thread (model upload / free,
-// stream create / destroy, pool trim) switch to the replica's device and put the caller's back when they return.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); } }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-// One stream for everything a host thread sends to the device during a stretch of work (a part of a search-mode call: its batches'
-// encodes and runs, its lattices): taken from the encoder's pool, installed as the thread's encoder stream, handed back at the end.
-void* thread_stream_begin(int device) {
-  if (t_encoder_stream) return nullptr;  // the thread brought its own
-  DeviceGuard guard;  // (the pool may have to create the stream: on the replica's device, not on the thread's current one)
-  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  hipStream_t s = encoder_stream_acquire(device);
-  t_encoder_stream = s;
-  return s;
-}
-void thread_stream_end(int device, void* s) {
-  if (!s) return;
-  t_encoder_stream = nullptr;
-  encoder_stream_release(device, reinterpret_cast<hipStream_t>(s));
-}
-// streams of the replicas of a multi-device model (capi.cpp owns them; HIP stays behind this file)
-void* stream_create(int device, std::string& err, bool high_priority) {
-  DeviceGuard guard;
-  void* s = nullptr;
-  if (hipSetDevice(device) != hipSuccess || !(s = make_stream(high_priority))) {
-    err = std::string("hipStreamCreate: ") + hipGetErrorString(hipGetLastError());
-    return nullptr;
-  }
-  return s;
-}
-void stream_destroy(int device, void* s) {
-  DeviceGuard guard;
-  if (!s) return;
-  (void)hipSetDevice(device);
-  (void)hipStreamDestroy(reinterpret_cast<hipStream_t>(s));
-}
-
-// Blocks the cache let go (pool_free) wait here for a call that can afford hipFree -- it waits for the whole device, and pool_free runs
-// on the hot path: a pipeline of fresh batches whose (un-hinted, 7 GB) first runs had filled the cache freed a block per batch and stalled
-// its fetch thread behind the runs in flight: 273 instead of 355 M queries/s in bench.py's end-to-end section (round 6).
-static void pool_reap(DevPool& pl) {
-  std::vector<std::pair<void*, size_t>> drop;
-  { std::lock_guard<std::mutex> g(pl.mu); drop.swap(pl.doomed); pl.doomed_bytes = 0; }
-  for (auto& d : drop) (void)hipFree(d.first);
-}
-hipError_t pool_malloc(void** p, size_t bytes) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  DevPool& pl = pool_of(dev);
-  bytes = (bytes + 255) & ~(size_t)255;
-  {
-    std::lock_guard<std::mutex> g(pl.mu);
-    auto it = pl.free_blocks.lower_bound(bytes);
-    if (it != pl.free_blocks.end() && it->first <= 2 * bytes + (1u << 20)) {
-      *p = it->second;
-      pl.cached -= it->first;
-      pl.free_blocks.erase(it);
-      pl.freed_at.erase(*p);
-      return hipSuccess;
-    }
-  }
-  pool_reap(pl);  // (a cache miss pays a hipMalloc anyway: the evicted blocks go to the driver here)
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess) {  // out of memory: give the cache back and retry once
-    std::vector<void*> drop;
-    {
-      std::lock_guard<std::mutex> g(pl.mu);
-      for (auto& kv : pl.free_blocks) { drop.push_back(kv.second); pl.size_of.erase(kv.second); }
-      pl.free_blocks.clear();
-      pl.freed_at.clear();
-      pl.cached = 0;
-    }
-    for (void* d : drop) (void)hipFree(d);
-    (void)hipGetLastError();
-    e = hipMalloc(p, bytes);
-    if (e != hipSuccess) return e;
-  }
-  std::lock_guard<std::mutex> g(pl.mu);
-  pl.size_of[*p] = bytes;
-  return hipSuccess;
-}
-void pool_free(void* p) {
-  if (!p) return;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  DevPool& pl = pool_of(dev);
-  std::vector<void*> evicted;
-  bool kept = false;
-  {
-    std::lock_guard<std::mutex> g(pl.mu);
-    auto it = pl.size_of.find(p);
-    if (it != pl.size_of.end() && it->second <= pool_cache_limit()) {
-      // A full cache makes room by letting its OLDEST blocks go.  (Until the end of round 5 the block that came back was handed to
-      // hipFree instead -- a call that waits for the device: after a workload that had filled the cache -- bench.py's 1 M-entry
-      // lexicon -- every call of the next one paid its frees and mallocs in full: 18-22 ms per part of a search-mode call.)
-      while (pl.cached + it->second > pool_cache_limit() && !pl.free_blocks.empty()) {
-        auto old = pl.free_blocks.begin();
-        for (auto jt = pl.free_blocks.begin(); jt != pl.free_blocks.end(); ++jt)
-          if (pl.freed_at[jt->second] < pl.freed_at[old->second]) old = jt;
-        pl.cached -= old->first;
-        pl.doomed.emplace_back(old->second, old->first);   // freed by the next cache miss / trim (pool_reap), not here
-        pl.doomed_bytes += old->first;
-        pl.freed_at.erase(old->second);
-        pl.size_of.erase(old->second);
-        pl.free_blocks.erase(old);
-      }
-      if (pl.doomed_bytes > pool_cache_limit() / 2) { evicted.reserve(pl.doomed.size()); for (auto& d : pl.doomed) evicted.push_back(d.first); pl.doomed.clear(); pl.doomed_bytes = 0; }  // (a bound all the same)
-      pl.free_blocks.emplace(it->second, p);
-      pl.freed_at[p] = ++pl.clock;
-      pl.cached += it->second;
-      kept = true;
-    } else if (it != pl.size_of.end()) {
-      pl.size_of.erase(it);
-    }
-  }
-  for (void* q : evicted) (void)hipFree(q);
-  if (!kept) (void)hipFree(p);
-}
-static void pool_trim(int device) {
-  DevPool& pl = pool_of(device);
-  small_ctxs_destroy(device);  // (first: their blocks go back to the pool that is emptied below)
-  pool_reap(pl);
-  std::vector<void*> drop;
-  {
-    std::lock_guard<std::mutex> g(pl.mu);
-    for (auto& kv : pl.free_blocks) { drop.push_back(kv.second); pl.size_of.erase(kv.second); }
-    pl.free_blocks.clear();
-    pl.freed_at.clear();
-    pl.cached = 0;
-  }
-  for (void* d : drop) (void)hipFree(d);
-  shells_destroy(device);
-}
-// Pinned host buffers for the downloaded results.  A fresh malloc'd buffer of 141 MB (1 M queries of config 2) is pageable and
-// untouched: the D2H copy is staged and page-faults its way through it (~20 ms); a pinned buffer takes the rows at PCIe speed.
-// Pinning costs more than the copy, so freed buffers are kept (anx_results_free returns them here) up to ANX_PINNED_CACHE_MB
-// (default 2048: a pipeline of 6-8 batches of a million queries in flight, 75-140 MB of rows each, outgrew 1024 and pinned afresh
-// for every batch at half the rate); anx_device_pool_trim releases them.  Without a HIP device the buffers are plain malloc blocks.
-namespace {
-struct HostCache {
-  std::mutex mu;
-  std::multimap<size_t, void*> free_blocks;
-  std::unordered_map<void*, std::pair<size_t, bool>> live;  // every block handed out or cached: (bytes, pinned)
-  std::unordered_map<void*, uint64_t> freed_at;             // cached blocks: when they came back (the oldest leave first)
-  uint64_t clock = 0;
-  size_t cached = 0;
-  std::vector<void*> doomed;   // evicted pinned blocks awaiting hipHostFree (which waits for the device: done on a cache miss, not on the hot path)
-  size_t doomed_bytes = 0;
-};
-HostCache& host_cache() { static HostCache c; return c; }
-size_t host_cache_limit() {
-  static const size_t lim = []() { const char* e = getenv("ANX_PINNED_CACHE_MB"); const long long v = e ? atoll(e) : -1; return v >= 0 ? (size_t)v << 20 : (size_t)2 << 30; }();
-  return lim;
-}
-}  // namespace
-static std::atomic<uint64_t> g_host_hits{0}, g_host_misses{0}, g_host_miss_bytes{0};
-void host_result_cache_stats(uint64_t* hits, uint64_t* misses, uint64_t* miss_bytes) { *hits = g_host_hits.load(); *misses = g_host_misses.load(); *miss_bytes = g_host_miss_bytes.load(); }
-void* host_result_alloc(size_t bytes) {
-  HostCache& hc = host_cache();
-  bytes = (std::max<size_t>(bytes, 64) + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);  // whole MB: a few distinct sizes
-  {
-    std::lock_guard<std::mutex> g(hc.mu);
-    auto it = hc.free_blocks.lower_bound(bytes);
-    if (it != hc.free_blocks.end() && it->first <= 2 * bytes) {
-      void* p = it->second;
-      hc.cached -= it->first;
-      hc.free_blocks.erase(it);
-      hc.freed_at.erase(p);
-      ++g_host_hits;
-      return p;
-    }
-  }
-  ++g_host_misses;
-  g_host_miss_bytes += bytes;
-  {  // a miss pins a fresh block anyway: the evicted ones are released here
-    std::vector<void*> drop;
-    { std::lock_guard<std::mutex> g(hc.mu); drop.swap(hc.doomed); hc.doomed_bytes = 0; }
-    for (void* q : drop) (void)hipHostFree(q);
-  }
-  void* p = nullptr;
-  bool pinned = hipHostMalloc(&p, bytes, hipHostMallocPortable) == hipSuccess && p;  // portable: the replicas of a multi-device model download into one buffer
-  if (!pinned) {
-    (void)hipGetLastError();
-    p = malloc(bytes);
-    if (!p) return nullptr;
-  }
-  std::lock_guard<std::mutex> g(hc.mu);
-  hc.live[p] = std::make_pair(bytes, pinned);
-  return p;
-}
-bool host_result_is_pinned(void* p) {
-  HostCache& hc = host_cache();
-  std::lock_guard<std::mutex> g(hc.mu);
-  auto it = hc.live.find(p);
-  return it != hc.live.end() && it->second.second;
-}
-void host_result_free(void* p) {
-  if (!p) return;
-  HostCache& hc = host_cache();
-  size_t bytes = 0;
-  bool pinned = false, known = false;
-  std::vector<void*> evicted;
-  {
-    std::lock_guard<std::mutex> g(hc.mu);
-    auto it = hc.live.find(p);
-    if (it != hc.live.end()) {
-      known = true;
-      bytes = it->second.first;
-      pinned = it->second.second;
-      if (pinned && bytes <= host_cache_limit()) {
-        // A full cache makes room by letting its OLDEST blocks go.  (Until the end of round 5 the block that came back was dropped
-        // instead: a process that had filled the cache with the buffers of one workload -- bench.py after its 1 M-entry lexicon --
-        // then pinned and unpinned the buffers of the next one on every call: search mode 225-240 instead of 250-280 MB/s.)
-        while (hc.cached + bytes > host_cache_limit() && !hc.free_blocks.empty()) {
-          auto old = hc.free_blocks.begin();
-          for (auto jt = hc.free_blocks.begin(); jt != hc.free_blocks.end(); ++jt)
-            if (hc.freed_at[jt->second] < hc.freed_at[old->second]) old = jt;
-          hc.cached -= old->first;
-          hc.doomed.push_back(old->second);
-          hc.doomed_bytes += old->first;
-          hc.freed_at.erase(old->second);
-          hc.live.erase(old->second);
-          hc.free_blocks.erase(old);
-        }
-        if (hc.doomed_bytes > host_cache_limit()) { evicted.swap(hc.doomed); hc.doomed_bytes = 0; }  // (a bound all the same)
-        hc.free_blocks.emplace(bytes, p);
-        hc.freed_at[p] = ++hc.clock;
-        hc.cached += bytes;
-        known = false;  // (cached: nothing to release below)
-        p = nullptr;
-      } else {
-        hc.live.erase(it);
-      }
-    }
-  }
-  for (void* q : evicted) (void)hipHostFree(q);
-  if (!p) return;
-  if (known && pinned) (void)hipHostFree(p);
-  else free(p);  // a malloc block (also: rows assembled by anx_find_variants_batch from several device batches)
-}
-static void host_cache_trim() {
-  HostCache& hc = host_cache();
-  std::vector<void*> drop;
-  {
-    std::lock_guard<std::mutex> g(hc.mu);
-    for (auto& kv : hc.free_blocks) { drop.push_back(kv.second); hc.live.erase(kv.second); }
-    for (void* q : hc.doomed) drop.push_back(q);
-    hc.doomed.clear();
-    hc.doomed_bytes = 0;
-    hc.free_blocks.clear();
-    hc.freed_at.clear();
-    hc.cached = 0;
-  }
-  for (void* p : drop) (void)hipHostFree(p);
-}
-void device_pool_trim(int device) {
-  int cur = -1;
-  const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-  if (hipSetDevice(device) == hipSuccess) pool_trim(device);
-  else (void)hipGetLastError();
-  if (have_cur && cur != device) (void)hipSetDevice(cur);  // the caller's current device is not ours to change
-  host_cache_trim();
-}
-
 // Host staging array WITHOUT value-initialisation: the threaded fill loops write every element, so the pages are first
 // touched (and faulted in) by the worker threads instead of being zero-filled by the calling thread (a million queries
 // stage ~150 MB; the single-threaded zero fill of std::vector cost a quarter of the encode time).
@@ -441,7 +86,7 @@ DeviceLexicon* lexicon_upload(const LexiconImage& img, const EncodeTables& et, c
   if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return nullptr; }
   DeviceLexicon* d = new DeviceLexicon();
   d->device = device;
-  { DevPool& pl = pool_of(device); std::lock_guard<std::mutex> g(pl.mu); ++pl.lexicons; }
+  lexicon_registered(device);
   d->nplanes = img.nplanes;
   d->nsym = img.nsym;
   d->nclasses = img.nclasses;
@@ -625,9 +270,7 @@ void lexicon_free(DeviceLexicon* d) {
     if (p) pool_free(p);
   conf_free(d->dconf);
   lm_free(d->dlm);
-  bool last;
-  { DevPool& pl = pool_of(d->device); std::lock_guard<std::mutex> g(pl.mu); last = --pl.lexicons <= 0; }
-  if (last) pool_trim(d->device);  // the last model of this device: hand the cached blocks back to the driver
+  lexicon_released(d->device);  // the last model of this device: its pool goes back to the driver
   delete d;
 }
 
@@ -953,51 +596,6 @@ static int encode_host(const HostModel& m, const DeviceLexicon* dl, Batch* b, co
   return ANX_OK;
 }
 
-// events + pinned read-back block of a batch: from the device's pool of shells (freed batches), created when the pool is empty
-static int shell_acquire(Batch* b, std::string& err) {
-  DevPool& pl = pool_of(b->device);
-  BatchShell sh;
-  bool have = false;
-  {
-    std::lock_guard<std::mutex> g(pl.mu);
-    if (!pl.shells.empty()) { sh = pl.shells.back(); pl.shells.pop_back(); have = true; }
-  }
-  if (!have) {
-    for (auto& e : sh.ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreate(&sh.ev_fs0));
-    HIP_TRY(hipEventCreate(&sh.ev_fs1));
-    HIP_TRY(hipEventCreate(&sh.ev_scan0));
-    HIP_TRY(hipEventCreate(&sh.ev_done));
-    HIP_TRY(hipEventCreateWithFlags(&sh.ev_in, hipEventDisableTiming));
-    // pinned: the counters the run reads back, and behind them the staging copy of FsCold (a pageable source would make the host
-    // wait, in stream order behind the scan just enqueued, until the copy has been staged)
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sh.h_read), HR_COLD_OFF + sizeof(FsCold), hipHostMallocDefault));
-  }
-  for (int i = 0; i < 6; ++i) b->ev[i] = sh.ev[i];
-  b->ev_fs0 = sh.ev_fs0; b->ev_fs1 = sh.ev_fs1; b->ev_scan0 = sh.ev_scan0; b->ev_done = sh.ev_done; b->ev_in = sh.ev_in; b->h_read = sh.h_read;
-  return ANX_OK;
-}
-static void shell_release(Batch* b) {
-  if (!b->ev_done) return;  // never acquired (an encode that failed early)
-  BatchShell sh;
-  for (int i = 0; i < 6; ++i) { sh.ev[i] = b->ev[i]; b->ev[i] = nullptr; }
-  sh.ev_fs0 = b->ev_fs0; sh.ev_fs1 = b->ev_fs1; sh.ev_scan0 = b->ev_scan0; sh.ev_done = b->ev_done; sh.ev_in = b->ev_in; sh.h_read = b->h_read;
-  b->ev_fs0 = b->ev_fs1 = b->ev_scan0 = b->ev_done = b->ev_in = nullptr; b->h_read = nullptr;
-  DevPool& pl = pool_of(b->device);
-  std::lock_guard<std::mutex> g(pl.mu);
-  pl.shells.push_back(sh);
-}
-static void shells_destroy(int device) {  // (the current device is `device`)
-  DevPool& pl = pool_of(device);
-  std::vector<BatchShell> drop;
-  { std::lock_guard<std::mutex> g(pl.mu); drop.swap(pl.shells); }
-  for (BatchShell& sh : drop) {
-    for (auto& e : sh.ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {sh.ev_fs0, sh.ev_fs1, sh.ev_scan0, sh.ev_done, sh.ev_in}) if (e) (void)hipEventDestroy(e);
-    if (sh.h_read) (void)hipHostFree(sh.h_read);
-  }
-}
-
 // what every batch needs besides its query arrays: counters, per-query accumulators, events
 static int encode_tail(Batch* b, std::string& err) {
   const size_t nq = b->nq;
@@ -1009,7 +607,7 @@ static int encode_tail(Batch* b, std::string& err) {
     return rc;
   b->rctr = b->ctl + HR_RCTR; b->sctr = b->ctl + HR_SCTR; b->lctr = b->ctl + HR_LCTR; b->counters = b->ctl + HR_CTR;
   b->qmaxfreq = b->qsurv + nq; b->qexpand = b->qsurv + 2 * nq;  // (qexpand last: only models with variant lists clear and use it)
-  return shell_acquire(b, err);
+  return shell_acquire(b->device, *b, HR_COLD_OFF + sizeof(FsCold), err);  // events + pinned read-back block (runtime.hip)
 }
 
 Batch* batch_encode_spans(const HostModel& m, const DeviceLexicon* dl, const char* blob, size_t blob_bytes, const uint32_t* off, size_t n,
@@ -1103,72 +701,6 @@ static int exclusive_scan(const uint32_t* in, uint32_t n, uint32_t* out, uint32_
   if (!fused) hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, tmp, nb);
   hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(SCAN_THREADS), 0, st, out, n, tmp, nb, copy, fused);
   return 0;
-}
-
-// ---- kernel timer (engine_internal.h) ---------------------------------------------------------------------------------
-namespace {
-struct KTimerRec { std::string name; hipEvent_t e0 = nullptr, e1 = nullptr; int device = 0; bool closed = false; };
-struct KTimer {
-  std::mutex mu;
-  std::atomic<bool> on{false};
-  std::vector<KTimerRec> pending;
-  uint32_t generation = 0;  // of `pending`: part of the handles ktimer_begin hands out
-  std::map<std::string, std::pair<double, uint64_t>> acc;
-};
-KTimer& ktimer() { static KTimer* t = new KTimer; return *t; }
-void ktimer_resolve_locked(KTimer& t) {
-  for (KTimerRec& r : t.pending) {
-    if (r.closed && hipEventSynchronize(r.e1) == hipSuccess) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) { auto& a = t.acc[r.name]; a.first += ms; a.second += 1; }
-    }
-    if (r.e0) (void)hipEventDestroy(r.e0);
-    if (r.e1) (void)hipEventDestroy(r.e1);
-  }
-  t.pending.clear();
-  ++t.generation;  // handles of the records just dropped (also unclosed ones of a launch in progress on another thread) are void now
-}
-}  // namespace
-int ktimer_begin(const char* name, hipStream_t st) {
-  KTimer& t = ktimer();
-  if (!t.on.load(std::memory_order_relaxed)) return -1;
-  KTimerRec r;
-  r.name = name;
-  if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess || hipEventRecord(r.e0, st) != hipSuccess) {
-    if (r.e0) (void)hipEventDestroy(r.e0);
-    if (r.e1) (void)hipEventDestroy(r.e1);
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (t.pending.size() >= 0xFFFFu) return -1;
-  t.pending.push_back(r);
-  return (int)(((t.generation & 0x7FFFu) << 16) | (uint32_t)(t.pending.size() - 1));  // generation + index: stable across kernel_timer_read
-}
-void ktimer_end(int handle, hipStream_t st) {
-  if (handle < 0) return;
-  KTimer& t = ktimer();
-  std::lock_guard<std::mutex> lk(t.mu);
-  const uint32_t idx = (uint32_t)handle & 0xFFFFu;
-  if ((((uint32_t)handle >> 16) & 0x7FFFu) != (t.generation & 0x7FFFu) || idx >= t.pending.size()) return;  // the totals were read in between: the record is gone
-  KTimerRec& r = t.pending[idx];
-  if (hipEventRecord(r.e1, st) == hipSuccess) r.closed = true;
-}
-void kernel_timer_enable(bool on) {
-  KTimer& t = ktimer();
-  std::lock_guard<std::mutex> lk(t.mu);
-  ktimer_resolve_locked(t);
-  t.acc.clear();
-  t.on.store(on);
-}
-bool kernel_timer_read(const char* name, double* total_ms, uint64_t* launches) {
-  KTimer& t = ktimer();
-  std::lock_guard<std::mutex> lk(t.mu);
-  ktimer_resolve_locked(t);
-  auto it = t.acc.find(name ? name : "");
-  if (it == t.acc.end()) { if (total_ms) *total_ms = 0.0; if (launches) *launches = 0; return false; }
-  if (total_ms) *total_ms = it->second.first;
-  if (launches) *launches = it->second.second;
-  return true;
 }
 
 #include "launch_plan.hpp"
@@ -1704,14 +1236,7 @@ int batch_run_async(const HostModel& m, const DeviceLexicon* dl, Batch* b, void*
   void* use = stream;
   if (own_streams && dl && switches().run_overlap) {
     HIP_TRY(hipSetDevice(dl->device));
-    DevPool& pl = pool_of(dl->device);
-    hipStream_t s = nullptr;
-    {
-      std::lock_guard<std::mutex> g(pl.mu);
-      hipStream_t& slot = pl.run_streams[pl.run_counter++ & 1u];
-      if (!slot && hipStreamCreateWithFlags(&slot, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); slot = nullptr; }
-      s = slot;
-    }
+    hipStream_t s = run_stream_next(dl->device);
     if (s) {
       HIP_TRY(hipEventRecord(b->ev_in, reinterpret_cast<hipStream_t>(stream)));
       HIP_TRY(hipStreamWaitEvent(s, b->ev_in, 0));
@@ -1742,201 +1267,8 @@ void batch_set_last_stream(Batch* b, void* stream) { if (b && !b->launched) b->l
 size_t batch_n_results(const Batch* b) { return b->ran ? (size_t)b->n_results : 0; }
 size_t batch_n_input(const Batch* b) { return b->n_input; }
 
-// The way of the ranked rows into the CALLER's input order, enqueued on st -- what every fetch and the compact export share: the
-// counts scattered to the original indices (d_cnt[n_input]), an exclusive scan over them (d_off[n_input + 1]; d_tmp: the scan's
-// block sums, scan_tmp_bytes), and the row copy through `emit` (kernels_rank.hpp) to where the offsets say.
-static size_t scan_tmp_bytes(size_t n) { return ((n + SCAN_TILE - 1) / SCAN_TILE + 2) * sizeof(uint32_t); }
-template <typename Emit>
-static int enqueue_rows(const Batch* b, uint32_t* d_cnt, uint32_t* d_off, uint32_t* d_tmp, hipStream_t st, const Emit& emit, std::string& err) {
-  const uint32_t n32 = (uint32_t)b->n_input, nq32 = (uint32_t)b->nq;
-  HIP_TRY(hipMemsetAsync(d_cnt, 0, n32 * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
-  exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
-  hipLaunchKernelGGL(k_emit_rows<Emit>, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->soff, b->r_count, b->r_rows, b->q_orig, d_off, emit);
-  return ANX_OK;
-}
-
-// Downloads the ranked rows of the batch into caller-provided storage: out[0 .. n_results), off[0 .. n_input] = base + the CSR
-// offsets (a shard of a multi-device batch writes its slice of the whole call's arrays) and, where via is given, via[0 .. n_results).
-// The device lays the rows out in input order (enqueue_rows with make_emit(d_out, d_via)), so the host only copies: the offsets
-// (u32) and the finished arrays.  Runs on the stream of the batch's last run; every exit frees the temporaries.
-template <typename Row, typename Off, typename MakeEmit>
-static int fetch_rows(const Batch* b, Row* out, Off* off, uint32_t* via, Off base, const MakeEmit& make_emit, std::string& err) {
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t n = b->n_input;
-  if (!b->nq || !b->n_results) {
-    for (size_t i = 0; i <= n; ++i) off[i] = base;
-    return ANX_OK;
-  }
-  uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr, *d_via = nullptr;
-  Row* d_out = nullptr;
-  hipStream_t st = reinterpret_cast<hipStream_t>(b->last_stream);
-  auto body = [&]() -> int {
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), scan_tmp_bytes(n)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_out), b->n_results * sizeof(Row)));
-    if (via) HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_via), b->n_results * sizeof(uint32_t)));
-    if (const int rc = enqueue_rows(b, d_cnt, d_off, d_tmp, st, make_emit(d_out, d_via), err)) return rc;
-    std::vector<uint32_t> staged;  // u32 offsets land in the caller's array, wider ones are widened from a copy
-    uint32_t* h_off;
-    if constexpr (sizeof(Off) == sizeof(uint32_t)) h_off = off;
-    else { staged.resize(n + 1); h_off = staged.data(); }
-    HIP_TRY(hipMemcpyAsync(h_off, d_off, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out, d_out, b->n_results * sizeof(Row), hipMemcpyDeviceToHost, st));
-    if (via) HIP_TRY(hipMemcpyAsync(via, d_via, b->n_results * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (base || !staged.empty())
-      for (size_t i = 0; i <= n; ++i) off[i] = base + h_off[i];
-    return ANX_OK;
-  };
-  const int rc = body();
-  if (rc) (void)hipStreamSynchronize(st);  // nothing of this call may still be in flight when its blocks return to the pool
-  for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_out, (void*)d_via}) pool_free(p);
-  return rc;
-}
-
-int batch_fetch_into(const Batch* b, anx_result* out, size_t* off, size_t base, std::string& err) {
-  return fetch_rows(b, out, off, nullptr, base, [](anx_result* d_out, uint32_t*) { return EmitResult{d_out}; }, err);
-}
-
-// The same rows as 16-byte anx_topk_record {vocab u32, freq f32, dist f64} with u32 offsets: half the bytes over PCIe (config 2:
-// 70 MB instead of 141 MB per million queries).  via (may be null): one word per row, 0xFFFFFFFF = none.  plain: the model has no
-// variant lists -- every word is 0xFFFFFFFF, written on the host: the device and PCIe see what the call without via does.
-int batch_fetch_compact_into(const Batch* b, anx_topk_record* out, uint32_t* off, uint32_t* via, uint32_t base, bool plain, std::string& err) {
-  if (via && !plain)
-    return fetch_rows(b, out, off, via, base, [](anx_topk_record* d_out, uint32_t* d_via) { return EmitRecordVia{d_out, d_via}; }, err);
-  const int rc = fetch_rows(b, out, off, nullptr, base, [](anx_topk_record* d_out, uint32_t*) { return EmitRecord{d_out}; }, err);
-  if (rc == ANX_OK && via && b->n_results) memset(via, 0xFF, (size_t)b->n_results * sizeof(uint32_t));
-  return rc;
-}
-
-// anx_batch_fetch_measures for one shard: out[0 .. n_results) = the measures behind row r of batch_fetch_compact_into (same rows, same
-// order), off[0 .. n_input] = base + the CSR offsets.  The vocabulary id -> entry table of the replica is built on first use; the
-// offsets are the scan every fetch makes (k_fetch_counts + exclusive_scan); k_row_measures settles the short rows and lists the
-// long ones for k_row_measures_long (kernels_explain.hpp).  Runs on the stream of the batch's last run; every exit frees the blocks.
-static int vocab_entry_ensure(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, std::string& err) {
-  std::lock_guard<std::mutex> g(dl->explain_mu);
-  if (dl->vocab_ent) return ANX_OK;
-  const size_t V = std::max<size_t>(m.decoder.size(), 1);
-  if (V >= 0xFFFFFFFFull) { err = "more than 2^32 vocabulary items"; return ANX_ELIMIT; }
-  uint32_t* t = nullptr;
-  HIP_TRY(pool_malloc(reinterpret_cast<void**>(&t), V * sizeof(uint32_t)));
-  auto fill = [&]() -> int {
-    HIP_TRY(hipMemsetAsync(t, 0xFF, V * sizeof(uint32_t), st));
-    if (dl->nentries) hipLaunchKernelGGL(k_vocab_entry_scatter, dim3((dl->nentries + 255) / 256), dim3(256), 0, st, dl->nentries, dl->ent_vocab, (uint32_t)V, t);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));  // (another thread's stream may read the table as soon as the pointer is published)
-    return ANX_OK;
-  };
-  if (const int rc = fill()) { (void)hipStreamSynchronize(st); pool_free(t); return rc; }
-  dl->vocab_ent_n = (uint32_t)V;
-  dl->vocab_ent = t;
-  return ANX_OK;
-}
-// The device sequence of anx_batch_fetch_measures, enqueued on st: the offsets of the compact export into d_off[n_input + 1] and one
-// record per ranked row into d_out[n_results], in export order.  d_cnt[n_input], d_tmp (scan_tmp_bytes), d_list[n_surv + 4]: scratch.
-static int measures_enqueue(const HostModel& m, const DeviceLexicon* dl, const Batch* b, hipStream_t st, uint32_t* d_cnt, uint32_t* d_off, uint32_t* d_tmp,
-                            uint4* d_out, uint32_t* d_list, std::string& err) {
-  const uint32_t total = (uint32_t)b->n_surv, n32 = (uint32_t)b->n_input, nq32 = (uint32_t)b->nq;
-  HIP_TRY(hipMemsetAsync(d_cnt, 0, n32 * sizeof(uint32_t), st));
-  HIP_TRY(hipMemsetAsync(d_list, 0, 4 * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_fetch_counts, dim3((nq32 + 255) / 256), dim3(256), 0, st, nq32, b->r_count, b->q_orig, d_cnt);
-  exclusive_scan(d_cnt, n32, d_off, d_tmp, st);
-  ExplainArgs k{};
-  k.nq = nq32; k.total = total; k.V = dl->vocab_ent_n; k.nentries = dl->nentries; k.qw = b->qw; k.cstride = dl->cstride; k.n_out = (uint32_t)b->n_results;
-  k.NP = dl->nplanes; k.bits_ok = (dl->nsym <= 32 && !scan_mode()) ? 1 : 0;
-  k.soff = b->soff; k.r_count = b->r_count; k.q_orig = b->q_orig; k.off_orig = d_off; k.q_meta = b->q_meta; k.r_rows = b->r_rows;
-  k.q_rec = b->q_rec; k.q_rows = b->q_rows; k.q_bits = reinterpret_cast<const uint4*>(b->q_bits); k.q_cv = b->q_cv;
-  k.vocab_ent = dl->vocab_ent; k.e_rec = dl->e_rec; k.scan_rec = dl->scan_rec; k.rows = dl->rows; k.cls_planes = dl->cls_planes; k.quot = dl->quot;
-  k.w_ld = m.weights.ld; k.w_lcs = m.weights.lcs; k.w_prefix = m.weights.prefix; k.w_suffix = m.weights.suffix; k.w_case = m.weights.casew;
-  k.w_sum = m.weights.ld + m.weights.lcs + m.weights.prefix + m.weights.suffix + m.weights.casew;  // src/types.rs:69-73, as launch_plan.hpp
-  k.out = d_out; k.list = d_list + 4; k.list_n = d_list;
-  {
-    const int kt = ktimer_begin("k_row_measures", st);
-    hipLaunchKernelGGL(k_row_measures, dim3((total + XM_THREADS - 1) / XM_THREADS), dim3(XM_THREADS), 0, st, k);
-    ktimer_end(kt, st);
-  }
-  {
-    const int kt = ktimer_begin("k_row_measures_long", st);
-    hipLaunchKernelGGL(k_row_measures_long, dim3(std::min<uint32_t>(XM_LONG_BLOCKS, total)), dim3(64), 0, st, k);
-    ktimer_end(kt, st);
-  }
-  HIP_TRY(hipGetLastError());
-  return ANX_OK;
-}
-int batch_fetch_measures_into(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_row_measures* out, uint32_t* off, uint32_t base, std::string& err) {
-  static_assert(sizeof(anx_row_measures) == sizeof(uint4), "the record leaves as one 16-byte store");
-  if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  HIP_TRY(hipSetDevice(b->device));
-  const size_t n = b->n_input;
-  if (!b->nq || !b->n_results) {
-    for (size_t i = 0; i <= n; ++i) off[i] = base;
-    return ANX_OK;
-  }
-  if (b->n_results >= 0xFFFFFFFFull || b->n_surv >= 0xFFFFFFFFull) { err = "more than 2^32 result rows"; return ANX_ELIMIT; }
-  hipStream_t st = reinterpret_cast<hipStream_t>(b->last_stream);
-  if (const int rc = vocab_entry_ensure(m, dl, st, err)) return rc;
-  const uint32_t total = (uint32_t)b->n_surv;
-  uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr, *d_list = nullptr;
-  uint4* d_out = nullptr;
-  auto body = [&]() -> int {
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), scan_tmp_bytes(n)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_out), b->n_results * sizeof(uint4)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_list), ((size_t)total + 4) * sizeof(uint32_t)));  // [0]: the list's length, rows from [4] on
-    if (const int rc = measures_enqueue(m, dl, b, st, d_cnt, d_off, d_tmp, d_out, d_list, err)) return rc;
-    HIP_TRY(hipMemcpyAsync(off, d_off, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out, d_out, b->n_results * sizeof(uint4), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (base)
-      for (size_t i = 0; i <= n; ++i) off[i] += base;
-    return ANX_OK;
-  };
-  const int rc = body();
-  if (rc) (void)hipStreamSynchronize(st);  // nothing of this call may still be in flight when its blocks return to the pool
-  for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_out, (void*)d_list}) pool_free(p);
-  return rc;
-}
-
-// The same records for the weight sweep (reweigh.hip): not downloaded but placed at dst on device dst_device, beside the shard's section
-// of batch_gather_compact_via -- record r belongs to record r of that section.  Computed on the batch's own device into a pool block
-// (in place when the batch lives on dst_device), copied over as gather_compact copies a section; returns when the bytes are there.
-int batch_gather_measures(const HostModel& m, const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err) {
-  if (!dl) { err = "model is not resident on a device"; return ANX_ENODEVICE; }
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  if (!b->nq || !b->n_results) return ANX_OK;
-  if (b->n_results >= 0xFFFFFFFFull || b->n_surv >= 0xFFFFFFFFull) { err = "more than 2^32 result rows"; return ANX_ELIMIT; }
-  const size_t need = (size_t)b->n_results * sizeof(uint4), n = b->n_input;
-  if (!dst || capacity < need) { err = "measure buffer too small: " + std::to_string(need) + " bytes needed for this shard"; return ANX_ELIMIT; }
-  HIP_TRY(hipSetDevice(b->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (const int rc = vocab_entry_ensure(m, dl, st, err)) return rc;
-  const bool local = b->device == dst_device;
-  uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_tmp = nullptr, *d_list = nullptr;
-  uint4* d_tmp_out = nullptr;
-  auto body = [&]() -> int {
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_cnt), n * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_off), (n + 1) * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp), scan_tmp_bytes(n)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_list), ((size_t)b->n_surv + 4) * sizeof(uint32_t)));
-    if (!local) HIP_TRY(pool_malloc(reinterpret_cast<void**>(&d_tmp_out), need));
-    uint4* d_out = local ? static_cast<uint4*>(dst) : d_tmp_out;
-    if (const int rc = measures_enqueue(m, dl, b, st, d_cnt, d_off, d_tmp, d_out, d_list, err)) return rc;
-    if (!local) HIP_TRY(hipMemcpyPeerAsync(dst, dst_device, d_out, b->device, need, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return ANX_OK;
-  };
-  const int rc = body();
-  if (rc) (void)hipStreamSynchronize(st);  // nothing of this call may still be in flight when its blocks return to the pool
-  for (void* p : {(void*)d_cnt, (void*)d_off, (void*)d_tmp, (void*)d_list, (void*)d_tmp_out}) pool_free(p);
-  return rc;
-}
-// ---- what reweigh.hip asks of this translation unit: the replica's vocabulary id -> entry table, the prefix sum and k_rank ---------------
-int replica_vocab_entries(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, std::string& err) { return vocab_entry_ensure(m, dl, st, err); }
+// ---- what results.hip and reweigh.hip ask of this translation unit: the prefix sum and k_rank -----------------------------------------------
+static size_t scan_tmp_bytes(size_t n) { return ((n + SCAN_TILE - 1) / SCAN_TILE + 2) * sizeof(uint32_t); }  // exclusive_scan's tmp
 size_t prefix_scan_tmp_bytes(size_t n) { return scan_tmp_bytes(n); }
 int prefix_scan_enqueue(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* tmp, hipStream_t st, uint32_t* copy) { return exclusive_scan(in, n, out, tmp, st, copy); }
 void rank_rows_enqueue(const RankPlain& r, hipStream_t st, uint32_t nq, const uint32_t* soff, const SurvRow* c_rows, const uint32_t* qmaxfreq, double* t_key, DevRow* r_rows,
@@ -1948,22 +1280,6 @@ void rank_rows_enqueue(const RankPlain& r, hipStream_t st, uint32_t nq, const ui
   ra.have_freq = r.have_freq;
   ra.any_variants = 0;
   launch_rank(ra, st, nq, soff, c_rows, qmaxfreq, nullptr, t_key, r_rows, r_count, row_cap, overflow, SegRows{nullptr, 0u, nullptr});
-}
-
-int batch_fetch(const HostModel& m, const DeviceLexicon* dl, const Batch* b, anx_result** rows, size_t** offs,
-                std::string& err) {
-  (void)m;
-  (void)dl;
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  HIP_TRY(hipSetDevice(b->device));
-  size_t* off = static_cast<size_t*>(malloc((b->n_input + 1) * sizeof(size_t)));
-  anx_result* out = static_cast<anx_result*>(host_result_alloc(std::max<size_t>(1, b->n_results) * sizeof(anx_result)));
-  if (!off || !out) { free(off); host_result_free(out); err = "out of memory"; return ANX_EINVAL; }
-  const int rc = batch_fetch_into(b, out, off, 0, err);
-  if (rc) { free(off); host_result_free(out); return rc; }
-  *rows = out;
-  *offs = off;
-  return ANX_OK;
 }
 
 // sorted position -> input index on the host (the device-side encoder only leaves it in q_orig): downloaded on first use
@@ -2022,148 +1338,6 @@ int batch_fetch_pairs(const HostModel& m, const DeviceLexicon* dl, const Batch* 
   return ANX_OK;
 }
 
-int batch_export_topk(const DeviceLexicon* dl, const Batch* b, void* dst, uint32_t stride, void* stream,
-                      std::string& err) {
-  (void)dl;
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  if (!dst || stride == 0) { err = "bad export arguments"; return ANX_EINVAL; }
-  if (stride < b->max_rows) {  // rows beyond the stride would be dropped silently (freq_weight != 0, variant lists or max_matches = 0
-                               // can return more than max_matches + 1 rows): refuse
-    err = "export stride " + std::to_string(stride) + " is smaller than the longest result list (" + std::to_string(b->max_rows) + " rows): use a larger stride or anx_batch_export_compact";
-    return ANX_ELIMIT;
-  }
-  HIP_TRY(hipSetDevice(b->device));
-  b->async_stream = stream; b->async_pending = true;
-  const uint64_t total = (uint64_t)b->nq * stride;
-  if (total)
-    hipLaunchKernelGGL(k_export_topk<false>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), (uint32_t)b->nq, stride, b->soff, b->r_count,
-                       b->r_rows, b->q_orig, static_cast<anx_topk_record*>(dst), static_cast<uint32_t*>(nullptr));
-  HIP_TRY(hipGetLastError());
-  return ANX_OK;
-}
-// The same with the `via` word of every slot in a parallel array via[n_input * stride] (k_export_topk<true>): 0xFFFFFFFF for rows
-// without one and for unused slots -- also those of inputs the encoder dropped (no query: their RECORD slots stay untouched, as above)
-int batch_export_topk_via(const DeviceLexicon* dl, const Batch* b, void* dst, void* via, uint32_t stride, void* stream, std::string& err) {
-  (void)dl;
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  if (!dst || !via || stride == 0) { err = "bad export arguments"; return ANX_EINVAL; }
-  if (stride < b->max_rows) {
-    err = "export stride " + std::to_string(stride) + " is smaller than the longest result list (" + std::to_string(b->max_rows) + " rows): use a larger stride or anx_batch_export_compact_via";
-    return ANX_ELIMIT;
-  }
-  HIP_TRY(hipSetDevice(b->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  b->async_stream = stream; b->async_pending = true;
-  if (b->nq < b->n_input) HIP_TRY(hipMemsetAsync(via, 0xFF, b->n_input * (size_t)stride * sizeof(uint32_t), st));
-  const uint64_t total = (uint64_t)b->nq * stride;
-  if (total)
-    hipLaunchKernelGGL(k_export_topk<true>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, (uint32_t)b->nq, stride, b->soff, b->r_count,
-                       b->r_rows, b->q_orig, static_cast<anx_topk_record*>(dst), static_cast<uint32_t*>(via));
-  HIP_TRY(hipGetLastError());
-  return ANX_OK;
-}
-
-// Compact form of the same records: uint32 offsets[n+1] (input order; padded to a 16-byte multiple), then the
-// n_results records back to back.  The size is known on the host (n_results is read back by the run), so the
-// multi-GPU gather moves the used bytes only (config 2: 4.4 results per query, 74 MB per million instead of 176 MB).
-int batch_export_compact(const DeviceLexicon* dl, const Batch* b, void* dst, size_t capacity, void* stream,
-                         size_t* used, std::string& err) {
-  (void)dl;
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  if (!dst || !used) { err = "bad export arguments"; return ANX_EINVAL; }
-  const size_t n = b->n_input;
-  const size_t off_bytes = ((n + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
-  *used = off_bytes + (size_t)b->n_results * sizeof(anx_topk_record);
-  if (capacity < *used) { err = "export buffer too small: " + std::to_string(*used) + " bytes needed"; return ANX_ELIMIT; }
-  HIP_TRY(hipSetDevice(b->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  b->async_stream = stream; b->async_pending = true;
-  uint32_t* d_off = static_cast<uint32_t*>(dst);
-  anx_topk_record* d_rows = reinterpret_cast<anx_topk_record*>(static_cast<char*>(dst) + off_bytes);
-  if (n == 0 || b->nq == 0) { HIP_TRY(hipMemsetAsync(d_off, 0, off_bytes, st)); return ANX_OK; }
-  if (!b->x_cnt) {
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_cnt), n * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_tmp), scan_tmp_bytes(n)));
-  }
-  if (const int rc = enqueue_rows(b, b->x_cnt, d_off, b->x_tmp, st, EmitRecord{d_rows}, err)) return rc;
-  HIP_TRY(hipGetLastError());
-  return ANX_OK;
-}
-
-// The compact form followed by the `via` words of its rows (EmitRecordVia): [u32 offsets[n + 1] padded to 16 bytes][records][u32 via[n_results]]
-// -- offsets and records are the bytes batch_export_compact writes; a model without variant lists gets 0xFFFFFFFF in every word
-size_t batch_compact_via_bytes(const Batch* b) { return batch_compact_bytes(b) + (b->ran ? (size_t)b->n_results : 0) * sizeof(uint32_t); }
-int batch_export_compact_via(const DeviceLexicon* dl, const Batch* b, void* dst, size_t capacity, void* stream, size_t* used, std::string& err) {
-  (void)dl;
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  if (!dst || !used) { err = "bad export arguments"; return ANX_EINVAL; }
-  const size_t n = b->n_input;
-  const size_t off_bytes = ((n + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
-  *used = batch_compact_via_bytes(b);
-  if (capacity < *used) { err = "export buffer too small: " + std::to_string(*used) + " bytes needed"; return ANX_ELIMIT; }
-  HIP_TRY(hipSetDevice(b->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  b->async_stream = stream; b->async_pending = true;
-  uint32_t* d_off = static_cast<uint32_t*>(dst);
-  anx_topk_record* d_rows = reinterpret_cast<anx_topk_record*>(static_cast<char*>(dst) + off_bytes);
-  uint32_t* d_via = reinterpret_cast<uint32_t*>(d_rows + b->n_results);
-  if (n == 0 || b->nq == 0) { HIP_TRY(hipMemsetAsync(d_off, 0, off_bytes, st)); return ANX_OK; }
-  if (!b->x_cnt) {
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_cnt), n * sizeof(uint32_t)));
-    HIP_TRY(pool_malloc(reinterpret_cast<void**>(&b->x_tmp), scan_tmp_bytes(n)));
-  }
-  if (const int rc = enqueue_rows(b, b->x_cnt, d_off, b->x_tmp, st, EmitRecordVia{d_rows, d_via}, err)) return rc;
-  HIP_TRY(hipGetLastError());
-  return ANX_OK;
-}
-
-size_t batch_compact_bytes(const Batch* b) {
-  return (((b->n_input + 1) * sizeof(uint32_t) + 15) & ~(size_t)15) + (b->ran ? (size_t)b->n_results : 0) * sizeof(anx_topk_record);
-}
-// with_via: the section is batch_export_compact_via's
-static int gather_compact(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, bool with_via, std::string& err) {
-  if (!b->ran) { err = "batch has not been run"; return ANX_EINVAL; }
-  const size_t need = with_via ? batch_compact_via_bytes(b) : batch_compact_bytes(b);
-  if (capacity < need) { err = "gather buffer too small: " + std::to_string(need) + " bytes needed for this shard"; return ANX_ELIMIT; }
-  auto export_to = [&](void* to, size_t cap, size_t* used) {
-    return with_via ? batch_export_compact_via(dl, b, to, cap, stream, used, err) : batch_export_compact(dl, b, to, cap, stream, used, err);
-  };
-  size_t used = 0;
-  if (b->device == dst_device) {  // already where the rows are wanted
-    const int rc = export_to(dst, capacity, &used);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
-    return ANX_OK;
-  }
-  HIP_TRY(hipSetDevice(b->device));
-  {  // direct access between the two devices where the topology has it (xGMI); without it the peer copy is staged by the runtime
-    int can = 0;
-    if (hipDeviceCanAccessPeer(&can, b->device, dst_device) == hipSuccess && can) {
-      const hipError_t e = hipDeviceEnablePeerAccess(dst_device, 0);
-      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
-      else (void)hipGetLastError();
-    } else (void)hipGetLastError();
-  }
-  void* tmp = nullptr;
-  HIP_TRY(pool_malloc(&tmp, std::max<size_t>(need, 16)));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int rc = export_to(tmp, need, &used);
-  if (rc == ANX_OK) {
-    const hipError_t e = hipMemcpyPeerAsync(dst, dst_device, tmp, b->device, used, st);
-    if (e != hipSuccess) { err = std::string("hipMemcpyPeerAsync: ") + hipGetErrorString(e); rc = ANX_ENODEVICE; }
-  }
-  (void)hipStreamSynchronize(st);
-  pool_free(tmp);
-  return rc;
-}
-int batch_gather_compact(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err) {
-  return gather_compact(dl, b, dst_device, dst, capacity, stream, false, err);
-}
-int batch_gather_compact_via(const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err) {
-  return gather_compact(dl, b, dst_device, dst, capacity, stream, true, err);
-}
-
 // Scored pairs per input query, counted by the scan of a PRODUCTION run (pairs that fail the DL's length test are only
 // counted there, never materialised): the batch is run once more with the per-query counters switched on.
 int batch_pair_counts(const HostModel& m, const DeviceLexicon* dl, Batch* b, uint32_t** out, std::string& err) {
@@ -2192,24 +1366,6 @@ void batch_set_run_mode(Batch* b, const anx_params& p, int conf_mode) {
   b->params = p;
   b->conf_mode = conf_mode;
 }
-bool batch_conf_fallback(const Batch* b) { return b->conf_fallback; }
-int batch_download_text(const Batch* b, std::string& text, std::vector<uint32_t>& off, std::string& err) {
-  if (b->n_input == 0) {  // a shard that received no inputs never allocated its text: it contributes nothing
-    text.clear();
-    off.assign(1, 0u);
-    return ANX_OK;
-  }
-  if (!b->d_text || !b->d_textoff) { err = "the batch does not hold its inputs"; return ANX_EINVAL; }
-  HIP_TRY(hipSetDevice(b->device));
-  off.assign(b->n_input + 1, 0u);
-  HIP_TRY(hipMemcpy(off.data(), b->d_textoff, (b->n_input + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  text.assign(b->n_input ? (size_t)off[b->n_input] : 0, '\0');
-  if (!text.empty()) HIP_TRY(hipMemcpy(&text[0], b->d_text, text.size(), hipMemcpyDeviceToHost));
-  return ANX_OK;
-}
-
-void batch_stats(const Batch* b, anx_batch_stats* s) { *s = b->stats; }
-
 void batch_free(Batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
@@ -2223,429 +1379,12 @@ void batch_free(Batch* b) {
                   (void*)b->c_rows, (void*)b->sseg, (void*)b->r_rows, (void*)b->t_key, (void*)b->r_count,
                   (void*)b->d_text, (void*)b->d_textoff, (void*)b->cf_weight, (void*)b->cf_need, (void*)b->cf_ctr, b->cf_work, (void*)b->cf_sort, b->cf_sort_tmp})
     if (p) pool_free(p);
-  shell_release(b);  // events + pinned read-back block: to the device's pool (hipHostFree / hipEventDestroy here would wait for the device)
+  shell_release(b->device, *b);  // events + pinned read-back block: to the device's shells (runtime.hip) (hipHostFree / hipEventDestroy here would wait for the device)
   delete b;
 }
 
 #include "small_path.hpp"
+#include "debug_doors.hpp"
 
-// ---- test hook: the band-match bound alone (anx_debug_band_bound; tests/test_gpu_switches.py) ------------------------------------
-// One lane per pair, rows as the kernels see them (first 16 symbols, query padded with 0xFE, candidate with 0xFF); the three forms
-// in use: 0 the scan's fused filter (B7 masks, wave-uniform d, words by the wave's longest string), 1 k_filter_score's (B7, per-lane
-// d), 2 the general zero test (alphabets above 124 classes).  out[i] = 1: the bound says damerau_levenshtein(q, c) > d.
-__global__ __launch_bounds__(64) void k_debug_band_bound(const uint4* __restrict__ q, const uint4* __restrict__ c, const uint8_t* __restrict__ lqs,
-                                                         const uint8_t* __restrict__ lcs, uint32_t n, int d, int form, uint8_t* __restrict__ out) {
-  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-  const bool act = i < n;
-  const uint4 Q = act ? q[i] : make_uint4(0xFEFEFEFEu, 0xFEFEFEFEu, 0xFEFEFEFEu, 0xFEFEFEFEu);
-  const uint4 C = act ? c[i] : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-  const int lq = act ? lqs[i] : 1, lc = act ? lcs[i] : 1;
-  const int ml = lq > lc ? lq : lc;
-  bool rej;
-  if (form == 2) {
-    constexpr uint32_t M = 0xFFFFFFFFu;
-    if (__any(act && ml > 12)) { const uint32_t q4[4] = {Q.x, Q.y, Q.z, Q.w}, c6[6] = {M, C.x, C.y, C.z, C.w, M}; rej = band_bound_rejects<4, false>(q4, c6, act, d, lq, lc); }
-    else if (__any(act && ml > 8)) { const uint32_t q3[3] = {Q.x, Q.y, Q.z}, c5[5] = {M, C.x, C.y, C.z, M}; rej = band_bound_rejects<3, false>(q3, c5, act, d, lq, lc); }
-    else { const uint32_t q2[2] = {Q.x, Q.y}, c4[4] = {M, C.x, C.y, M}; rej = band_bound_rejects<2, false>(q2, c4, act, d, lq, lc); }
-  } else {
-    constexpr uint32_t M = 0x7F7F7F7Fu;
-    const uint32_t q4[4] = {Q.x & M, Q.y & M, Q.z & M, Q.w & M}, c6[6] = {M, C.x & M, C.y & M, C.z & M, C.w & M, M};
-    const uint32_t q3[3] = {q4[0], q4[1], q4[2]}, c5[5] = {M, c6[1], c6[2], c6[3], M};
-    const uint32_t q2[2] = {q4[0], q4[1]}, c4[4] = {M, c6[1], c6[2], M};
-    if (form == 0) {
-      if (__any(act && ml > 12)) rej = band_bound_rejects<4, true, true>(q4, c6, act, d, lq, lc);
-      else if (__any(act && ml > 8)) rej = band_bound_rejects<3, true, true>(q3, c5, act, d, lq, lc);
-      else rej = band_bound_rejects<2, true, true>(q2, c4, act, d, lq, lc);
-    } else {
-      if (__any(act && ml > 12)) rej = band_bound_rejects<4, true>(q4, c6, act, d, lq, lc);
-      else if (__any(act && ml > 8)) rej = band_bound_rejects<3, true>(q3, c5, act, d, lq, lc);
-      else rej = band_bound_rejects<2, true>(q2, c4, act, d, lq, lc);
-    }
-  }
-  if (act) out[i] = rej ? 1 : 0;
-}
-int debug_band_bound(int device, const uint8_t* q_rows, const uint8_t* c_rows, const uint8_t* lq, const uint8_t* lc, size_t n, int d, int form,
-                     uint8_t* out, std::string& err) {
-  if (n == 0) return ANX_OK;
-  if (n > (1u << 30) || d < 0 || d > 3 || form < 0 || form > 2) { err = "band bound: bad arguments"; return ANX_EINVAL; }
-  HIP_TRY(hipSetDevice(device));
-  uint4 *dq = nullptr, *dc = nullptr;
-  uint8_t *dlq = nullptr, *dlc = nullptr, *dout = nullptr;
-  int rc = ANX_OK;
-  auto cleanup = [&]() { for (void* p : {(void*)dq, (void*)dc, (void*)dlq, (void*)dlc, (void*)dout}) if (p) (void)hipFree(p); };
-  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
-  hipError_t e;
-  if ((e = hipMalloc(reinterpret_cast<void**>(&dq), n * 16)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&dc), n * 16)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&dlq), n)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&dlc), n)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&dout), n)) != hipSuccess)
-    return fail_hip(e);
-  if ((e = hipMemcpy(dq, q_rows, n * 16, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(dc, c_rows, n * 16, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(dlq, lq, n, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(dlc, lc, n, hipMemcpyHostToDevice)) != hipSuccess)
-    return fail_hip(e);
-  hipLaunchKernelGGL(k_debug_band_bound, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, 0, dq, dc, dlq, dlc, (uint32_t)n, d, form, dout);
-  if ((e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(out, dout, n, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e);
-  cleanup();
-  return rc;
-}
-
-// ---- test hook: the run's prefix sum alone (anx_debug_exclusive_scan; tests/test_gpu_prefix_sum.py) -----------------------------------
-// out[0 .. n] = the exclusive prefix sum of in[0 .. n) as exclusive_scan computes it on the device (out[n] = the total), copy (may be
-// nullptr) = out[0 .. n) through the kernel's second output.
-int debug_exclusive_scan(int device, const uint32_t* in, size_t n, uint32_t* out, uint32_t* copy, std::string& err) {
-  if (n >= ((size_t)1 << 31)) { err = "prefix sum: more than 2^31 elements"; return ANX_EINVAL; }
-  HIP_TRY(hipSetDevice(device));
-  uint32_t *din = nullptr, *dout = nullptr, *dcopy = nullptr, *dtmp = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)din, (void*)dout, (void*)dcopy, (void*)dtmp}) if (p) (void)hipFree(p); };
-  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
-  hipError_t e;
-  if ((e = hipMalloc(reinterpret_cast<void**>(&din), (n + 1) * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&dout), (n + 1) * 4)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&dcopy), (n + 1) * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&dtmp), scan_tmp_bytes(n))) != hipSuccess)
-    return fail_hip(e);
-  if (n && (e = hipMemcpy(din, in, n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e);
-  if (exclusive_scan(din, (uint32_t)n, dout, dtmp, 0, copy ? dcopy : nullptr)) return fail_hip(hipGetLastError());
-  if ((e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(out, dout, (n + 1) * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-      (copy && n && (e = hipMemcpy(copy, dcopy, n * 4, hipMemcpyDeviceToHost)) != hipSuccess))
-    return fail_hip(e);
-  cleanup();
-  return ANX_OK;
-}
-
-// ---- test hook: k_rank alone on hand-made candidate rows (anx_debug_rank_rows; tests/test_gpu_rank_rows.py) ---------------------------
-// soff = the exclusive sum of counts; the rows as a run lays them out (c_rows, or segments of seg_cap records + ent_rec + surplus in
-// c_rows); t_key / r_rows / r_count sized by the total whatever row_cap says, r_rows and r_count filled with 0xFF bytes; launch_rank.
-int debug_rank_rows(int device, const DebugRankIn& in, uint32_t* out_count, void* out_rows, std::string& err) {
-  const size_t nq = in.nq;
-  if (nq == 0) return ANX_OK;
-  if (nq >= ((size_t)1 << 28)) { err = "rank rows: too many queries"; return ANX_EINVAL; }
-  std::vector<uint32_t> soff(nq + 1, 0u);
-  uint64_t total64 = 0;
-  for (size_t q = 0; q < nq; ++q) { soff[q] = (uint32_t)total64; total64 += in.counts[q]; if (total64 >= (1ull << 31)) { err = "rank rows: more than 2^31 rows"; return ANX_EINVAL; } }
-  soff[nq] = (uint32_t)total64;
-  const size_t total = (size_t)total64, C = in.seg_cap;
-  for (size_t r = 0; r < total; ++r) {
-    if (in.position[r] >= (1u << 20)) { err = "rank rows: expansion position beyond 2^20"; return ANX_EINVAL; }
-    if (C && (in.position[r] != 0 || (in.via && in.via[r] != 0xFFFFFFFFu))) { err = "rank rows: segments hold rows without expansion position and via only"; return ANX_EINVAL; }
-  }
-  if (C && in.any_variants) { err = "rank rows: no segments with variant lists"; return ANX_EINVAL; }
-  if (C && nq * C >= ((size_t)1 << 31)) { err = "rank rows: segments too large"; return ANX_EINVAL; }
-  std::vector<SurvRow> rows(total ? total : 1, SurvRow{0.0, 0ull, 0u, 0u, 0xFFFFFFFFu, 0u});
-  std::vector<SurvSeg> seg(nq * C + 1, SurvSeg{0.0, 0u, 0u});  // (one spare record behind the last segment)
-  std::vector<EntRec> ent(C && total ? total : 1, EntRec{0u, 0u, 0u, 0u});
-  for (size_t q = 0; q < nq; ++q)
-    for (size_t i = 0; i < in.counts[q]; ++i) {
-      const size_t e = soff[q] + i;
-      if (i < C) {
-        seg[q * C + i] = SurvSeg{in.score[e], (uint32_t)e, 0u};
-        ent[e] = EntRec{in.vocab[e], in.freq[e], in.order[e], 0u};
-      } else {
-        rows[e - C] = SurvRow{in.score[e], (unsigned long long)in.order[e] << 20 | in.position[e], in.vocab[e], in.freq[e], in.via ? in.via[e] : 0xFFFFFFFFu, 0u};
-      }
-    }
-  HIP_TRY(hipSetDevice(device));
-  uint32_t *d_soff = nullptr, *d_maxf = nullptr, *d_qex = nullptr, *d_count = nullptr, *d_ovf = nullptr;
-  SurvRow* d_rows = nullptr;
-  SurvSeg* d_seg = nullptr;
-  EntRec* d_ent = nullptr;
-  double* d_tkey = nullptr;
-  DevRow* d_out = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)d_soff, (void*)d_maxf, (void*)d_qex, (void*)d_count, (void*)d_ovf, (void*)d_rows, (void*)d_seg, (void*)d_ent, (void*)d_tkey, (void*)d_out}) if (p) (void)hipFree(p); };
-  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
-  const size_t out_bytes = (total ? total : 1) * sizeof(DevRow);
-  hipError_t e;
-  if ((e = hipMalloc(reinterpret_cast<void**>(&d_soff), (nq + 1) * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_maxf), nq * 4)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_qex), nq * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_count), nq * 4)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_ovf), 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_rows), rows.size() * sizeof(SurvRow))) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_seg), seg.size() * sizeof(SurvSeg))) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_ent), ent.size() * sizeof(EntRec))) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_tkey), (total ? total : 1) * 8)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes)) != hipSuccess)
-    return fail_hip(e);
-  if ((e = hipMemcpy(d_soff, soff.data(), (nq + 1) * 4, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_maxf, in.maxfreq, nq * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(d_qex, in.qexpand, nq * 4, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_ovf, &in.overflow, 4, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(d_rows, rows.data(), rows.size() * sizeof(SurvRow), hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(d_seg, seg.data(), seg.size() * sizeof(SurvSeg), hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(d_ent, ent.data(), ent.size() * sizeof(EntRec), hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemset(d_tkey, 0, (total ? total : 1) * 8)) != hipSuccess || (e = hipMemset(d_count, 0xFF, nq * 4)) != hipSuccess || (e = hipMemset(d_out, 0xFF, out_bytes)) != hipSuccess)
-    return fail_hip(e);
-  RankArgs ra{};
-  ra.cutoff_threshold = in.cutoff_threshold;
-  ra.max_matches = in.max_matches;
-  ra.freq_weight = in.freq_weight;
-  ra.have_freq = in.have_freq;
-  ra.any_variants = in.any_variants;
-  launch_rank(ra, 0, (uint32_t)nq, d_soff, d_rows, d_maxf, d_qex, d_tkey, d_out, d_count, in.row_cap, d_ovf, C ? SegRows{d_seg, (uint32_t)C, d_ent} : SegRows{nullptr, 0u, nullptr});
-  if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(out_count, d_count, nq * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-      (total && (e = hipMemcpy(out_rows, d_out, total * sizeof(DevRow), hipMemcpyDeviceToHost)) != hipSuccess))
-    return fail_hip(e);
-  cleanup();
-  return ANX_OK;
-}
-
-// ---- test hook: the scoring stage alone on a pair list the caller laid out (anx_debug_score_slots; tests/test_gpu_score_slots.py) ------
-// The band-match bound (kernels_swar.hpp band_bound_rejects) on the host: positions of either string without an equal symbol of the other
-// one within +-d positions; more than d of them on a side rejects the pair.
-static bool host_band_bound_rejects(const uint8_t* q, int lq, const uint8_t* c, int lc, int d) {
-  int unA = 0, unB = 0;
-  for (int i = 0; i < lq; ++i) {
-    bool hit = false;
-    for (int j = std::max(0, i - d); j <= std::min(lc - 1, i + d); ++j) hit = hit || q[i] == c[j];
-    unA += !hit;
-  }
-  for (int j = 0; j < lc; ++j) {
-    bool hit = false;
-    for (int i = std::max(0, j - d); i <= std::min(lq - 1, j + d); ++i) hit = hit || q[i] == c[j];
-    unB += !hit;
-  }
-  return unA > d || unB > d;
-}
-// Everything is checked on the host before the first launch (a wrong test input is refused, never gathered from); the device buffers of
-// the stage are the hook's own (the batch keeps its pair list and results), filled with 0xFF bytes, and launched through
-// score_stage_launch like a run's.
-int debug_score_slots(const HostModel& m, const DeviceLexicon* dl, const Batch* b, const DebugScoreIn& in, const DebugScoreOut& out, std::string& err) {
-  if (!dl || !b) { err = "score slots: the model is not resident on a device"; return ANX_ENODEVICE; }
-  const size_t nq = b->nq, n_input = b->n_input, C = in.seg_cap;
-  const uint32_t region_cap = 1u << (in.region_shift & 31u);
-  auto refuse = [&](const std::string& msg) { err = "score slots: " + msg; return ANX_EINVAL; };
-  if (in.region_shift < 10 || in.region_shift > 16) return refuse("region_shift outside 10 .. 16");
-  if (in.surv_region_cap == 0 || in.list_cap == 0) return refuse("a capacity of 0");
-  if (in.surv_region_cap > (1u << 16) || in.list_cap > (1u << 16)) return refuse("a capacity beyond 65536 per region");
-  if (in.blk == 0 || in.blk % 256 != 0 || in.blk > FS_BLK) return refuse("blk is no multiple of 256 up to " + std::to_string(FS_BLK));
-  if (nq == 0 || nq >= ((size_t)1 << 20)) return refuse("the batch holds no query (or more than 2^20)");
-  if (C && (C > 1024 || seg_wanted(b) == 0 || dl->any_variants)) return refuse("no per-query segments for this model and batch (variant lists, StopAtExactMatch, freq_weight, switch)");
-  for (uint32_t r = 0; r < SCAN_REGIONS; ++r)
-    if (in.fills[r] > region_cap) return refuse("fill of region " + std::to_string(r) + " beyond the region");
-  HIP_TRY(hipSetDevice(dl->device));
-  { const int rc = ensure_order(b, err); if (rc) return rc; }
-  const int stop = b->params.stop_at_exact_match ? 1 : 0;
-  ScorePlan plan;
-  { const int rc = score_stage_plan(m, dl, b->params.score_threshold, b->qw, b->dmax, true, plan, err); if (rc) return rc; }
-  if (in.one_launch && plan.threads != 256) return refuse("the one-launch list kernels take 256 threads: the per-lane state of this model and batch allows " + std::to_string(plan.threads));
-  // what the checks read: the queries' and entries' records (first 16 symbols, meta)
-  std::vector<uint32_t> pos_of(n_input, 0xFFFFFFFFu);
-  for (size_t q = 0; q < nq; ++q) if (b->order[q] < n_input) pos_of[b->order[q]] = (uint32_t)q;
-  std::vector<uint4> qrec(2 * nq), erec(2 * (size_t)dl->nentries + 2);
-  HIP_TRY(hipMemcpy(qrec.data(), b->q_rec, 2 * nq * sizeof(uint4), hipMemcpyDeviceToHost));
-  if (dl->nentries) HIP_TRY(hipMemcpy(erec.data(), dl->e_rec, 2 * (size_t)dl->nentries * sizeof(uint4), hipMemcpyDeviceToHost));
-  const bool bit_planes = dl->nsym <= 32 && !switches().scan_sad;
-  std::vector<uint2> raw((size_t)SCAN_REGIONS << in.region_shift, make_uint2(RAW_INVALID, 0xFFFFFFFFu));
-  {
-    size_t i = 0;
-    for (uint32_t r = 0; r < SCAN_REGIONS; ++r)
-      for (uint32_t k = 0; k < in.fills[r]; ++k, ++i) {
-        const uint32_t qi = in.slots[2 * i], ew = in.slots[2 * i + 1];
-        if (qi == RAW_INVALID) continue;
-        const std::string at = " (slot " + std::to_string(k) + " of region " + std::to_string(r) + ")";
-        if (qi >= n_input || pos_of[qi] == 0xFFFFFFFFu) return refuse("query index out of range or not encoded" + at);
-        // the entry id as the GENERAL round reads it (30 bits): a flagged slot of a mixed wave is gathered there, not under the short round's 26-bit mask
-        const uint32_t q = pos_of[qi], e = ew & RAW_ENTRY_MASK;
-        if (e >= dl->nentries) return refuse("entry id out of range" + at);
-        if ((ew & 0x80000000u) && !stop) return refuse("bit 31 (exact class) outside a StopAtExactMatch batch" + at);
-        if (ew & RAW_PREFILTERED) {  // the scan's contract (kernels_scan.hpp, the fused prefilter of emit_dense)
-          const uint32_t qm = qrec[2 * (size_t)q + 1].x, em = erec[2 * (size_t)e + 1].x;
-          const int lq = qm & 0xFF, d = (qm >> 16) & 0xFF, lc = em & 0xFF;
-          if (!bit_planes || stop || (ew & 0x80000000u)) return refuse("RAW_PREFILTERED outside a bit-plane model or in a StopAtExactMatch batch" + at);
-          if (e >= (1u << 26)) return refuse("RAW_PREFILTERED with an entry id beyond 2^26" + at);
-          if (lq > 16 || lc > 16 || d > 3 || std::abs(lq - lc) > d) return refuse("RAW_PREFILTERED on a pair the scan does not filter (lengths, d)" + at);
-          if (host_band_bound_rejects(reinterpret_cast<const uint8_t*>(&qrec[2 * (size_t)q]), lq, reinterpret_cast<const uint8_t*>(&erec[2 * (size_t)e]), lc, d))
-            return refuse("RAW_PREFILTERED on a pair the band-match bound rejects" + at);
-        }
-        raw[((size_t)r << in.region_shift) + k] = make_uint2(q, ew);
-      }
-  }
-  // ---- device buffers of the stage ------------------------------------------------------------------------------------------------------
-  const size_t R = raw.size(), nsurv = (size_t)SCAN_REGIONS * in.surv_region_cap, nlist = (size_t)SCAN_REGIONS * in.list_cap;
-  uint2* d_raw = nullptr;
-  double* d_pscore = nullptr;
-  uint32_t *d_pmeta = nullptr, *d_ctl = nullptr, *d_q3 = nullptr, *d_lists = nullptr;
-  SurvRec* d_surv = nullptr;
-  SurvSeg* d_seg = nullptr;
-  void* d_cold = nullptr;
-  FsCold* h_cold = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_raw, (void*)d_pscore, (void*)d_pmeta, (void*)d_ctl, (void*)d_q3, (void*)d_lists, (void*)d_surv, (void*)d_seg, d_cold}) if (p) (void)hipFree(p);
-    if (h_cold) (void)hipHostFree(h_cold);
-  };
-  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
-  hipError_t e;
-  if ((e = hipMalloc(reinterpret_cast<void**>(&d_raw), R * sizeof(uint2))) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_pscore), R * 8)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_pmeta), R * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_ctl), HR_N * 4)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_q3), 3 * nq * 4)) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_lists), 3 * nlist * 4)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_surv), nsurv * sizeof(SurvRec))) != hipSuccess || (e = hipMalloc(reinterpret_cast<void**>(&d_seg), (nq * C + 1) * sizeof(SurvSeg))) != hipSuccess ||
-      (e = hipMalloc(&d_cold, sizeof(FsCold))) != hipSuccess || (e = hipHostMalloc(reinterpret_cast<void**>(&h_cold), sizeof(FsCold), hipHostMallocDefault)) != hipSuccess)
-    return fail_hip(e);
-  std::vector<uint32_t> ctl(HR_N, 0u);
-  for (uint32_t r = 0; r < SCAN_REGIONS; ++r) ctl[HR_RCTR + r * RC_STRIDE + RC_RAW] = in.fills[r];
-  if ((e = hipMemcpy(d_raw, raw.data(), R * sizeof(uint2), hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_ctl, ctl.data(), HR_N * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemset(d_pscore, 0xFF, R * 8)) != hipSuccess || (e = hipMemset(d_pmeta, 0xFF, R * 4)) != hipSuccess || (e = hipMemset(d_q3, 0xFF, 3 * nq * 4)) != hipSuccess ||
-      (e = hipMemset(d_lists, 0xFF, 3 * nlist * 4)) != hipSuccess || (e = hipMemset(d_surv, 0xFF, nsurv * sizeof(SurvRec))) != hipSuccess ||
-      (e = hipMemset(d_seg, 0xFF, (nq * C + 1) * sizeof(SurvSeg))) != hipSuccess)
-    return fail_hip(e);
-  ScoreStage S{};
-  S.nq = (uint32_t)nq; S.stop = stop; S.region_shift = in.region_shift; S.fill_cap = region_cap; S.blk = in.blk; S.one_launch = in.one_launch != 0;
-  S.raw = d_raw; S.q_meta = b->q_meta; S.q_rows = b->q_rows; S.q_rec = b->q_rec; S.qexact = b->qexact; S.p_score = d_pscore; S.p_meta = d_pmeta;
-  S.qsurv = d_q3; S.rctr = d_ctl + HR_RCTR; S.sctr = d_ctl + HR_SCTR; S.lctr = d_ctl + HR_LCTR; S.counters = d_ctl + HR_CTR;
-  S.so = SurvOut{d_surv, d_ctl + HR_SCTR, in.surv_region_cap, C ? d_seg : nullptr, (uint32_t)C};
-  S.need_lists = score_stage_needs_lists(plan, dl); S.list8 = d_lists; S.listg = d_lists + nlist; S.listw = d_lists + 2 * nlist; S.list_cap = in.list_cap;
-  S.h_cold = h_cold; S.d_cold = d_cold; S.ev_fs0 = nullptr; S.ev_fs1 = nullptr;
-  { const int rc = score_stage_launch(dl, plan, S, 0, err); if (rc) { cleanup(); return rc; } }
-  // ---- everything back, in the caller's terms (input indices, slots in the caller's order) ---------------------------------------------
-  std::vector<uint32_t> pmeta(R), q3(3 * nq);
-  std::vector<double> pscore(R);
-  std::vector<SurvRec> surv(nsurv);
-  std::vector<SurvSeg> seg(nq * C + 1);
-  if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(pmeta.data(), d_pmeta, R * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-      (e = hipMemcpy(pscore.data(), d_pscore, R * 8, hipMemcpyDeviceToHost)) != hipSuccess || (e = hipMemcpy(q3.data(), d_q3, 3 * nq * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-      (e = hipMemcpy(ctl.data(), d_ctl, HR_N * 4, hipMemcpyDeviceToHost)) != hipSuccess || (e = hipMemcpy(surv.data(), d_surv, nsurv * sizeof(SurvRec), hipMemcpyDeviceToHost)) != hipSuccess ||
-      (e = hipMemcpy(seg.data(), d_seg, (nq * C + 1) * sizeof(SurvSeg), hipMemcpyDeviceToHost)) != hipSuccess)
-    return fail_hip(e);
-  cleanup();
-  {
-    size_t i = 0;
-    for (uint32_t r = 0; r < SCAN_REGIONS; ++r)
-      for (uint32_t k = 0; k < in.fills[r]; ++k, ++i) {
-        out.meta[i] = pmeta[((size_t)r << in.region_shift) + k];
-        out.score[i] = pscore[((size_t)r << in.region_shift) + k];
-      }
-  }
-  for (size_t q = 0; q < nq; ++q) {
-    const uint32_t qi = b->order[q];
-    if (qi >= n_input) continue;
-    for (int k = 0; k < 3; ++k) out.qcount[k * n_input + qi] = q3[k * nq + q];
-    if (C) memcpy(static_cast<char*>(out.seg) + (size_t)qi * C * sizeof(SurvSeg), &seg[q * C], C * sizeof(SurvSeg));
-  }
-  for (uint32_t r = 0; r < SCAN_REGIONS; ++r) {
-    const uint32_t fill = ctl[HR_SCTR + r * RC_STRIDE];
-    for (uint32_t k = 0; k < std::min(fill, in.surv_region_cap); ++k) {  // (written records: the query as its input index)
-      SurvRec& s = surv[(size_t)r * in.surv_region_cap + k];
-      if (s.q < nq) s.q = b->order[s.q];
-    }
-    out.ctr[0 * SCAN_REGIONS + r] = fill;
-    for (uint32_t l = 0; l < 3; ++l) out.ctr[(1 + l) * SCAN_REGIONS + r] = ctl[HR_LCTR + (l * SCAN_REGIONS + r) * RC_STRIDE];
-    out.ctr[4 * SCAN_REGIONS + r] = ctl[HR_SCTR + r * RC_STRIDE + 1];
-  }
-  memcpy(out.surv, surv.data(), nsurv * sizeof(SurvRec));
-  *out.skipped = ctl[HR_CTR + CTR_SKIPPED];
-  return ANX_OK;
-}
-
-// ---- test hook: the scan stage alone (anx_debug_scan_pairs; tests/test_gpu_scan_door.py) ------------------------------------------------
-// The tiles are the encoder's own, never the caller's: the batch's (batch form) or those small_encode_launch lays on a borrowed context of the
-// small path (small form, as small_find borrows one).  What is plain data in ScanArgs is the caller's and validated on the host before anything
-// is launched.  The pair list, its counters and the per-query counts are the hook's own buffers: the pair list (and SCAN_GUARD slots behind
-// it) starts as 0xFE bytes -- neither RAW_INVALID nor a pair -- the counters as 0.  The launch is scan_stage_launch / launch_scan_small.
-constexpr uint32_t SCAN_GUARD = 4096;  // slots behind the pair list that must keep the fill
-int debug_scan_pairs(const HostModel& m, const DeviceLexicon* dl, const Batch* b, const DebugScanIn& in, const DebugScanOut& out, std::string& err) {
-  if (!dl) { err = "scan pairs: the model is not resident on a device"; return ANX_ENODEVICE; }
-  auto refuse = [&](const std::string& msg) { err = "scan pairs: " + msg; return ANX_EINVAL; };
-  const bool small = b == nullptr;
-  if (in.region_shift < 10 || in.region_shift > 25) return refuse("region_shift outside 10 .. 25");
-  for (uint32_t c : {in.chunk, in.chunk_fused, in.chunk_first})
-    if (c < 32 || c > 1024) return refuse("a chunk size outside 32 .. 1024");
-  if (in.fuse && (!in.drop_len || in.want_exact)) return refuse("fuse without drop_len or with want_exact: the fused filter takes pairs that passed the length test (as a run sets it)");
-  uint32_t lens[SMALL_MAX];
-  uint32_t maxbytes = 0;
-  if (small) {
-    if (in.n == 0 || in.n > SMALL_MAX) return refuse("the small form takes 1 .. " + std::to_string(SMALL_MAX) + " strings");
-    if (in.slots != 8 && in.slots != 16 && in.slots != 32) return refuse("tile slots per query are 8, 16 or 32");
-    if ((size_t)in.slots * in.n > (size_t)8 * SMALL_MAX) return refuse("more tile slots than a context of the small path holds");
-    if (in.want_exact || in.count_pairs || !in.drop_len) return refuse("the small call's kernel has no instance for StopAtExactMatch, per-query counts or every pair");
-    if (dl->nplanes > 42) return refuse("the small path does not take this alphabet");
-    for (size_t i = 0; i < in.n; ++i) {
-      const size_t l = in.utf8[i] ? strlen(in.utf8[i]) : 0;
-      if (l > SMALL_MAX_BYTES) return refuse("a string of more than " + std::to_string(SMALL_MAX_BYTES) + " bytes");
-      lens[i] = (uint32_t)l;
-      maxbytes = std::max(maxbytes, (uint32_t)l);
-    }
-  } else {
-    if (b->nq >= ((size_t)1 << 26)) return refuse("more than 2^26 queries");
-    if (in.want_exact && (!b->params.stop_at_exact_match || !b->qexact)) return refuse("want_exact with a batch that was not encoded for StopAtExactMatch");
-  }
-  HIP_TRY(hipSetDevice(dl->device));
-  const size_t nq = small ? in.n : b->nq;
-  const uint32_t ntiles = small ? in.slots * (uint32_t)in.n : b->ntiles;
-  const size_t R = (size_t)SCAN_REGIONS << in.region_shift;
-  uint2* d_raw = nullptr;
-  uint32_t *d_rctr = nullptr, *d_qpairs = nullptr;
-  SmallCtx* c = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_raw, (void*)d_rctr, (void*)d_qpairs}) if (p) (void)hipFree(p);
-    if (c) { (void)hipStreamSynchronize(c->st); small_ctx_release(c); }
-  };
-  auto fail_hip = [&](hipError_t e) { err = std::string("HIP: ") + hipGetErrorString(e); cleanup(); return ANX_ENODEVICE; };
-  hipError_t e;
-  if ((e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e);  // (the encoder's streams: the tiles and query arrays are complete)
-  if ((e = hipMalloc(reinterpret_cast<void**>(&d_raw), (R + SCAN_GUARD) * sizeof(uint2))) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_rctr), SCAN_REGIONS * RC_STRIDE * 4)) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&d_qpairs), std::max<size_t>(nq, 1) * 4)) != hipSuccess)
-    return fail_hip(e);
-  if ((e = hipMemset(d_raw, 0xFE, (R + SCAN_GUARD) * sizeof(uint2))) != hipSuccess || (e = hipMemset(d_rctr, 0, SCAN_REGIONS * RC_STRIDE * 4)) != hipSuccess ||
-      (e = hipMemset(d_qpairs, 0, std::max<size_t>(nq, 1) * 4)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)
-    return fail_hip(e);
-  ScanStage S{};
-  S.ntiles = ntiles;
-  S.raw = d_raw; S.region_cap = 1u << in.region_shift; S.rctr = d_rctr;
-  S.chunk = in.chunk; S.chunk_fused = in.chunk_fused; S.chunk_first = in.chunk_first;
-  S.want_exact = in.want_exact ? 1 : 0; S.drop_len = in.drop_len ? 1 : 0; S.fuse = in.fuse ? 1 : 0; S.twins = in.twins ? 1 : 0;
-  S.qpairs = in.count_pairs ? d_qpairs : nullptr; S.dbg = 0;
-  const Tile* d_tiles = nullptr;
-  const uint32_t *d_qorig = nullptr, *d_qmeta = nullptr;
-  uint32_t nadj = 0, nsad = 0;
-  if (small) {
-    c = small_ctx_acquire(dl, err);
-    if (!c) { (void)hipGetLastError(); cleanup(); return ANX_ENODEVICE; }
-    uint32_t* h_off = reinterpret_cast<uint32_t*>(c->h_in + SMALL_IN_BLOB);
-    size_t pos = 0;
-    for (size_t i = 0; i < in.n; ++i) {  // the inputs -> pinned staging, as small_find packs them
-      h_off[i] = (uint32_t)pos;
-      if (lens[i]) memcpy(c->h_in + pos, in.utf8[i], lens[i]);
-      c->h_in[pos + lens[i]] = '\0';
-      pos += (size_t)lens[i] + 1;
-    }
-    h_off[in.n] = (uint32_t)pos;
-    memset(c->h_in + pos, 0, 16);
-    const uint32_t qw = std::max<uint32_t>(1u, (maxbytes + 15u) / 16u);
-    SmallEnc enc = c->enc;
-    enc.text = nullptr; enc.textoff = nullptr;
-    SmallZero z{};  // (the context's counters are not this call's: nothing to clear)
-    const int rc = small_encode_launch(m, dl, enc, reinterpret_cast<const uint8_t*>(c->h_in), h_off, (uint32_t)in.n, qw, *in.params, z, in.slots, true, h_off, c->st, err);
-    if (rc) { cleanup(); return rc; }
-    S.tiles = c->enc.tiles; S.q_bits = c->enc.q_bits; S.q_cv = c->enc.q_cv; S.q_rec = c->enc.q_rec; S.qexact = c->enc.qexact;
-    launch_scan_small(dl, S, c->st);
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(c->st)) != hipSuccess) return fail_hip(e);
-    d_tiles = c->enc.tiles; d_qorig = c->enc.q_orig; d_qmeta = c->enc.q_meta;
-  } else {
-    nsad = b->n_sad_tiles; nadj = std::min(b->n_adj_tiles, ntiles - nsad);
-    S.tiles = b->d_tiles; S.n_adj_tiles = b->n_adj_tiles; S.n_sad_tiles = nsad; S.q_bits = b->q_bits; S.q_cv = b->q_cv; S.q_rec = b->q_rec; S.qexact = b->qexact;
-    if (ntiles) scan_stage_launch(dl, S, 0, nullptr, nullptr);
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e);
-    d_tiles = b->d_tiles; d_qorig = b->q_orig; d_qmeta = b->q_meta;
-  }
-  // ---- everything back ----------------------------------------------------------------------------------------------------------------
-  static_assert(sizeof(Tile) == 15 * sizeof(uint32_t), "a tile is 15 words");
-  uint32_t* tiles = static_cast<uint32_t*>(malloc(std::max<size_t>(ntiles, 1) * sizeof(Tile)));
-  std::vector<uint2> guard(SCAN_GUARD);
-  if (!tiles) { cleanup(); err = "out of memory"; return ANX_EINVAL; }
-  if ((ntiles && (e = hipMemcpy(tiles, d_tiles, (size_t)ntiles * sizeof(Tile), hipMemcpyDeviceToHost)) != hipSuccess) ||
-      (nq && ((e = hipMemcpy(out.q_orig, d_qorig, nq * 4, hipMemcpyDeviceToHost)) != hipSuccess || (e = hipMemcpy(out.q_meta, d_qmeta, nq * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-              (e = hipMemcpy(out.qpairs, d_qpairs, nq * 4, hipMemcpyDeviceToHost)) != hipSuccess)) ||
-      (e = hipMemcpy(out.raw, d_raw, R * sizeof(uint2), hipMemcpyDeviceToHost)) != hipSuccess ||
-      (e = hipMemcpy(guard.data(), d_raw + R, SCAN_GUARD * sizeof(uint2), hipMemcpyDeviceToHost)) != hipSuccess ||
-      (e = hipMemcpy(out.rctr, d_rctr, SCAN_REGIONS * RC_STRIDE * 4, hipMemcpyDeviceToHost)) != hipSuccess) {
-    free(tiles);
-    return fail_hip(e);
-  }
-  cleanup();
-  // the kind of every query as its tile tests it (kend), 0 = count vectors; UINT32_MAX = in no tile
-  for (size_t q = 0; q < nq; ++q) out.q_kind[q] = 0xFFFFFFFFu;
-  for (uint32_t i = 0; i < ntiles; ++i) {
-    const Tile& t = reinterpret_cast<const Tile*>(tiles)[i];
-    for (uint32_t j = 0; j < t.nq && (size_t)t.q0 + j < nq; ++j)
-      out.q_kind[t.q0 + j] = t.kind == 0u ? 0u : j < (t.kend & 0xFFu) ? 1u : j < ((t.kend >> 8) & 0xFFu) ? 2u : j < ((t.kend >> 16) & 0xFFu) ? 3u : 4u;
-  }
-  uint32_t touched = 0;
-  for (const uint2& g : guard) touched += (g.x != 0xFEFEFEFEu || g.y != 0xFEFEFEFEu) ? 1u : 0u;
-  out.counts[0] = ntiles; out.counts[1] = nadj; out.counts[2] = small ? 0u : ntiles - nsad - nadj; out.counts[3] = nsad; out.counts[4] = (uint32_t)nq;
-  out.counts[5] = touched;
-  *out.tiles = tiles;
-  return ANX_OK;
-}
 
 }  // namespace anx

@@ -1,4 +1,4 @@
-// engine_internal.h -- shared by the HIP translation units of the engine (engine.hip, encode.hip); include after hip_runtime.h
+// engine_internal.h -- shared by the HIP translation units of the engine (engine.hip, runtime.hip, results.hip, encode.hip, ...); include after hip_runtime.h
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -27,17 +27,38 @@ __host__ __device__ inline bool tile_probes(uint32_t balln, uint32_t window, uns
 }
 inline bool probe_enabled() { return !switches().scan_walk_flat; }
 
-// Kernel timer (engine.hip; off unless anx_debug_kernel_timer(1)): HIP events around the launches of the kernels that dominate the
+// ---- runtime.hip: what the engine keeps per device, no kernel -----------------------------------------------------------------------------
+// Kernel timer (off unless anx_debug_kernel_timer(1)): HIP events around the launches of the kernels that dominate the
 // configurations bench.py reports (k_scan_bits, k_filter_score, k_conf_script, k_lattice), on the launch stream; resolved lazily
 // when the totals are read.  ktimer_begin returns a handle (or -1 when off) for ktimer_end.
 int ktimer_begin(const char* name, hipStream_t st);
 void ktimer_end(int handle, hipStream_t st);
-// per-device scratch pool (engine.hip): freed blocks are kept for the next batch
+// per-device scratch pool: freed blocks are kept for the next batch
 hipError_t pool_malloc(void** p, size_t bytes);
 void pool_free(void* p);
+// the lexicons resident on a device: the last one to leave empties the device's pool (idle small-call contexts, cached blocks, shells)
+void lexicon_registered(int device);
+void lexicon_released(int device);   // (the current device is `device`)
+// the idle contexts of the small call (engine.hip small_path.hpp, where they are made): destroyed before a pool is emptied
+void small_ctxs_destroy(int device);
+// a non-blocking stream on the current device (high: at the device's highest priority), or nullptr
+void* make_stream(bool high);
 // non-blocking stream for one call of the device-side encoder (kept per device, reused)
 hipStream_t encoder_stream_acquire(int device);
 void encoder_stream_release(int device, hipStream_t s);
+// the library's own two streams for asynchronous runs, alternately (the current device is `device`); nullptr: none
+hipStream_t run_stream_next(int device);
+// events + pinned read-back block (pinned_bytes) of a batch: from the shells of the device's freed batches, created when there is none
+struct BatchShell;
+int shell_acquire(int device, BatchShell& sh, size_t pinned_bytes, std::string& err);
+void shell_release(int device, BatchShell& sh);
+// The calling thread's current HIP device is not ours to change: entry points that run on a CALLER's thread (model upload / free,
+// stream create / destroy, pool trim) switch to the replica's device and put the caller's back when they return.
+struct DeviceGuard {
+  int prev = -1;
+  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); } }
+  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
 // confusable weighting on the device (conf.hip)
 struct DeviceConf;
 void conf_free(DeviceConf*);
@@ -200,11 +221,12 @@ struct PairsOnDevice {
 int pairs_chunk_enqueue(const HostModel& m, const DeviceLexicon* dl, const PairSpan* a, const PairSpan* b, size_t n, const anx_params* thr, PairScratch& sc,
                         PairsOnDevice& pd, std::string& err);
 
-// ---- the weight sweep (reweigh.hip): what it uses of engine.hip's translation unit --------------------------------------------------------
-// the measures behind the rows of a shard's gathered section, on the gather's device (engine.hip, next to batch_fetch_measures_into)
+// ---- results.hip: what the weight sweep (reweigh.hip) uses of the rows' way off the device ------------------------------------------------
+// the measures behind the rows of a shard's gathered section, on the gather's device (next to batch_fetch_measures_into)
 int batch_gather_measures(const HostModel& m, const DeviceLexicon* dl, const Batch* b, int dst_device, void* dst, size_t capacity, void* stream, std::string& err);
 // dl->vocab_ent (vocabulary id -> lexicon entry), built on first use as anx_batch_fetch_measures builds it; waits on st
 int replica_vocab_entries(const HostModel& m, const DeviceLexicon* dl, hipStream_t st, std::string& err);
+// ---- engine.hip: what results.hip and reweigh.hip use of the run's translation unit ------------------------------------------------------
 // the run's exclusive prefix sum (kernels_prefix.hpp): out[n + 1]; tmp: prefix_scan_tmp_bytes(n); copy: nullptr or a second array for out[0 .. n)
 size_t prefix_scan_tmp_bytes(size_t n);
 int prefix_scan_enqueue(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* tmp, hipStream_t st, uint32_t* copy);

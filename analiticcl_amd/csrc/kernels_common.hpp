@@ -1,5 +1,5 @@
 // kernels_common.hpp -- device-side structures shared by the kernels and the host driver (tiles, batch state, row records)
-// Part of the single translation unit engine.hip (included inside namespace anx); gfx950 only.
+// Included inside namespace anx by engine.hip and the other HIP units; gfx950 only.
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
@@ -73,11 +73,14 @@ struct DevAlphabet {  // tables of the device-side query encoder (encode.hip), d
 // What a batch needs from the runtime besides device memory: its events and the pinned block its run reads back into.  Creating and
 // destroying them per batch costs more than it looks -- hipHostFree waits for the DEVICE to go idle: a batch freed while the next one
 // was running serialised the two (round 5: the step with the encoder inside, 3.56 ms, was encode + run back to back, never
-// overlapped).  Freed batches hand theirs to the device's pool (engine.hip DevPool::shells); device_pool_trim releases them.
+// overlapped).  Freed batches hand theirs to the device's shells (runtime.hip shell_acquire / shell_release); device_pool_trim releases them.
 struct BatchShell {
   hipEvent_t ev[6] = {};
-  hipEvent_t ev_scan0 = nullptr, ev_fs0 = nullptr, ev_fs1 = nullptr, ev_done = nullptr, ev_in = nullptr;
-  uint32_t* h_read = nullptr;
+  hipEvent_t ev_scan0 = nullptr;   // just before the scan kernels (after the counter memsets)
+  hipEvent_t ev_fs0 = nullptr, ev_fs1 = nullptr;  // around k_filter_score
+  hipEvent_t ev_done = nullptr;    // after the read-back of a launched run
+  hipEvent_t ev_in = nullptr;      // the caller's stream at the time of an asynchronous run on one of the library's streams
+  uint32_t* h_read = nullptr;      // pinned: counters of the launched run (engine.hip HR_*), behind them the staging copy of FsCold
 };
 // Sizes of the last finished first run on this replica, per query: the next batch of the same parameters sizes its pair list, its
 // scoring grid and its survivor buffers from them (with a margin) instead of from worst-case estimates.  A wrong guess costs what a
@@ -165,7 +168,7 @@ struct DevRow {   // one ranked result row (device) for download / gather
   double dist_score, freq_score;
 };
 
-struct Batch {
+struct Batch : BatchShell {   // (its events and pinned read-back block: the shell, handed on when the batch is freed)
   int device = 0;
   size_t nq = 0;            // encoded queries
   anx_params params;
@@ -252,12 +255,6 @@ struct Batch {
   bool ran = false;
   bool keep_all_pairs = false;     // also materialise the pairs whose lengths differ by more than d (debug fetch of every pair)
   bool ran_keep_all = false;       // what the last run did
-  hipEvent_t ev[6] = {};
-  hipEvent_t ev_scan0 = nullptr;   // just before the scan kernels (after the counter memsets)
-  hipEvent_t ev_fs0 = nullptr, ev_fs1 = nullptr;  // around k_filter_score
-  hipEvent_t ev_done = nullptr;    // after the read-back of a launched run
-  hipEvent_t ev_in = nullptr;      // the caller's stream at the time of an asynchronous run on one of the library's streams
-  uint32_t* h_read = nullptr;      // pinned: counters of the launched run (engine.hip HR_*)
   bool launched = false;           // a run is enqueued and not yet finished
   uint32_t fill_cap_launched = 0;  // slots per region the scoring grid of the launched run covers
   uint32_t prev_maxfill = 0, prev_surv_fill = 0, prev_list_fill = 0;  // largest fills seen by earlier runs of this batch

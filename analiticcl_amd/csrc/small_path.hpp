@@ -138,23 +138,31 @@ static bool small_ctx_conf(SmallCtx* c) {
   c->cf_ready = true;
   return true;
 }
+// the idle contexts of a device, checked out per call
+namespace {
+struct SmallIdle { std::mutex mu; std::vector<SmallCtx*> v; };
+SmallIdle& small_idle_of(int device) {
+  static SmallIdle idle[64];
+  return idle[device >= 0 && device < 64 ? device : 0];
+}
+}  // namespace
 static SmallCtx* small_ctx_acquire(const DeviceLexicon* dl, std::string& err) {
-  DevPool& pl = pool_of(dl->device);
+  SmallIdle& si = small_idle_of(dl->device);
   {
-    std::lock_guard<std::mutex> g(pl.mu);
-    if (!pl.small_idle.empty()) { SmallCtx* c = pl.small_idle.back(); pl.small_idle.pop_back(); return c; }
+    std::lock_guard<std::mutex> g(si.mu);
+    if (!si.v.empty()) { SmallCtx* c = si.v.back(); si.v.pop_back(); return c; }
   }
   return small_ctx_create(dl, err);
 }
 static void small_ctx_release(SmallCtx* c) {
-  DevPool& pl = pool_of(c->device);
-  std::lock_guard<std::mutex> g(pl.mu);
-  pl.small_idle.push_back(c);
+  SmallIdle& si = small_idle_of(c->device);
+  std::lock_guard<std::mutex> g(si.mu);
+  si.v.push_back(c);
 }
-static void small_ctxs_destroy(int device) {  // (the current device is `device`)
-  DevPool& pl = pool_of(device);
+void small_ctxs_destroy(int device) {  // (the current device is `device`; runtime.hip pool_trim, before it empties the pool)
+  SmallIdle& si = small_idle_of(device);
   std::vector<SmallCtx*> drop;
-  { std::lock_guard<std::mutex> g(pl.mu); drop.swap(pl.small_idle); }
+  { std::lock_guard<std::mutex> g(si.mu); drop.swap(si.v); }
   for (SmallCtx* c : drop) small_ctx_destroy(c);
 }
 

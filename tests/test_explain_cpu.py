@@ -110,7 +110,7 @@ def test_explain_kernels_isa_metadata(tmp_path):
     """DESIGN.md section 5 "Measures of the ranked rows": no scratch, no VGPR or SGPR spills; k_row_measures keeps a 16 x 16 byte matrix
     and both strings per lane in LDS (128 lanes x 73 dwords) within 64 VGPRs, computes L1 with v_sad_u8 and writes a record as one
     16-byte store; k_row_measures_long keeps the 255-row matrix in LDS."""
-    ks, text = kernels_of("engine.hip", tmp_path)
+    ks, text = kernels_of("results.hip", tmp_path)
     one = {}
     for kernel in ("k_vocab_entry_scatter", "k_row_measuresENS", "k_row_measures_long"):
         r = [v for n, v in ks.items() if kernel in n]

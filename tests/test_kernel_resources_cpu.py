@@ -48,15 +48,12 @@ def test_row_kernels_do_not_spill(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("isa") / "engine.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S",
-                           "--cuda-device-only", "-o", out, os.path.join(CSRC, "engine.hip")], stderr=subprocess.DEVNULL)
-    text = open(out).read()
+    # the kernels of a run and of the small call (engine.hip) and those that take the ranked rows off the device (results.hip)
     res = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", text, re.S):
-        body = m.group(2)
-        res[m.group(1)] = {k: int(re.search(r"\." + k + r":\s+(\d+)", body).group(1))
-                           for k in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")}
+    for source in ("engine.hip", "results.hip"):
+        ks = _kernels_of(source, tmp_path_factory)
+        assert ks and not set(ks) & set(res), source
+        res.update(ks)
     assert len(res) > 20
     return res
 
