@@ -112,6 +112,29 @@ class GoldSummary(C.Structure):  # anx_gold_summary, 624 bytes
                 ("rr_fixed", C.c_uint64), ("n_results", C.c_uint64), ("gained_at_1", C.c_uint64), ("lost_at_1", C.c_uint64)]
 
 
+FIT_MAX_GRID, FIT_MAX_ROUNDS, FIT_MAX_PAIRS = 16, 256, 1 << 24  # anx.h ANX_FIT_MAX_GRID, ANX_FIT_MAX_ROUNDS, ANX_FIT_MAX_PAIRS
+ANX_FIT_ACC1, ANX_FIT_MRR = 0, 1
+FIT_OBJECTIVES = {"acc1": ANX_FIT_ACC1, "mrr": ANX_FIT_MRR}
+
+
+class FitCounts(C.Structure):  # anx_fit_counts, 24 bytes
+    _fields_ = [("at1", C.c_uint64), ("ranked", C.c_uint64), ("rr_fixed", C.c_uint64)]
+
+
+class FitParams(C.Structure):  # anx_fit_params
+    _fields_ = [("grid", C.POINTER(C.c_double)), ("n_grid", C.c_uint32), ("_pad", C.c_uint32), ("start", C.POINTER(C.c_double)),
+                ("objective", C.c_uint32), ("max_rounds", C.c_uint32), ("min_gain", C.c_uint64)]
+
+
+class FitRound(C.Structure):  # anx_fit_round, 40 bytes
+    _fields_ = [("pattern", C.c_uint32), ("grid_index", C.c_uint32), ("weight", C.c_double), ("counts", FitCounts)]
+
+
+class FitResult(C.Structure):  # anx_fit_result, 64 bytes
+    _fields_ = [("n_rounds", C.c_uint32), ("n_trial_rounds", C.c_uint32), ("stop", C.c_uint32), ("_pad", C.c_uint32),
+                ("start", FitCounts), ("final", FitCounts)]
+
+
 class MineParams(C.Structure):  # anx_mine_params
     _fields_ = [("context", C.c_uint32), ("anchors", C.c_uint32), ("no_sites", C.c_uint32), ("_reserved", C.c_uint32)]
 
@@ -294,6 +317,17 @@ def lib():
                                                  C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(sz)]),
         "anx_debug_conf_mask_text": (C.c_int, [C.POINTER(cp), sz, cp, cp, C.POINTER(C.c_uint64)]),
         "anx_debug_conf_sweep_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
+        "anx_fit_confusable_weights": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(cp), sz, C.POINTER(Params), C.POINTER(FitParams),
+                                                 C.POINTER(C.c_double), C.POINTER(FitRound), C.POINTER(FitCounts), C.POINTER(FitResult)]),
+        "anx_fit_confusable_weights_packed": (C.c_int, [vp, C.c_char_p, sz, C.c_char_p, sz, sz, C.POINTER(cp), sz, C.POINTER(Params),
+                                                        C.POINTER(FitParams), C.POINTER(C.c_double), C.POINTER(FitRound), C.POINTER(FitCounts),
+                                                        C.POINTER(FitResult)]),
+        "anx_debug_fit_confusable_weights_chunk": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), sz, C.POINTER(cp), sz, C.POINTER(Params),
+                                                             C.POINTER(FitParams), C.POINTER(C.c_double), C.POINTER(FitRound), C.POINTER(FitCounts),
+                                                             C.POINTER(FitResult), sz]),
+        "anx_debug_fit_select": (C.c_int, [C.POINTER(FitCounts), C.POINTER(C.c_double), sz, C.POINTER(C.c_double), sz, C.POINTER(FitCounts),
+                                           C.c_uint32, u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "anx_debug_fit_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
         "anx_default_mine_params": (None, [C.POINTER(MineParams)]),
         "anx_mine_confusables": (C.c_int, [vp, C.POINTER(cp), C.POINTER(cp), C.POINTER(C.c_uint32), sz, C.POINTER(MineParams),
                                            C.POINTER(C.POINTER(MineResult))]),

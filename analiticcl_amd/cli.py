@@ -25,7 +25,10 @@ weights are printed behind the seven parameters).  `sweep --candidates LIST.tsv 
 confusable list (what `mine --as-confusables` writes; its weight column is ignored) of at most 64 candidate patterns, and under the
 command line's parameters the output is one TSV line per set (evaluate_sweep_confusables) -- first the baseline with every candidate
 off, then one per (pattern, weight) with only that pattern on: pattern, weight, accuracy@1, mrr, gained@1 / lost@1 against the baseline,
-the eight reason counts; `--early-confusables` weights before pruning.
+the eight reason counts; `--early-confusables` weights before pruning.  With `--fit` the candidates' weights are fitted instead
+(fit_confusables: greedy coordinate ascent over `--candidate-weights`, late confusables only; `--fit-objective acc1|mrr`, `--fit-rounds`,
+`--fit-min-gain`): the start line (`-`), one line per accepted round -- pattern, weight, accuracy@1, mrr, ranked pairs -- and a `# stop:`
+line; `--fit-output OUT.tsv` writes the fitted confusable list.
 Not mirrored: index mode,
 --interactive buffering semantics (output is flushed per batch).  `--progress` prints the reference's "@ N - processing speed
 was R items per second" lines to stderr after every batch (bin:638-654).  `--unicode-offsets` is accepted and, as in the reference
@@ -171,6 +174,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--candidates", default=None, metavar="LIST.tsv",
                    help="sweep mode: a confusable list of candidate patterns (at most 64; the weight column is ignored): every candidate is tried alone at every --candidate-weights value")
     p.add_argument("--candidate-weights", default=None, metavar="W,W,..", help="sweep mode, with --candidates: the weights to try, comma-separated (each finite, above 0)")
+    p.add_argument("--fit", action="store_true",
+                   help="sweep mode, with --candidates: fit the candidates' weights on the device by greedy coordinate ascent over --candidate-weights (late confusables only) "
+                        "instead of printing the table: the start line, one line per accepted round, the stop reason")
+    p.add_argument("--fit-objective", choices=("acc1", "mrr"), default="acc1", help="sweep --fit: what a round improves, accuracy@1 (ties by MRR) or MRR (ties by accuracy@1)")
+    p.add_argument("--fit-rounds", type=int, default=16, help="sweep --fit: accepted rounds at most (1..256)")
+    p.add_argument("--fit-min-gain", type=float, default=None, metavar="G",
+                   help="sweep --fit: the least gain a round must bring, in pairs (acc1, default 1) or in reciprocal rank summed over the pairs (mrr, default 0: any improvement)")
+    p.add_argument("--fit-output", default=None, metavar="OUT.tsv", help="sweep --fit: write the fitted confusable list (`pattern<TAB>weight`, the patterns at 1.0 left out) to this file")
     p.add_argument("--index-cache", default=None, help="image of the built model: loaded if the file exists (lexicons are then not read), written after build() otherwise")
     p.add_argument("--device", type=int, default=None)
     p.add_argument("--single-thread", "-1", action="store_true", help="accepted for compatibility, no effect")
@@ -726,10 +737,81 @@ def run_sweep_candidates(model, a, out) -> None:
             f.write("\n")
 
 
+def fit_args_error(a) -> Optional[str]:
+    """What is wrong with a `sweep --fit` command line, before any file is read; None: nothing."""
+    if not a.fit:
+        if a.fit_output:
+            return "--fit-output needs --fit"
+        return None
+    if not a.candidates:
+        return "--fit needs --candidates LIST.tsv and --candidate-weights W,W,.."
+    if a.early_confusables:
+        return "--fit weights the candidates after pruning (late confusables) only: drop --early-confusables"
+    if a.grid:
+        return "sweep takes --grid or --candidates, not both (the candidates run under the command line's parameters)"
+    if not 1 <= a.fit_rounds <= 256:
+        return "--fit-rounds must be in 1..256"
+    gain = fit_min_gain_of(a)
+    if not gain >= 0.0 or gain == float("inf") or (a.fit_objective == "acc1" and gain != int(gain)):
+        return "--fit-min-gain is a number >= 0 (acc1: a whole number of pairs)"
+    return None
+
+
+def fit_min_gain_of(a) -> float:
+    return float(a.fit_min_gain) if a.fit_min_gain is not None else (1.0 if a.fit_objective == "acc1" else 0.0)
+
+
+def fit_tsv_line(pattern: str, weight: float, c: dict) -> str:
+    """One line of `sweep --fit`: pattern (`-`: the start), weight, accuracy@1, MRR, ranked pairs.  c: VariantModel.fit_counts_summary."""
+    return "\t".join([pattern, rust_f64(weight), rust_f64(c["accuracy_at_1"]), rust_f64(c["mrr"]), str(c["ranked"])])
+
+
+def fit_list_text(weights: dict) -> str:
+    """The fitted list as read_confusablelist reads it: `pattern<TAB>weight`, the weight printed so that it reads back bit for bit."""
+    return "".join("%s\t%s\n" % (p, repr(float(w))) for p, w in weights.items())
+
+
+def run_sweep_fit(model, a, out) -> None:
+    """`sweep --candidates --fit`: fit_confusables over the `input<TAB>gold` lines under the command line's parameters."""
+    import json
+    try:
+        with open(a.candidates, encoding="utf-8", newline="") as f:
+            patterns = parse_candidates(f.read().split("\n"))
+        grid = parse_candidate_weights(a.candidate_weights)
+        if len(grid) > 16:
+            raise ValueError("candidate weights: %d weights, --fit takes 16 at most" % len(grid))
+    except ValueError as e:
+        sys.stderr.write("ERROR: %s\n" % e)
+        sys.exit(2)
+    pa: List[str] = []
+    pg: List[str] = []
+    for line in _lines(a.files):
+        x, _, y = (line[:-1] if line.endswith("\r") else line).partition("\t")
+        pa.append(x)
+        pg.append(y.split("\t", 1)[0])
+    gain = fit_min_gain_of(a)
+    fit = model.fit_confusables(pa, pg, patterns, make_params(a), grid, None, a.fit_objective, a.fit_rounds, int(gain) if a.fit_objective == "acc1" else gain)
+    out.write(fit_tsv_line("-", 1.0, fit["start"]) + "\n")
+    for r in fit["rounds"]:
+        out.write(fit_tsv_line(r["pattern"], r["weight"], r) + "\n")
+    out.write("# stop: %s after %d rounds\n" % ("no trial improves the objective" if fit["stop"] == "converged" else "--fit-rounds reached", len(fit["rounds"])))
+    out.flush()
+    if a.fit_output:
+        with open(a.fit_output, "w", encoding="utf-8", newline="") as f:
+            f.write(fit_list_text(fit["weights"]))
+    if a.summary_json:
+        with open(a.summary_json, "w") as f:
+            json.dump(fit, f, indent=1)
+            f.write("\n")
+
+
 def run_sweep(model, a, out) -> None:
     """`sweep`: the `input<TAB>gold` lines of the input under every parameter set of --grid in one evaluate_sweep call: one TSV line per
     set (sweep_tsv_line), in grid order; --summary-json: the same as a JSON list (the set's parameters under "params")."""
     import json
+    if a.fit:
+        run_sweep_fit(model, a, out)
+        return
     if a.candidates:
         run_sweep_candidates(model, a, out)
         return
@@ -775,6 +857,9 @@ def main(argv=None) -> int:
         weights = Weights(ld=a.weight_ld, lcs=a.weight_lcs, prefix=a.weight_prefix, suffix=a.weight_suffix, case=a.weight_case)
         run_mine(VariantModel(a.alphabet, weights, debug=a.debug, device=a.device), a, sys.stdout)
         return 0
+    if a.mode == "sweep" and fit_args_error(a):
+        sys.stderr.write("ERROR: %s\n" % fit_args_error(a))
+        return 2
     model = make_model(a)
     params = make_params(a)
     out = sys.stdout

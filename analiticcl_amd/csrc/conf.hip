@@ -333,15 +333,7 @@ __global__ __launch_bounds__(256) void k_conf_apply_early(ConfArgs a) {
   if (w != 1.0) a.c_rows[slot].score *= w;
 }
 
-__device__ inline double conf_vr_score(const DevRow& r, float fw) {  // src/types.rs:335-341
-  if (fw == 0.0f) return r.dist_score;
-  return (r.dist_score + ((double)fw * r.freq_score)) / (1.0 + (double)fw);
-}
-__device__ inline bool conf_before(const DevRow& x, const DevRow& y, float fw) {  // rank_cmp, src/types.rs:344-365: x strictly before y
-  if (fw > 0.0f) return conf_vr_score(x, fw) > conf_vr_score(y, fw);
-  if (x.dist_score != y.dist_score) return x.dist_score > y.dist_score;
-  return x.freq_score > y.freq_score;
-}
+#include "conf_rank.hpp"  // conf_vr_score, conf_before
 // late mode: one lane per query: weight the ranked rows, stable re-sort, cutoff (src/lib.rs:1591-1622), new count
 __global__ __launch_bounds__(256) void k_conf_apply_late(ConfArgs a, uint32_t* __restrict__ r_count) {
   const uint32_t s = blockIdx.x * 256 + threadIdx.x;

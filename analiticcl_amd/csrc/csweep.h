@@ -33,6 +33,24 @@ int csweep_group_begin(CsCall* c, const SweepChunkView& v, const anx_params& gro
 // then k_conf_apply_late (stable re-sort, p's cutoff).  The chunk's counts are ADDED to *sum; out may be nullptr (needs want_records).
 // One download, one wait, no edit script.
 int csweep_group_set(CsGroup* g, const anx_params& p, size_t set, bool early, bool baseline, anx_gold_summary* sum, anx_gold_eval* out, std::string& err);
+// The front of a late set by itself, for the confusable fit (fit.hip): the unweighted rows with a score >= p.score_threshold through
+// k_rank under p's max_matches / freq_weight without a cutoff -- the cropped lists every late weight assignment re-ranks.  Enqueued on the
+// chunk's stream, no wait; k_conf_apply_late has NOT run.  The view's arrays are the group's and live until csweep_group_end.
+struct DevRow;
+struct CsRankedView {
+  const DeviceLexicon* dl;
+  void* stream;
+  size_t n, R;                     // pairs of the chunk; base rows of the group (the capacity of r_rows)
+  const void* info;                // [R] uint4 {pair, ., ., vocabulary id} per base row
+  const unsigned long long* mask;  // [R] the base rows' match masks
+  const uint32_t *rbeg, *rend;     // [n] the pair's range of base rows
+  const uint32_t* soff;            // [n + 1] where the pair's ranked rows begin in r_rows
+  const uint32_t* r_count;         // [n] ranked rows of the pair
+  const uint32_t* gid;             // [n] gold id or 0xFFFFFFFF
+  const DevRow* r_rows;
+  uint32_t* scan_tmp;              // prefix_scan_tmp_bytes(n), free once the rank is enqueued
+};
+int csweep_group_rank_late(CsGroup* g, const anx_params& p, CsRankedView* out, std::string& err);
 // anx_debug_sweep_conf_masks: the group's base rows as (pair, vocabulary id, mask); rows without a pair are left out
 int csweep_group_masks(CsGroup* g, std::vector<uint32_t>& pair, std::vector<uint32_t>& vocab, std::vector<uint64_t>& mask, std::string& err);
 void csweep_group_end(CsGroup* g);

@@ -27,6 +27,8 @@
 //     k_conf_apply_late : conf.hip's kernel (conf_apply_late_enqueue): multiply, stable re-sort, cutoff -- not restated
 //     k_rw_classify : reweigh.hip's kernel (reweigh_group_finish) with the model's weights: THRESHOLD from the direct pair's unweighted
 //                     score, the top row's weighted dist_score, the integer reduction; 624 bytes down (+ 32 n with the records)
+// The front of a late set -- k_cs_count .. k_rank -- is also csweep_group_rank_late's: the confusable fit (fit.hip) cuts its state from
+// the unweighted cropped lists and runs neither k_cs_slot_w nor k_conf_apply_late on them.
 // w(mask, set) = 1.0 times the set's weights of the set bits in ascending pattern order, f64, -ffp-contract=off; the set's weights reach
 // the lanes through LDS.  Every append is bounds-checked against the scan's own offsets and the row capacity.
 #include <hip/hip_runtime.h>
@@ -632,11 +634,12 @@ int csweep_group_begin(CsCall* c, const SweepChunkView& v, const anx_params& gro
   return ANX_OK;
 }
 
-int csweep_group_set(CsGroup* cg, const anx_params& p, size_t set, bool early, bool baseline, anx_gold_summary* sum, anx_gold_eval* out, std::string& err) {
+namespace {
+// The front of a set: the rows with an unweighted score >= p.score_threshold as SurvRow (early: score times the weight of the row's mask
+// under set `set`), then k_rank -- late without a cutoff, as the batch path ranks before k_conf_apply_late.  k: the set's kernel arguments.
+int cs_rank_enqueue(CsGroup* cg, const anx_params& p, size_t set, bool early, CsSetArgs& k, std::string& err) {
   RwGroup* g = cg->g;
   const CsCall* c = cg->call;
-  if (out && !g->d_out) { err = "csweep_group_set: the group keeps no record buffer"; return ANX_EINVAL; }
-  if (set >= c->n_sets) { err = "csweep_group_set: no such set"; return ANX_EINVAL; }
   const SweepChunkView& v = g->v;
   const size_t n = g->n, R = g->R;
   HIP_TRY(hipSetDevice(v.dl->device));
@@ -644,7 +647,6 @@ int csweep_group_set(CsGroup* cg, const anx_params& p, size_t set, bool early, b
   HIP_TRY(hipMemsetAsync(g->cnt, 0, n * sizeof(uint32_t), st));
   HIP_TRY(hipMemsetAsync(g->r_count, 0, n * sizeof(uint32_t), st));
   HIP_TRY(hipMemsetAsync(g->d_sum, 0, sizeof(anx_gold_summary), st));
-  CsSetArgs k{};
   k.n = (uint32_t)n; k.R = (uint32_t)R; k.info = g->info; k.score = g->score; k.mask = cg->mask;
   k.weights = c->d_weights + set * c->np; k.np = c->np; k.early = early ? 1 : 0; k.score_threshold = p.score_threshold;
   k.cnt = g->cnt; k.soff = g->soff; k.cur = g->cur; k.c_rows = reinterpret_cast<uint4*>(g->c_rows); k.row_cap = (uint32_t)R;
@@ -663,6 +665,31 @@ int csweep_group_set(CsGroup* cg, const anx_params& p, size_t set, bool early, b
                       g->t_key, g->r_rows, g->r_count, (uint32_t)R, g->ovf);
     ktimer_end(kt, st);
   }
+  return ANX_OK;
+}
+}  // namespace
+
+int csweep_group_rank_late(CsGroup* cg, const anx_params& p, CsRankedView* out, std::string& err) {
+  RwGroup* g = cg->g;
+  CsSetArgs k{};
+  if (int rc = cs_rank_enqueue(cg, p, 0, false, k, err)) return rc;
+  HIP_TRY(hipGetLastError());
+  out->dl = g->v.dl; out->stream = g->v.stream; out->n = g->n; out->R = g->R;
+  out->info = g->info; out->mask = cg->mask; out->rbeg = cg->rbeg; out->rend = cg->rend; out->soff = g->soff; out->r_count = g->r_count;
+  out->gid = g->v.gid; out->r_rows = g->r_rows; out->scan_tmp = g->tmp;
+  return ANX_OK;
+}
+
+int csweep_group_set(CsGroup* cg, const anx_params& p, size_t set, bool early, bool baseline, anx_gold_summary* sum, anx_gold_eval* out, std::string& err) {
+  RwGroup* g = cg->g;
+  const CsCall* c = cg->call;
+  if (out && !g->d_out) { err = "csweep_group_set: the group keeps no record buffer"; return ANX_EINVAL; }
+  if (set >= c->n_sets) { err = "csweep_group_set: no such set"; return ANX_EINVAL; }
+  const SweepChunkView& v = g->v;
+  const size_t n = g->n, R = g->R;
+  hipStream_t st = reinterpret_cast<hipStream_t>(v.stream);
+  CsSetArgs k{};
+  if (int rc = cs_rank_enqueue(cg, p, set, early, k, err)) return rc;
   if (!early) {
     if (R) {
       const int kt = ktimer_begin("k_cs_slot_w", st);

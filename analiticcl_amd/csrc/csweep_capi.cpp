@@ -55,8 +55,10 @@ bool model_weights_score_numbers(const anx_weights& w) {
   const double sum = w.ld + w.lcs + w.prefix + w.suffix + w.casew;
   return std::isfinite(mag) && sum != 0.0;
 }
+}  // namespace
 // the candidate patterns through the list parser, flattened as a model's list is; the weights in the tables are 1.0 (the sets carry them)
-int parse_patterns(const char* const* patterns, size_t n_patterns, anx::HostModel::ConfTables& t) {
+// (also the confusable fit's, fit_capi.cpp)
+int anx_csweep_parse_patterns(const char* const* patterns, size_t n_patterns, anx::HostModel::ConfTables& t) {
   if (!patterns) return anx_fail(ANX_EINVAL, "NULL argument");
   if (n_patterns == 0 || n_patterns > ANX_SWEEP_CONF_MAX_PATTERNS) return anx_fail(ANX_EINVAL, "confusable sweep: the number of patterns is outside 1 .. 64");
   std::vector<anx::Confusable> list(n_patterns);
@@ -68,6 +70,7 @@ int parse_patterns(const char* const* patterns, size_t n_patterns, anx::HostMode
   anx::conf_tables_build(list, t);
   return ANX_OK;
 }
+namespace {
 
 // one chunk: pairs [lo, lo + cnt) of the call's n
 int chunk_run(anx_model* m, anx::CsCall* call, const char* const* in, const anx::PairSpan* sa, const anx::PairSpan* sg, size_t lo, size_t cnt, size_t n, const Tail& t,
@@ -128,8 +131,9 @@ int run_call(anx_model* m, const char* const* in, const std::vector<anx::PairSpa
   }
   return ANX_OK;
 }
-// what is refused because of the model, before the device is asked for
-int check_model(anx_model* m, const char* who) {
+}  // namespace
+// what is refused because of the model, before the device is asked for (also the confusable fit's, fit_capi.cpp)
+int anx_csweep_check_model(anx_model* m, const char* who) {
   const anx::HostModel& h = anx_learn_host(m);
   if (!h.built) return anx_fail(ANX_ENOTBUILT, std::string("Model has not been built yet! Call build() before ") + who + "()");
   if (h.lex.any_variants)
@@ -142,12 +146,13 @@ int check_model(anx_model* m, const char* who) {
     return anx_fail(ANX_ENODEVICE, "model is not resident on a device (no HIP device / anx_model_to_device not called)");
   return ANX_OK;
 }
+namespace {
 // everything but the strings themselves; *run = false: the call is answered already (code in the return value)
 int check_call(anx_model* m, const void* a, const void* g, size_t n, const Tail& t, anx::HostModel::ConfTables& tables, bool* run) {
   *run = false;
   if (!m || !t.sets || !t.weights || !t.summaries || !t.patterns) return anx_fail(ANX_EINVAL, "NULL argument");
   if (t.n_sets == 0 || t.n_sets > ANX_SWEEP_MAX_SETS) return anx_fail(ANX_EINVAL, "confusable sweep: the number of sets is outside 1 .. 256");
-  if (int rc = parse_patterns(t.patterns, t.n_patterns, tables)) return rc;
+  if (int rc = anx_csweep_parse_patterns(t.patterns, t.n_patterns, tables)) return rc;
   for (size_t s = 0; s < t.n_sets; ++s)
     for (size_t j = 0; j < t.n_patterns; ++j) {
       const double w = t.weights[s * t.n_patterns + j];
@@ -157,7 +162,7 @@ int check_call(anx_model* m, const void* a, const void* g, size_t n, const Tail&
   memset(t.summaries, 0, t.n_sets * sizeof(anx_gold_summary));
   if (n == 0) return ANX_OK;
   if (!a || !g) return anx_fail(ANX_EINVAL, "NULL argument");
-  if (int rc = check_model(m, "evaluate_sweep_confusables")) return rc;
+  if (int rc = anx_csweep_check_model(m, "evaluate_sweep_confusables")) return rc;
   *run = true;
   return ANX_OK;
 }
@@ -205,8 +210,8 @@ int anx_debug_sweep_conf_masks(anx_model* m, const char* const* inputs, size_t n
   if (!m || !inputs || !group || !pair || !vocab || !mask || !rows) return anx_fail(ANX_EINVAL, "NULL argument");
   if (n == 0 || n > anx::PAIRS_CHUNK) return anx_fail(ANX_EINVAL, "anx_debug_sweep_conf_masks: 1 .. 2^20 inputs");
   anx::HostModel::ConfTables tables;
-  if (int rc = parse_patterns(patterns, n_patterns, tables)) return rc;
-  if (int rc = check_model(m, "anx_debug_sweep_conf_masks")) return rc;
+  if (int rc = anx_csweep_parse_patterns(patterns, n_patterns, tables)) return rc;
+  if (int rc = anx_csweep_check_model(m, "anx_debug_sweep_conf_masks")) return rc;
   std::vector<anx::PairSpan> sa;
   if (!anx::spans_of_pointers(inputs, n, sa)) return anx_fail(ANX_EINVAL, "NULL string");
   std::lock_guard<std::mutex> lk(anx_learn_mutex());
@@ -244,7 +249,7 @@ int anx_debug_sweep_conf_masks(anx_model* m, const char* const* inputs, size_t n
 int anx_debug_conf_mask_text(const char* const* patterns, size_t n_patterns, const char* a, const char* b, uint64_t* mask) {
   if (!a || !b || !mask) return anx_fail(ANX_EINVAL, "NULL argument");
   anx::HostModel::ConfTables tables;
-  if (int rc = parse_patterns(patterns, n_patterns, tables)) return rc;
+  if (int rc = anx_csweep_parse_patterns(patterns, n_patterns, tables)) return rc;
   *mask = anx::confusable_mask_text(tables, a, strlen(a), b, strlen(b));
   return ANX_OK;
 }

@@ -1079,6 +1079,116 @@ class VariantModel:
         L.check(L.lib().anx_debug_conf_sweep_stats(out, len(keys)))
         return {k: int(out[i]) for i, k in enumerate(keys)}
 
+    # -- confusable fit ----------------------------------------------------------------------------------
+    FIT_COUNTS_DTYPE = [("at1", "<u8"), ("ranked", "<u8"), ("rr_fixed", "<u8")]
+    FIT_ROUND_DTYPE = [("pattern", "<u4"), ("grid_index", "<u4"), ("weight", "<f8"), ("counts", FIT_COUNTS_DTYPE)]
+    FIT_RESULT_DTYPE = [("n_rounds", "<u4"), ("n_trial_rounds", "<u4"), ("stop", "<u4"), ("_pad", "<u4"), ("start", FIT_COUNTS_DTYPE),
+                        ("final", FIT_COUNTS_DTYPE)]
+
+    @staticmethod
+    def fit_min_gain(objective: str, min_gain) -> int:
+        """min_gain in the units of the objective's first key component: pairs for "acc1", reciprocal rank as 32.32 fixed point for "mrr"."""
+        if objective not in L.FIT_OBJECTIVES:
+            raise ValueError("fit_confusables: objective is 'acc1' or 'mrr'")
+        if not (float(min_gain) >= 0.0) or float(min_gain) == float("inf"):
+            raise ValueError("fit_confusables: min_gain is a number >= 0")
+        if objective == "mrr":
+            return int(round(float(min_gain) * 4294967296.0))
+        if int(min_gain) != min_gain:
+            raise ValueError("fit_confusables: for objective 'acc1' min_gain counts pairs: an integer")
+        return int(min_gain)
+
+    def fit_confusables_arrays(self, inputs: Sequence[str], gold: Sequence[str], patterns: Sequence[str], params: SearchParameters,
+                               grid: Sequence[float], start: Optional[Sequence[float]] = None, objective: str = "acc1", max_rounds: int = 16,
+                               min_gain=1, with_trials: bool = False, packed: bool = True, chunk: Optional[int] = None):
+        """anx_fit_confusable_weights: a greedy coordinate ascent over the weights of the candidate patterns (late mode), on the
+        device.  A round tries every (pattern, grid weight) that differs from the current weights; the best trial by (at1, rr_fixed)
+        -- "mrr": (rr_fixed, at1) -- is accepted when it improves the key and gains at least min_gain in its first component
+        (pairs; "mrr": reciprocal rank, a float); the fit ends when none is accepted (stop 0) or after max_rounds accepted rounds
+        (stop 1).  Every count equals what evaluate_sweep_confusables_arrays gives for the same weights.  Returns (weights[J] f64,
+        rounds (FIT_ROUND_DTYPE, the accepted ones), result (FIT_RESULT_DTYPE, one element)[, trials[n_trial_rounds][J][G]
+        (FIT_COUNTS_DTYPE)]).  packed = False: the pointer form; chunk: the test hook (pointer form)."""
+        import numpy as np
+        n, J, G = len(inputs), len(patterns), len(grid)
+        if len(gold) != n:
+            raise ValueError("fit_confusables: inputs and gold differ in length")
+        if start is not None and len(start) != J:
+            raise ValueError("fit_confusables: start needs one weight per pattern")
+        gain = self.fit_min_gain(objective, min_gain)
+        max_rounds = int(max_rounds)
+        room = min(max(max_rounds, 1), L.FIT_MAX_ROUNDS)   # (a max_rounds outside 1 .. 256 is the library's to refuse)
+        ga = np.ascontiguousarray(np.asarray([float(x) for x in grid], dtype=np.float64))
+        sa = None if start is None else np.ascontiguousarray(np.asarray([float(x) for x in start], dtype=np.float64))
+        dp = C.POINTER(C.c_double)
+        fp = L.FitParams(ga.ctypes.data_as(dp) if G else (C.c_double * 1)(1.0), G, 0, sa.ctypes.data_as(dp) if sa is not None and J else None,
+                         L.FIT_OBJECTIVES[objective], max_rounds & 0xFFFFFFFF, gain)
+        weights = np.zeros(max(J, 1), dtype=np.float64)
+        rounds = np.zeros(room, dtype=np.dtype(self.FIT_ROUND_DTYPE))
+        result = np.zeros(1, dtype=np.dtype(self.FIT_RESULT_DTYPE))
+        trials = np.zeros((room, max(J, 1), max(G, 1)), dtype=np.dtype(self.FIT_COUNTS_DTYPE)) if with_trials else None
+        assert rounds.dtype.itemsize == C.sizeof(L.FitRound) and result.dtype.itemsize == C.sizeof(L.FitResult)
+        tail = (C.byref(fp), weights.ctypes.data_as(dp), rounds.ctypes.data_as(C.POINTER(L.FitRound)),
+                trials.ctypes.data_as(C.POINTER(L.FitCounts)) if with_trials else None, result.ctypes.data_as(C.POINTER(L.FitResult)))
+        pats = (C.c_char_p * max(J, 1))(*[_b(t) for t in patterns])
+        cp = params._c()
+        if packed and chunk is None:
+            ba, bg = _pack(inputs), _pack(gold)
+            L.check(L.lib().anx_fit_confusable_weights_packed(self.h, ba, len(ba), bg, len(bg), n, pats, J, C.byref(cp), *tail))
+        else:
+            aa = (C.c_char_p * max(n, 1))(*[_b(t) for t in inputs])
+            ag = (C.c_char_p * max(n, 1))(*[_b(t) for t in gold])
+            if chunk is None:
+                L.check(L.lib().anx_fit_confusable_weights(self.h, aa, ag, n, pats, J, C.byref(cp), *tail))
+            else:
+                L.check(L.lib().anx_debug_fit_confusable_weights_chunk(self.h, aa, ag, n, pats, J, C.byref(cp), *tail, int(chunk)))
+        res = (weights[:J], rounds[:int(result[0]["n_rounds"])], result)
+        return res + (trials[:int(result[0]["n_trial_rounds"]), :J, :G],) if with_trials else res
+
+    @staticmethod
+    def fit_counts_summary(c, n: int) -> dict:
+        """An anx_fit_counts as a dict, accuracy_at_1, ranked_share and mrr derived as sweep_summary derives them."""
+        at1, ranked, rr = int(c["at1"]), int(c["ranked"]), int(c["rr_fixed"])
+        return {"at1": at1, "ranked": ranked, "rr_fixed": rr, "accuracy_at_1": at1 / n if n else 0.0, "ranked_share": ranked / n if n else 0.0,
+                "mrr": rr / 4294967296.0 / n if n else 0.0}
+
+    def fit_confusables(self, inputs: Sequence[str], gold: Sequence[str], patterns: Sequence[str], params: SearchParameters,
+                        grid: Sequence[float], start: Optional[Sequence[float]] = None, objective: str = "acc1", max_rounds: int = 16,
+                        min_gain=1) -> dict:
+        """fit_confusables_arrays as a dict: "weights" (pattern -> weight, the patterns at 1.0 left out), "rounds" (one dict per
+        accepted round: pattern, grid_index, weight and the counts after it), "start" and "final" (fit_counts_summary), "stop"
+        ("converged": no trial was accepted; "max_rounds"), "n_trial_rounds"."""
+        n = len(inputs)
+        weights, rounds, result = self.fit_confusables_arrays(inputs, gold, patterns, params, grid, start, objective, max_rounds, min_gain)
+        r = result[0]
+        return {"weights": {p: float(w) for p, w in zip(patterns, weights) if float(w) != 1.0},
+                "rounds": [dict(self.fit_counts_summary(x["counts"], n), pattern=patterns[int(x["pattern"])], grid_index=int(x["grid_index"]),
+                                weight=float(x["weight"])) for x in rounds],
+                "start": self.fit_counts_summary(r["start"], n), "final": self.fit_counts_summary(r["final"], n),
+                "stop": "max_rounds" if int(r["stop"]) else "converged", "n_trial_rounds": int(r["n_trial_rounds"])}
+
+    @staticmethod
+    def fit_select(trials, cur: Sequence[float], grid: Sequence[float], cur_counts, objective: str = "acc1", min_gain: int = 1):
+        """anx_debug_fit_select (host only): the selection of one round.  trials[J][G] and cur_counts are (at1, ranked, rr_fixed)
+        triples; min_gain in the key's own units.  Returns (pattern, grid_index), (-1, -1) when no trial is accepted."""
+        J, G = len(cur), len(grid)
+        flat = [t for row in trials for t in row]
+        if len(trials) != J or len(flat) != J * G:
+            raise ValueError("fit_select: trials is [patterns][grid]")
+        tt = (L.FitCounts * max(J * G, 1))(*[L.FitCounts(*[int(x) for x in t]) for t in flat])
+        cc = L.FitCounts(*[int(x) for x in cur_counts])
+        pj, pg = C.c_int32(0), C.c_int32(0)
+        L.check(L.lib().anx_debug_fit_select(tt, (C.c_double * max(J, 1))(*[float(x) for x in cur]), J, (C.c_double * max(G, 1))(*[float(x) for x in grid]), G,
+                                             C.byref(cc), L.FIT_OBJECTIVES[objective], int(min_gain), C.byref(pj), C.byref(pg)))
+        return int(pj.value), int(pg.value)
+
+    @staticmethod
+    def fit_stats() -> dict:
+        """anx_debug_fit_stats: running totals of the fit calls since process start."""
+        keys = ("calls", "chunks", "rounds", "trial_launches", "state_pairs", "state_slots", "bytes_down")
+        out = (C.c_uint64 * len(keys))()
+        L.check(L.lib().anx_debug_fit_stats(out, len(keys)))
+        return {k: int(out[i]) for i, k in enumerate(keys)}
+
     def query_output(self, inputs: Sequence[str], params: SearchParameters, json: bool = False,
                      output_lexmatch: bool = False, first_seqnr: int = 1) -> str:
         """One device batch + the text `analiticcl query` prints for it (anx_format_query_output: the TSV lines or JSON

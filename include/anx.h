@@ -51,7 +51,9 @@ extern "C" {
  *    anx_debug_scan_pairs and its options struct anx_debug_scan_opts: additive; anx_evaluate_sweep_weights / _packed and the hooks
  *    anx_debug_evaluate_sweep_weights_chunk / anx_debug_weight_sweep_stats: sets that also differ in the score weights (additive);
  *    anx_evaluate_sweep_confusables / _packed and the hooks anx_debug_evaluate_sweep_confusables_chunk / anx_debug_sweep_conf_masks /
- *    anx_debug_conf_mask_text / anx_debug_conf_sweep_stats: candidate confusable patterns with a weight per set (additive). */
+ *    anx_debug_conf_mask_text / anx_debug_conf_sweep_stats: candidate confusable patterns with a weight per set (additive);
+ *    anx_fit_confusable_weights / _packed, the structs anx_fit_* and the hooks anx_debug_fit_confusable_weights_chunk /
+ *    anx_debug_fit_select / anx_debug_fit_stats: the weights of candidate patterns fitted on the device (additive). */
 #define ANX_ABI_VERSION 3
 
 enum {
@@ -942,6 +944,70 @@ int anx_debug_conf_mask_text(const char *const *patterns, size_t n_patterns, con
  * when a group's mask pass ends: a set adds none), [8] of those, rows the host computed because the device could not hold them,
  * [9] rows the host computed under ANX_CONFUSABLES=host, [10] bytes the sets downloaded. */
 int anx_debug_conf_sweep_stats(uint64_t *out, int n);
+
+/* ---- confusable fit: a greedy coordinate ascent over the weights of candidate patterns, on the device (late mode only) ---------------
+ * anx_fit_counts for a weight assignment w holds three fields of the anx_gold_summary that anx_evaluate_sweep_confusables returns for the
+ * set (params, w, late) over the same pairs: at1 == rank_hist[0], ranked == reasons[ANX_GOLD_RANKED], rr_fixed == rr_fixed.
+ * A round: every (pattern j, grid index g) with grid[g] != cur[j] is a trial "cur with cur[j] = grid[g]".  The key of a trial is
+ * (at1, rr_fixed) under ANX_FIT_ACC1 and (rr_fixed, at1) under ANX_FIT_MRR, compared lexicographically as uint64; the best trial has the
+ * largest key, ties go to the smallest j, then the smallest g.  It is accepted iff its key is greater than the current key and its
+ * first component exceeds the current one by at least min_gain (min_gain == 0: any lexicographic improvement).  On acceptance
+ * cur[j] = grid[g] and the round is appended to rounds.  The fit ends when no trial is accepted (stop = 0) or when max_rounds rounds
+ * were accepted (stop = 1).  A pattern may be revisited; a grid holding 1.0 can switch a pattern off again.
+ * weights_out: the final cur, every value start[j] or a grid value bit for bit.  trials (may be NULL): trials[r][j][g] = the counts of
+ * every trial of evaluated round r < n_trial_rounds, a skipped trial (grid[g] == cur[j]) holding the current counts.  result->start /
+ * final: the counts under the start weights and under weights_out.
+ * How: in late mode the cropped list of an input does not depend on the list's weights (src/lib.rs:1535-1622: crop, then weights,
+ * stable re-sort, cutoff), so per chunk the base run, the masks and the unweighted late ranking of the confusable sweep run ONCE, and
+ * what stays resident is 24 bytes per ranked slot of the pairs whose gold is in the cropped list and 12 bytes per pair (fit.hip
+ * k_fit_gold / k_fit_state).  A round is one launch of k_fit_trials per chunk -- every trial of every pair, gold's place found by
+ * counting, no k_rank, no classification -- and one download of at most 26 KB.
+ * Errors, each before the device is asked for: ANX_EINVAL for NULL arguments, n_patterns outside 1 .. 64, a pattern the list parser
+ * rejects, n_grid outside 1 .. ANX_FIT_MAX_GRID, max_rounds outside 1 .. ANX_FIT_MAX_ROUNDS, an unknown objective, a grid or start weight
+ * that is not finite or not above 0, and what anx_evaluate_sweep_confusables refuses of a model (a variant list, a confusable list of its
+ * own, score weights that are not finite or sum to 0), a model with anx_model_set_confusables_before_pruning, confusables weighted on the
+ * host; ANX_ENOTBUILT / ANX_ENODEVICE as the sweep; ANX_ELIMIT above 2^24 pairs per call (16 chunks of resident state: a stated limit) and
+ * the sweep's other limits.  n == 0: ANX_OK, zero rounds, zero counts, weights_out = start, no build and no device.  The learn lock is
+ * held and the pass runs on replica 0.  _packed: the blobs as anx_evaluate_sweep_confusables_packed. */
+#define ANX_FIT_MAX_GRID 16
+#define ANX_FIT_MAX_ROUNDS 256
+#define ANX_FIT_MAX_PAIRS ((size_t)1 << 24)
+enum { ANX_FIT_ACC1 = 0, ANX_FIT_MRR = 1 };
+typedef struct anx_fit_counts { uint64_t at1, ranked, rr_fixed; } anx_fit_counts; /* 24 bytes */
+typedef struct anx_fit_params {
+  const double *grid; /* [n_grid] candidate weights, each finite and > 0; 1.0 = switch the pattern off */
+  uint32_t n_grid;    /* 1 .. ANX_FIT_MAX_GRID */
+  uint32_t _pad;
+  const double *start; /* NULL (all 1.0) or [n_patterns], finite and > 0 */
+  uint32_t objective;  /* ANX_FIT_ACC1 or ANX_FIT_MRR */
+  uint32_t max_rounds; /* 1 .. ANX_FIT_MAX_ROUNDS */
+  uint64_t min_gain;   /* in units of the key's first component (ANX_FIT_MRR: 32.32 fixed point) */
+} anx_fit_params;
+typedef struct anx_fit_round { uint32_t pattern, grid_index; double weight; anx_fit_counts counts; } anx_fit_round; /* 40 bytes */
+typedef struct anx_fit_result { uint32_t n_rounds, n_trial_rounds, stop, _pad; anx_fit_counts start, final; } anx_fit_result; /* 64 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(anx_fit_counts) == 24 && sizeof(anx_fit_round) == 40 && sizeof(anx_fit_result) == 64, "the fit's records");
+#else
+_Static_assert(sizeof(anx_fit_counts) == 24 && sizeof(anx_fit_round) == 40 && sizeof(anx_fit_result) == 64, "the fit's records");
+#endif
+int anx_fit_confusable_weights(anx_model *, const char *const *inputs, const char *const *gold, size_t n, const char *const *patterns,
+                               size_t n_patterns, const anx_params *, const anx_fit_params *, double *weights_out /* [n_patterns] */,
+                               anx_fit_round *rounds /* [max_rounds] */, anx_fit_counts *trials /* NULL or [max_rounds][n_patterns][n_grid] */,
+                               anx_fit_result *);
+int anx_fit_confusable_weights_packed(anx_model *, const char *blob_in, size_t len_in, const char *blob_gold, size_t len_gold, size_t n,
+                                      const char *const *patterns, size_t n_patterns, const anx_params *, const anx_fit_params *,
+                                      double *weights_out, anx_fit_round *rounds, anx_fit_counts *trials, anx_fit_result *);
+/* Test hook: the pointer form with a caller-chosen chunk size (1 .. 2^20 pairs). */
+int anx_debug_fit_confusable_weights_chunk(anx_model *, const char *const *inputs, const char *const *gold, size_t n,
+                                           const char *const *patterns, size_t n_patterns, const anx_params *, const anx_fit_params *,
+                                           double *weights_out, anx_fit_round *rounds, anx_fit_counts *trials, anx_fit_result *, size_t chunk);
+/* The selection of a round alone (host only): trials[n_patterns][n_grid], cur[n_patterns], the current counts -> the accepted trial in
+ * *pattern / *grid_index, or -1 / -1 when none is accepted.  A trial with grid[g] == cur[j] is never chosen. */
+int anx_debug_fit_select(const anx_fit_counts *trials, const double *cur, size_t n_patterns, const double *grid, size_t n_grid,
+                         const anx_fit_counts *cur_counts, uint32_t objective, uint64_t min_gain, int32_t *pattern, int32_t *grid_index);
+/* Running totals of the fit calls since process start, the first min(n, 7) of: [0] calls, [1] chunks, [2] rounds evaluated,
+ * [3] launches of k_fit_trials, [4] pairs in the state (gold in the cropped list), [5] slots in the state, [6] bytes downloaded. */
+int anx_debug_fit_stats(uint64_t *out, int n);
 
 /* ---- anx_mine_confusables: confusable patterns from (observed, correct) string pairs ---------------------------------------------------
  * For every pair (a[i], b[i]) the change sites of shortest_edit_script(a[i], b[i]) -- a site is a maximal run of consecutive non-`=`
